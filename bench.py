@@ -1,12 +1,20 @@
 """Benchmark of the hot path named in BASELINE.json: one acoustic substep = d_sw + riem_solver3 on one
 cubed-sphere tile per GPU, fp64, C192 x 79 levels, synthetic (baroclinic-like) state.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 192] [--nz 79]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 192] [--nz 79] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one d_sw call followed by one riem_solver3 call on one pristine, HBM-resident copy of the
-model state (K + W copies are staged before the timed region; nothing is re-used between steps, so no
-step benefits from cached data of the previous one).  Prints ONE JSON line on rank 0.
+model state (K + W copies are staged before the timed region, up to STATE_POOL_BYTES of them: more steps are
+timed in rounds, and the copies are restored between rounds; nothing is re-used between steps, so no step
+benefits from cached data of the previous one).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line.  --full adds
+what else the benchmark measures and checks after the timed region: the dominant kernel alone and its
+roofline (HBM traffic from two rocprofv3 --pmc child passes, stream bandwidths), the substep under d_sw's
+other output contract, the CPU baseline and the verification of the last timed step against the oracle,
+and the per-phase diagnosis of a multi-rank step.  --dump-outputs DIR writes what the last timed step
+computed (rank 0's tile) as DIR/<field>.npy: see dump_outputs.
 
 Multi-GPU: one tile per GPU, weak scaling.  With exactly 6 ranks the ranks ARE the six faces of the cube and the
 delp / pt / q_con halo exchange that sits between d_sw and riem_solver3 in the acoustic loop (dyn_core.py:854) runs
@@ -27,6 +35,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 BYTES_PER_CELL_UPDATE = 360.0  # d_sw 32 fields + riem_solver3 13 fields, fp64
 TRANSPORT_FIELDS = 9  # fused transport kernel: q, crx, cry, xfx, yfx, x/y mass flux, delp in; updated scalar out
+STATE_POOL_BYTES = 64 << 30  # device memory for the staged state copies (~90 copies at C192 x 79, fp64): a bound set by the arguments
+DUMP_VALUES_PER_FIELD = 1 << 18  # --dump-outputs: at most this many values per field (at most 29 fields x 2 MiB in fp64: < 64 MB in all)
 
 
 def parse():
@@ -47,6 +57,12 @@ def parse():
     p.add_argument("--full-outputs", action="store_true",
                    help="d_sw also brings its dead work fields (delpc, divgd, uc, vc) to the state the reference leaves them in, as "
                         "the last substep of a remapping step does (default: skipped, as in every other substep of AcousticDynamics)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region, also measure and check what the headline does not need: the dominant kernel's roofline, "
+                        "the other output contract, the CPU baseline + verification against the oracle, the multi-rank phase diagnosis "
+                        "(each of them can be left out again by its --no-* option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the output fields of the last timed step as DIR/<field>.npy (a fixed sample of each larger field)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes that measure roofline.traffic")
     p.add_argument("--no-other-contract", action="store_true",
@@ -348,6 +364,35 @@ def verify_against_oracle(got, ref, n, nz, skip=()):
     return ok, errs
 
 
+def dump_outputs(out_dir, b, n, nz, skip=()):
+    """--dump-outputs: the fields one step hands back to its caller, as the device left them in the state copy `b`, written as
+    out_dir/<field>.npy in the storage type (float64, or float32 for --precision 32).  d_sw's arguments over the windows its
+    contract specifies (those of verify_against_oracle; `skip`: the dead work fields a run did not ask for), riem_solver3's outputs
+    over the compute domain.  A window of more than DUMP_VALUES_PER_FIELD values is sampled: that many flat indices, drawn by a
+    generator seeded with the field's name and sorted, so the same arguments sample the same points in every run and build."""
+    import zlib
+
+    import torch
+
+    from pace_amd.tile import DSW_ARGS, dsw_live_window, dsw_window, window
+
+    fields = {}
+    for k in DSW_ARGS:
+        if k in ("zh", "w") or k in skip:  # (zh, w: riem_solver3 writes them last)
+            continue
+        fields[k] = dsw_live_window(k, n, nz) if skip else dsw_window(k, n, nz)
+    for k in ("delz", "zh", "pe", "ppe", "pk3", "pk", "peln", "w"):
+        fields[k] = window(n, 0, 0, nz if k in ("delz", "w") else nz + 1)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, W in fields.items():
+        a = b[k].data[W]
+        if a.numel() > DUMP_VALUES_PER_FIELD:
+            rng = np.random.default_rng(zlib.crc32(k.encode()))
+            idx = np.sort(rng.choice(a.numel(), DUMP_VALUES_PER_FIELD, replace=False))
+            a = a.reshape(-1)[torch.as_tensor(idx, device=a.device)]
+        np.save(os.path.join(out_dir, k + ".npy"), a.detach().cpu().numpy())
+
+
 def measure_traffic(kernel_substring, n, nz, precision=64):
     """HBM bytes per launch of the dominant kernel, measured NOW: this script is run twice more as a child under
     `rocprofv3 --kernel-trace --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, as MI355X_MICROARCH.md prescribes; no
@@ -370,7 +415,8 @@ def measure_traffic(kernel_substring, n, nz, precision=64):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__), "--steps", "3",
-                   "--warmup", "1", "--n", str(n), "--nz", str(nz), "--precision", str(precision), "--no-cpu-baseline", "--no-traffic", "--no-other-contract"]
+                   "--warmup", "1", "--n", str(n), "--nz", str(nz), "--precision", str(precision), "--full", "--no-cpu-baseline", "--no-traffic",
+                   "--no-other-contract"]
             p = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=240)
             if p.returncode != 0:
                 return None, f"rocprofv3 --pmc {counter} failed (rc {p.returncode}): {p.stderr[-300:]}"
@@ -631,7 +677,11 @@ def main():
             out[k] = c
         return out
 
-    batches = [clone_state() for _ in range(nbatch)]
+    # at most STATE_POOL_BYTES of copies: step i runs on copy i % len(batches); a run with more steps than copies times them in
+    # rounds of len(batches) steps and gives the copies their pristine state back between two rounds (outside the timed region)
+    batches = [clone_state()]
+    copy_bytes = sum(q._base.numel() * q._base.element_size() for q in batches[0].values())
+    batches += [clone_state() for _ in range(min(nbatch, max(1, STATE_POOL_BYTES // copy_bytes)) - 1)]
     torch.cuda.synchronize()
 
     # The halo exchange of the acoustic loop stays inside the measured step whenever there is more than one rank: on the
@@ -686,31 +736,51 @@ def main():
         torch.cuda.synchronize()
 
     use_graph = args.graph == "on"
+    stepped = set()  # copies that are no longer pristine
+
+    def refresh(slots):
+        again = [j for j in slots if j in stepped]
+        for j in again:
+            for k, q in base.items():
+                batches[j][k]._base.copy_(q._base)
+            stepped.discard(j)
+        if again:
+            torch.cuda.synchronize()
+
     arm("warm-up")
     for i in range(args.warmup):
-        step(batches[i])
-    runners = None
+        refresh([i % len(batches)])
+        step(batches[i % len(batches)])
+        stepped.add(i % len(batches))
+    timed = [i % len(batches) for i in range(args.warmup, nbatch)]  # the state copy of every timed step
+    graphs = None
     if use_graph:
         # one graph per state copy (a graph is bound to the buffers it was captured on); both streams of the step are
         # captured through the fork/join events.  Capturing launches nothing, so the copies stay pristine.
         torch.cuda.synchronize()
-        runners = []
-        for i in range(args.warmup, nbatch):
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                step(batches[i])
-            runners.append(gr)
+        graphs = {}
+        for j in timed:
+            if j not in graphs:
+                graphs[j] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[j]):
+                    step(batches[j])
     arm("timed loop")
-    barrier()
-    t0 = time.perf_counter()
-    if runners is not None:
-        for gr in runners:
-            gr.replay()
-    else:
-        for i in range(args.warmup, nbatch):
-            step(batches[i])
-    barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = 0.0
+    for r in range(0, len(timed), len(batches)):  # (one round unless the steps outnumber the copies)
+        rnd = timed[r:r + len(batches)]
+        refresh(rnd)
+        barrier()
+        t0 = time.perf_counter()
+        if graphs is not None:
+            for j in rnd:
+                graphs[j].replay()
+        else:
+            for j in rnd:
+                step(batches[j])
+        barrier()
+        elapsed += time.perf_counter() - t0
+        stepped.update(rnd)
+    last = batches[timed[-1]]  # what the last timed step computed
     arm("reduction + report")
     if world > 1:
         import torch.distributed as dist
@@ -719,17 +789,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
-    # Multi-rank diagnosis (NOT part of the timed region): the same step again with the device synchronised after every phase,
-    # max over ranks per phase -- where a 6-GPU step spends its time (pack + post, interior compute under the exchange, wait +
+    if args.dump_outputs and rank == 0:  # before anything below steps the copies again
+        dump_outputs(args.dump_outputs, last, n, nz, skip=DEAD_AFTER_DSW if skip_dead else ())
+    # Multi-rank diagnosis (--full; NOT part of the timed region): the same step again with the device synchronised after every
+    # phase, max over ranks per phase -- where a 6-GPU step spends its time (pack + post, interior compute under the exchange, wait +
     # unpack, the rest of d_sw, the scalar exchange, the column solver).  The phases overlap in the timed loop, so they sum to
     # more than ms_per_step.
     phase_ms = None
-    if exchange is not None:
+    if exchange is not None and args.full:
         arm("phase diagnosis")
         names = ["uc_vc_start(pack+post)", "flux_prep_interior", "uc_vc_wait(+unpack)", "d_sw_rest", "delp_pt_qcon_start(pack+post)",
                  "riem_solver3", "delp_pt_qcon_wait(+unpack)"]
         acc = np.zeros(len(names))
-        nd = min(3, nbatch)
+        nd = min(3, len(batches))
         for i in range(nd):
             b = batches[i]
             a_ = [b[k] for k in DSW_ARGS]
@@ -767,9 +839,9 @@ def main():
     value = world * cells * args.steps / elapsed
     # the last TIMED batch's fields as the device left them (taken now: the roofline loop below accumulates into mfx / mfy)
     got_last = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         torch.cuda.synchronize()
-        got_last = {k: batches[-1][k].numpy().astype(np.float64) for k in list(DSW_ARGS) + ["delz", "ppe", "pk3"]}
+        got_last = {k: last[k].numpy().astype(np.float64) for k in list(DSW_ARGS) + ["delz", "ppe", "pk3"]}
 
     # The OTHER output contract of d_sw, timed right here in the same way (not part of `value`): the line quotes the substep that
     # skips the divergence damping's dead work fields (7 of 8 substeps of a remapping step); the reference's full contract --
@@ -777,7 +849,7 @@ def main():
     # eighth.  (--full-outputs swaps the two.)  The state copies have been stepped once already: a second step of the same
     # arithmetic, same bytes.
     other_contract = None
-    if world == 1 and not use_graph and not args.no_other_contract:
+    if args.full and world == 1 and not use_graph and not args.no_other_contract:
         nb = min(10, len(batches))
 
         def step_other(b):
@@ -803,7 +875,7 @@ def main():
     # separate outputs).  Other tilings: the single-scalar transport kernel k_fvtp2d<6, 2, 1> through pace_fvtp2d_update (three of
     # the step's launches are instances of it).
     roof = None
-    if rank == 0 and not args.emulate:
+    if args.full and rank == 0 and not args.emulate:
         import ctypes as C
 
         from pace_amd.fv3core.stencils._common import dptr, host_column
@@ -827,7 +899,7 @@ def main():
             spare_sets = [[env.q3() for _ in range(6)] for _ in range(2)]
 
             def kernel(r):
-                b = batches[r % nbatch]  # a different state copy every launch: operands come from HBM, as inside a step
+                b = batches[r % len(batches)]  # a different state copy every launch: operands come from HBM, as inside a step
                 sp = spare_sets[r % 2]
                 c_ = dsw._cfg
                 c_.delp_out, c_.pt_out, c_.w_out, c_.q_con_out = (dptr(x) for x in sp[:4])
@@ -844,7 +916,7 @@ def main():
             out = env.q3()
 
             def kernel(r):
-                b = batches[r % nbatch]
+                b = batches[r % len(batches)]
                 lib.call("pace_fvtp2d_update", C.byref(geom), C.byref(env.grid_data.c_struct()), b["pt"].ptr, b["crx"].ptr, b["cry"].ptr,
                          b["xfx"].ptr, b["yfx"].ptr, b["mfx"].ptr, b["mfy"].ptr, b["delp"].ptr, kdev.data_ptr(),
                          kdev.data_ptr() + lib.real_bytes * nz, int(nord_t.max()), out.ptr, 6, nz, dsw.stream())
@@ -968,7 +1040,7 @@ def main():
                                           "sum(phases) - ms_per_step is what the overlap hides"}
             if full_loop is not None:
                 line["comm"]["full_loop"] = full_loop
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             try:
                 rec, ref = cpu_baseline(n, nz, metrics, s, dt, ptop)
             except Exception as e:  # noqa: BLE001 -- the measured line must not be lost to its CPU leg: say so

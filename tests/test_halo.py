@@ -395,7 +395,7 @@ def test_bench_six_ranks_dry_run_over_gloo(tmp_path):
     port = 35500 + os.getpid() % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "6", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "6", "--steps", "2", "--warmup", "1", "--tile-size", "12",
-           "--nz", "8", "--emulate", "--watchdog", "240"]
+           "--nz", "8", "--emulate", "--watchdog", "240", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", PACE_TRACE_CALLS="1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
@@ -480,3 +480,35 @@ def test_bench_gpus_flag_starts_the_ranks_itself(tmp_path):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--emulate", "--tile-size", "12", "--nz", "8"],
                        capture_output=True, text=True, timeout=120, env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), cwd=str(tmp_path))
     assert p.returncode != 0 and "--gpus 4" in p.stderr
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (one rank, emulation build) does the timed steps and prints the line, nothing after them: no
+    roofline, other contract, CPU baseline or verification (those are --full's).  --dump-outputs writes the last timed step's
+    fields, and two runs with different step counts -- each step on a pristine state copy -- write the same values."""
+    import json
+
+    build_emu()
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "1"
+    outs = []
+    for steps, warmup in ((2, 1), (3, 2)):
+        d = tmp_path / f"dump_{steps}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--tile-size", "12",
+               "--nz", "8", "--emulate", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["roofline"] is None and line["other_contract"] is None
+        assert "cpu_baseline" not in line and "verified" not in line
+        outs.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    assert {"delp.npy", "pt.npy", "u.npy", "v.npy", "w.npy", "delz.npy", "pk3.npy"} <= set(outs[0])
+    assert not {"delpc.npy", "divgd.npy", "uc.npy", "vc.npy"} & set(outs[0])  # dead work fields: not asked for
+    assert sum(a.nbytes for a in outs[0].values()) < 64e6
+    assert set(outs[0]) == set(outs[1])
+    for k, a in outs[0].items():
+        assert a.dtype == np.float64 and np.isfinite(a).all(), k
+        assert np.array_equal(a, outs[1][k]), k
