@@ -6,7 +6,7 @@
 #include <cstdio>
 
 thread_local char g_pace_err[256] = "";
-int g_pace_sync_launches = getenv("PACE_SYNC_LAUNCHES") != nullptr;
+int g_pace_sync_launches = pace_env_on("PACE_SYNC_LAUNCHES");
 void pace_set_err(const char* where, hipError_t e) {
   snprintf(g_pace_err, sizeof(g_pace_err), "%s: %s", where, hipGetErrorString(e));
 }
@@ -36,11 +36,8 @@ static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 // PACE_LEGACY_COLUMN_SOLVERS=1 selects the round-1 thread-per-column kernels of k_riem3.hip (kept for more than 128 layers and
 // for A/B measurements, and the form that walks a column's levels IN THE REFERENCE'S ORDER: the whole acoustic loop then agrees with
 // the oracle to w 6e-9 / diss_estd 1e-7 where the scans' re-association gives 4e-7 / 2e-6 -- tests/helpers.py ACOUSTIC_TOL).
-#include <cstdlib>
 static bool legacy_column_solvers() {
-  // (read at every call: tests switch between the two forms within one process)
-  const char* e = getenv("PACE_LEGACY_COLUMN_SOLVERS");
-  return e != nullptr && e[0] == '1';
+  return pace_env_on("PACE_LEGACY_COLUMN_SOLVERS");  // (read at every call: tests switch between the two forms within one process)
 }
 
 extern "C" {

@@ -693,7 +693,7 @@ struct CswTiles {
 };
 static CswTiles csw_tiles(const Geo& g) {
   CswTiles t{g.is + 6, g.js + 6, (g.n - 11) / CSW_TI, (g.n - 11) / CSW_TJ};
-  if (g.n < 12 || !t.any() || getenv("PACE_CSW_NO_TILES")) t.ntx = t.nty = 0;
+  if (g.n < 12 || !t.any() || pace_env_on("PACE_CSW_NO_TILES")) t.ntx = t.nty = 0;
   return t;
 }
 // the plain region [a0, a1]^2 of a pass minus the hole, as up to four rectangles (the first ones of `r`: nplain of them)
@@ -800,7 +800,7 @@ int launch_c_sw(const Geo& g, const Met& m, void* ws, real* delpc, real* ptc, re
   // points there are) and need no LDS and few registers; the tile kernel is bound by what it issues and by its LDS.  Neither reads
   // what the other writes (pass B's winds go to the workspace; where both write -- the rim of the tiled area -- they write the same
   // values): the band runs on a stream of this thread's own, beside the tiles.
-  const PaceSideStream* side = (part == 0 && tiles.any() && !getenv("PACE_CSW_ONE_STREAM")) ? pace_side_stream() : nullptr;
+  const PaceSideStream* side = (part == 0 && tiles.any()) ? pace_side_stream() : nullptr;
   if (side != nullptr) {
     if (!side->fork(st)) return PACE_ERR_LAUNCH;
     pass_a(side->s);

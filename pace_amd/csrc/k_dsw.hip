@@ -65,7 +65,7 @@ bool dsw_pingpong_supported(const Geo& g, const pace_dsw_config_t* cfg) {
 // whether a whole-d_sw call runs the winds as the fifth pass of the scalar-phase kernel (then nothing of d_sw is left to overlap
 // with what follows it, and the winds can have outputs of their own)
 bool dsw_winds_in_scalars(const Geo& g, const pace_dsw_config_t* cfg) {
-  return dsw_pingpong_supported(g, cfg) && dsw_scalars_take_winds() && getenv("PACE_DSW_SEPARATE_WINDS") == nullptr;
+  return dsw_pingpong_supported(g, cfg) && dsw_scalars_take_winds();
 }
 
 // apply_pt_delp_fluxes (d_sw.py:148-201) + adjust_w_and_qcon (:331-350), given the flux-form updates
@@ -179,15 +179,6 @@ kinetic_energy_point(const Geo& g, const Met& m, const real* __restrict__ uc, co
   ke[c] = kev;
 }
 
-template <int MORD>
-__global__ void __launch_bounds__(256)
-k_kinetic_energy(Geo g, Met m, const real* __restrict__ uc, const real* __restrict__ vc,
-                 const real* __restrict__ u, const real* __restrict__ v, const real* __restrict__ ut,
-                 const real* __restrict__ vt, real* __restrict__ ke, double dt, Regions R, real* __restrict__ vort, int nke) {
-  REGION_POINT_XCD(R);  // (six rows of v per point: the j-neighbouring patches share an L2 -- 255 -> 156 MB, round 3's x17)
-  kinetic_energy_point<MORD>(g, m, uc, vc, u, v, ut, vt, ke, dt, vort, i, j, k, interior, reg__ < nke);
-}
-
 // The kinetic energy and the relative vorticity in ONE launch, as two kinds of workgroups (round 6): a level's kinetic-energy blocks and,
 // behind them in the same level's share of the launch, the 64 x 4 patches of its vorticity.  Nothing is shared per point (x02: the
 // vorticity inside the kinetic-energy point function was slower); what is shared is the launch -- no drain / fill between the two -- and
@@ -206,7 +197,9 @@ k_ke_vorticity(Geo g, Met m, const real* __restrict__ uc, const real* __restrict
 #ifdef PACE_EMU
   bx__ = (int)blockIdx.x, bz__ = (int)blockIdx.z;
 #else
-  {  // (REGION_POINT_XCD's map: XCD x works through levels x, x + 8, ...)
+  {  // (workgroups are dealt to the eight XCDs round-robin in launch order, each XCD has its own L2, and a point re-reads rows of its
+     // j-neighbours: the workgroups of a level run on ONE XCD -- XCD x works through levels x, x + 8, ...; affinity only, the map is a
+     // bijection of the launch's workgroups)
     const int nbx__ = (int)gridDim.x, nlev__ = (int)gridDim.z;
     const int lin__ = (int)blockIdx.x + nbx__ * (int)blockIdx.z;
     const int full__ = (nlev__ / 8) * 8;
@@ -222,7 +215,7 @@ k_ke_vorticity(Geo g, Met m, const real* __restrict__ uc, const real* __restrict
 #endif
   const int k0 = bz__ * KE_CH;
   if (bx__ >= nbr) {
-    // a patch of the vorticity (k_vorticity's enumeration)
+    // a 64 x 4 patch of the vorticity (patch_grid's enumeration)
     const int pb = bx__ - nbr, npx = (g.ni + PATCH_W - 1) / PATCH_W;
     const int i = (pb % npx) * PATCH_W + (int)threadIdx.x, j = (pb / npx) * PATCH_H + (int)threadIdx.y;
     if (i > g.ni - 2 || j > g.nj - 2) return;
@@ -262,22 +255,12 @@ k_ke_vorticity(Geo g, Met m, const real* __restrict__ uc, const real* __restrict
 // Separate outputs of the winds (which the caller swaps in): the output buffers get the halo the inputs have -- the storage outside
 // the faces d_sw writes, u: [is, ie] x [js, je + 1], v: [is, ie + 1] x [js, je].  The frame of the plane as four strips, one thread
 // per point: south rows [0, js), north rows (je, nj), and between them the west columns [0, is) and the east columns (ie, ni).
-// (Inside the scalar-phase kernel the copy cost an edge tile 4.5 - 8 k cycles; riding on k_vorticity it cost that kernel 7 us.)
+// (Inside the scalar-phase kernel the copy cost an edge tile 4.5 - 8 k cycles; riding on the vorticity kernel it cost that kernel 7 us.)
 __global__ void __launch_bounds__(256)
 k_copy_wind_halo(Geo g, const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ u_out, real* __restrict__ v_out) {
   const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
   if (p >= wind_halo_points(g)) return;
   wind_halo_copy_point(g, p, (int)blockIdx.y, u, v, u_out, v_out);
-}
-
-// compute_vorticity (d_sw.py:301-328) + rel_vorticity_to_abs (:389-402), compute domain + halo 3
-__global__ void __launch_bounds__(256)
-k_vorticity(Geo g, Met m, const real* __restrict__ u, const real* __restrict__ v, real* __restrict__ vort) {
-  PATCH_IJK(g);
-  if (i > g.ni - 2 || j > g.nj - 2) return;
-  const long c = IDX3(g, i, j, k);
-  const long c2 = IDX2(g, i, j);
-  vort[c] = rel_vorticity(g, m, u, v, c, c2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -331,34 +314,6 @@ __device__ __forceinline__ void divdamp_low_point(const Geo& g, const Met& m, co
   const double vort = damp * d;
   vort_b[c] = vort;
   if (ke != nullptr) ke[c] = ke[c] + vort;  // (nullptr: the consumer adds the damped vorticity to the kinetic energy itself)
-}
-
-__global__ void __launch_bounds__(256)
-k_divdamp_low(Geo g, Met m, const real* __restrict__ u, const real* __restrict__ v,
-              const real* __restrict__ ua, const real* __restrict__ va, const real* __restrict__ uc,
-              const real* __restrict__ vc, real* __restrict__ delpc, real* __restrict__ vort_b,
-              real* __restrict__ ke, const real* __restrict__ d2_bg, double dddmp, double dt) {
-  PLANE_IJK(g);
-  if (i < g.is || i > g.ie + 1 || j < g.js || j > g.je + 1) return;
-  const long c = IDX3(g, i, j, k);
-  const long c2 = IDX2(g, i, j);
-  const int sj = g.sj;
-  // a = u_contra_dyc, b = v_contra_dxc (argument order at divergence_damping.py:561-566)
-  const double a0 = dd_u_contra_dyc(g, m, u, va, vc, c, c2, j);
-  const double am = dd_u_contra_dyc(g, m, u, va, vc, c - 1, c2 - 1, j);
-  const double b0 = dd_v_contra_dxc(g, m, v, ua, uc, c, c2, i);
-  const double bm = dd_v_contra_dxc(g, m, v, ua, uc, c - sj, c2 - sj, i);
-  double d = bm - b0 + am - a0;
-  const bool ic = (i == g.is || i == g.ie + 1);
-  if (ic && j == g.js) d = d - bm;
-  if (ic && j == g.je + 1) d = d + b0;
-  d = m.rarea_c[c2] * d;
-  delpc[c] = d;
-  const double delpcdt = d * dt;
-  const double damp = m.da_min_c * fmax(d2_bg[k], fmin(0.2, dddmp * fabs(delpcdt)));
-  const double vort = damp * d;
-  vort_b[c] = vort;
-  ke[c] = ke[c] + vort;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -440,56 +395,6 @@ struct DivIterT {
     return uc_raw(i, j);
   }
 };
-
-__global__ void __launch_bounds__(256)
-k_divdamp_iter(Geo g, Met m, const real* __restrict__ din, real* __restrict__ dout, int k0, int fill, int adjust,
-               real* __restrict__ uc_out, real* __restrict__ vc_out, Regions R) {
-  REGION_POINT(R);
-  const int kk = k + k0;
-  const long c2 = IDX2(g, i, j);
-  const long c = c2 + (long)kk * g.sk;
-  double d, uc_here, vc_here;
-  if (interior) {
-    // columns is+1 .. ie: no operand lies in a corner region and no corner adjustment applies
-    const int sj = g.sj;
-    const double d0 = din[c];
-    const double ucm = (d0 - din[c - sj]) * m.divg_v[c2 - sj];
-    const double uc0 = (din[c + sj] - d0) * m.divg_v[c2];
-    const double vcm = (d0 - din[c - 1]) * m.divg_u[c2 - 1];
-    const double vc0 = (din[c + 1] - d0) * m.divg_u[c2];
-    d = ucm - uc0 + vcm - vc0;
-    uc_here = uc0;
-    vc_here = vc0;
-  } else {
-    DivIterT<PlaneInMemory> it{g, m, PlaneInMemory{din + (long)kk * g.sk, g.sj}, fill != 0};
-    const double ucm = it.uc(i, j - 1), uc0 = it.uc(i, j), vcm = it.vc(i - 1, j), vc0 = it.vc(i, j);
-    d = ucm - uc0 + vcm - vc0;  // redo_divg_d :212-240
-    const bool ic = (i == g.is || i == g.ie + 1);
-    if (ic && j == g.js) d = d - ucm;
-    if (ic && j == g.je + 1) d = d + uc0;
-    uc_here = uc0;
-    vc_here = vc0;
-  }
-  if (adjust) d = d * m.rarea_c[c2];
-  dout[c] = d;
-  // The reference uses the caller's uc / vc as the work fields of this iteration (uc_from_divg / vc_from_divg,
-  // divergence_damping.py:188-209) and its Translate tests compare what is left in them after d_sw on the staggered
-  // compute windows (translate_d_sw.py:36-65): the values of the LAST iteration.
-  if (uc_out != nullptr) {
-    if (j <= g.je) uc_out[c] = uc_here;
-    if (i <= g.ie) vc_out[c] = vc_here;
-  }
-}
-
-static void launch_divdamp_iter(const Geo& g, const Met& m, const real* din, real* dout, int k0, int nlev, int nt, int fill,
-                                real* uc_out, real* vc_out, hipStream_t st) {
-  const int jb = g.js - nt, je_ = g.je + nt + 1;
-  Regions r{};
-  add_region(r, g.is + 1, g.ie, jb, je_);
-  add_region(r, g.is - nt, g.is, jb, je_);
-  add_region(r, g.ie + 1, g.ie + nt + 1, jb, je_);
-  hipLaunchKernelGGL(k_divdamp_iter, regions_grid(r, nlev), dim3(64, 4), 0, st, g, m, din, dout, k0, fill, 1, uc_out, vc_out, r);
-}
 
 // ------------------------------------------------------------------------------------------------
 // a2b_ord4 (a2b_ord4.py:59-506) as a point function, + the tail of DivergenceDamping.__call__
@@ -663,33 +568,6 @@ __global__ void __launch_bounds__(256) k_copy_window(Geo g, const real* __restri
   dst[c] = src[c];
 }
 
-// tail of DivergenceDamping for nord > 0 levels: a2b_ord4(wk) -> smagorinsky -> damping
-__global__ void __launch_bounds__(256)
-k_divdamp_high_final(Geo g, Met m, const real* __restrict__ wk, const real* delpc_src, real* divgd_out,
-                     real* __restrict__ delpc, const real* __restrict__ divg_d, real* __restrict__ vort_b,
-                     real* __restrict__ ke, const real* __restrict__ d2_bg, double dddmp, double dd8, double absdt,
-                     int k0, Regions R) {
-  REGION_POINT(R);
-  const int kk = k + k0;
-  const long c = IDX3(g, i, j, kk);
-  const double dpc = delpc_src[c];  // copy_computeplus :578
-  delpc[c] = dpc;
-  double vb;
-  if (dddmp < 1e-5) {
-    vb = 0.0;
-  } else {
-    A2B a{g, m, {wk + (long)kk * g.sk}};
-    const double qb = interior ? a.point_interior(i, j) : a.point(i, j);
-    vb = absdt * sqrt(dpc * dpc + qb * qb);
-  }
-  const double damp = m.da_min_c * fmax(d2_bg[kk], fmin(0.2, dddmp * fabs(vb)));
-  const double dfin = divg_d[c];
-  const double vort = damp * dpc + dd8 * dfin;
-  vort_b[c] = vort;
-  ke[c] = ke[c] + vort;
-  divgd_out[c] = dfin;  // the caller's divgd ends as the iterated divergence (redo_divg_d; compared by TranslateD_SW)
-}
-
 // ------------------------------------------------------------------------------------------------
 // DivergenceDamping, nord > 0 levels, as ONE kernel per (tile, level): the `nord` passes of the divergence of the gradient
 // of the divergence run in LDS on the tile's footprint (halo `nord` <= 3, shrinking by one per pass like the reference's
@@ -697,7 +575,7 @@ k_divdamp_high_final(Geo g, Met m, const real* __restrict__ wk, const real* delp
 // then the tail (a2b_ord4 of the relative vorticity, Smagorinsky term, damped vorticity, ke += ...).  `din` holds the
 // divergence c_sw left (full contract: a copy of it on the whole plane in a scratch field, so that this kernel may overwrite
 // divg_d while neighbouring tiles still read their halo; PACE_DSW_SKIP_DEAD_OUTPUTS: divg_d itself, which is then not written).
-// Replaces 3 x k_divdamp_iter + k_divdamp_high_final: 10 field passes instead of 16.
+// 10 field passes where round 1's kernel per pass and tail kernel (retired) took 16.
 // ------------------------------------------------------------------------------------------------
 #ifndef DD_TI
 #define DD_TI 65  // 193 = 3 * 65 - 2 B-grid points per row at C192
@@ -994,19 +872,9 @@ k_divdamp_fused(Geo g, Met m, const real* __restrict__ wk, const real* din, real
 }
 
 // ------------------------------------------------------------------------------------------------
-// tail of d_sw: u_and_v_from_ke (:439-477), vort_differencing (:353-380) +
+// tail of d_sw: vort_differencing (:353-380) +
 // heat_source_from_vorticity_damping (:493-577), update_u_and_v (:582-608)
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-k_uv_from_ke(Geo g, Met m, real* __restrict__ u, real* __restrict__ v, const real* __restrict__ ke,
-             const real* __restrict__ fx, const real* __restrict__ fy) {
-  PATCH_IJK(g);
-  const long c = IDX3(g, i, j, k);
-  const long c2 = IDX2(g, i, j);
-  if (i >= g.is && i <= g.ie && j >= g.js && j <= g.je + 1) u[c] = u[c] * m.dx[c2] + ke[c] - ke[c + 1] + fy[c];
-  if (i >= g.is && i <= g.ie + 1 && j >= g.js && j <= g.je) v[c] = v[c] * m.dy[c2] + ke[c] - ke[c + g.sj] - fx[c];
-}
-
 struct HeatPt {
   double ubt, vbt, fy, fx, gy, gx;
 };
@@ -1086,15 +954,9 @@ int launch_a2b_ord4(const Geo& g, const Met& m, real* qin, real* qout, int k0, i
   return PACE_OK;
 }
 
-__global__ void __launch_bounds__(256) k_copy_levels(Geo g, const real* __restrict__ src, real* __restrict__ dst, int k0) {
-  PLANE_IJK(g);
-  const long c = IDX3(g, i, j, k + k0);
-  dst[c] = src[c];
-}
-
 // the two plane-wise preliminaries of the divergence damping in ONE launch: second-order damping on the sponge levels
-// [0, kstart) (k_divdamp_low's arithmetic) and delpc = divg_d on the levels below (k_copy_levels) -- two tiny kernels were two
-// launch latencies on the critical path of the wind phase
+// [0, kstart) and delpc = divg_d on the levels below -- two tiny kernels were two launch latencies on the critical path of the
+// wind phase
 __global__ void __launch_bounds__(256)
 k_divdamp_low_and_copy(Geo g, Met m, const real* __restrict__ u, const real* __restrict__ v, const real* __restrict__ ua,
                        const real* __restrict__ va, const real* __restrict__ uc, const real* __restrict__ vc,
@@ -1129,12 +991,6 @@ k_divdamp_low_and_copy(Geo g, Met m, const real* __restrict__ u, const real* __r
   const double vort = damp * d;
   vort_b[c] = vort;
   ke[c] = ke[c] + vort;
-}
-
-// PACE_LEGACY_DIVERGENCE_DAMPING=1: the round-1 sequence (one kernel per pass + the tail kernel), kept for A/B measurements
-static bool legacy_divergence_damping() {
-  static const bool v = getenv("PACE_LEGACY_DIVERGENCE_DAMPING") != nullptr;
-  return v;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1593,68 +1449,46 @@ int launch_divergence_damping(const Geo& g, const Met& m, const real* u, const r
   // ke_by_consumer (with skip_dead only): `ke += damped vorticity` is left to the kernel that reads both (the fused scalar + wind
   // kernel forms ke + vort_b, the same single addition): this operator then neither reads nor writes ke
   const int nk = g.nk;
-  const int nhigh = nk - kstart;
-  const bool fused = nhigh > 0 && !legacy_divergence_damping();
-  skip_dead = skip_dead && fused;
+  const int nhigh = nk - kstart;  // >= 1: kstart is the first level with nord > 0 (0 if there is none), nk >= 1
+  if (nhigh < 1) return PACE_ERR_ARG;
   if (ke_by_consumer && !skip_dead) return PACE_ERR_ARG;
   if (ke_by_consumer) ke = nullptr;
-  if (fused && !skip_dead) {
-    // sponge levels + delpc = divg_d below them (copy_computeplus :578; whole planes, so that the fused kernel can take its
-    // footprint from delpc), one launch
+  if (!skip_dead) {
+    // sponge levels + delpc = divg_d below them (copy_computeplus :578; at the tile's own B-grid points -- the fused kernel takes
+    // the rest of its footprint from divg_d), one launch
     hipLaunchKernelGGL(k_divdamp_low_and_copy, plane_grid(g, nk), dim3(256), 0, st, g, m, u, v, ua, va, uc, vc, delpc, vort_b, ke,
                        d2_bg_dev, dddmp, dt, divg_d, kstart);
-  } else if (fused) {
-    // the work fields are dead after d_sw (PACE_DSW_SKIP_DEAD_OUTPUTS): no copy -- the fused kernel reads the divergence where it
-    // is and writes neither it nor uc / vc -- and the sponge levels are extra workgroups of the fused launch
-  } else if (kstart > 0) {
-    hipLaunchKernelGGL(k_divdamp_low, plane_grid(g, kstart), dim3(256), 0, st, g, m, u, v, ua, va, uc, vc, delpc, vort_b, ke,
-                       d2_bg_dev, dddmp, dt);
   }
-  if (fused) {
-    const double dd8 = pow(m.da_min_c * d4_bg, (double)(nonzero_nord + 1));
-    const int ntx = (g.n + 1 + DD_TI - 1) / DD_TI, nty = (g.n + 1 + DD_TJ - 1) / DD_TJ;
-    DdSponge sp{u, v, ua, va, uc, vc, delpc, dt, 0, 0, 0, 1, 1, 1, 1};
-    if (skip_dead && kstart > 0) {
-      sp.nlev = kstart;
-      sp.nblocks = kstart * (((g.n + 1) * (g.n + 1) + DD_NT - 1) / DD_NT);
-    }
-    if (g.n >= 8) {
-      // chunks of at most DD_STRIP points along the edge (footprint (len + 6) x 8 <= a tile's: the strips share its two LDS planes)
-      const int nrow = g.n + 1, ncol = g.n - 3;
-      sp.nch_row = (nrow + DD_STRIP - 1) / DD_STRIP;
-      sp.len_row = (nrow + sp.nch_row - 1) / sp.nch_row;
-      sp.nch_col = (ncol + DD_STRIP - 1) / DD_STRIP;
-      sp.len_col = (ncol + sp.nch_col - 1) / sp.nch_col;
-      sp.nstrips = 2 * (sp.nch_row + sp.nch_col) * nhigh;
-    }
-    hipLaunchKernelGGL(k_divdamp_fused, dim3((unsigned)(sp.nblocks + sp.nstrips + ntx * nty * nhigh)), dim3(DD_NT), 0, st, g, m,
-                       rel_vort_agrid, skip_dead ? divg_d : delpc, divg_d, vort_b, ke, uc, vc, d2_bg_dev, dddmp, dd8, fabs(dt), kstart,
-                       nonzero_nord, ntx, ntx * nty, skip_dead ? 0 : 1, sp);
-    // the full contract: the halo of divg_d, uc, vc as the reference's in-place passes leave it
-    if (!skip_dead && nonzero_nord > 0) {
-      const bool mem = getenv("PACE_DDH_MEM") != nullptr;  // (tests: the memory form on a small tile; read at every call)
-      if (DdhBand(g, DDH_M).total <= DDH_SLOTS && !mem)
-        hipLaunchKernelGGL(k_divdamp_halo_state_lds, dim3((unsigned)nhigh), dim3(DDH_NT), 0, st, g, m, delpc, divg_d, uc, vc, kstart, nonzero_nord,
-                           ddh_tab);
-      else
-        hipLaunchKernelGGL(k_divdamp_halo_state_mem, dim3((unsigned)nhigh), dim3(DDH_NT), 0, st, g, m, delpc, da, db, divg_d, uc, vc, kstart,
-                           nonzero_nord);
-    }
-  } else if (nhigh > 0) {
-    const real* src = divg_d;
-    real* bufs[2] = {da, db};
-    for (int n = 0; n < nonzero_nord; ++n) {
-      const int nt = nonzero_nord - (n + 1);
-      const int fill = (n + 1 != nonzero_nord) ? 1 : 0;
-      real* dst = bufs[n & 1];
-      const bool last = (n + 1 == nonzero_nord);  // nt == 0: its region is exactly the (n+1) x (n+1) corner points
-      launch_divdamp_iter(g, m, src, dst, kstart, nhigh, nt, fill, last ? uc : nullptr, last ? vc : nullptr, st);
-      src = dst;
-    }
-    const double dd8 = pow(m.da_min_c * d4_bg, (double)(nonzero_nord + 1));
-    const Regions r = a2b_regions(g);
-    hipLaunchKernelGGL(k_divdamp_high_final, regions_grid(r, nhigh), dim3(64, 4), 0, st, g, m, rel_vort_agrid, divg_d, divg_d,
-                       delpc, src, vort_b, ke, d2_bg_dev, dddmp, dd8, fabs(dt), kstart, r);
+  // (skip_dead: the work fields are dead after d_sw (PACE_DSW_SKIP_DEAD_OUTPUTS): no copy -- the fused kernel reads the divergence
+  // where it is and writes neither it nor uc / vc -- and the sponge levels are extra workgroups of the fused launch)
+  const double dd8 = pow(m.da_min_c * d4_bg, (double)(nonzero_nord + 1));
+  const int ntx = (g.n + 1 + DD_TI - 1) / DD_TI, nty = (g.n + 1 + DD_TJ - 1) / DD_TJ;
+  DdSponge sp{u, v, ua, va, uc, vc, delpc, dt, 0, 0, 0, 1, 1, 1, 1};
+  if (skip_dead && kstart > 0) {
+    sp.nlev = kstart;
+    sp.nblocks = kstart * (((g.n + 1) * (g.n + 1) + DD_NT - 1) / DD_NT);
+  }
+  if (g.n >= 8) {
+    // chunks of at most DD_STRIP points along the edge (footprint (len + 6) x 8 <= a tile's: the strips share its two LDS planes)
+    const int nrow = g.n + 1, ncol = g.n - 3;
+    sp.nch_row = (nrow + DD_STRIP - 1) / DD_STRIP;
+    sp.len_row = (nrow + sp.nch_row - 1) / sp.nch_row;
+    sp.nch_col = (ncol + DD_STRIP - 1) / DD_STRIP;
+    sp.len_col = (ncol + sp.nch_col - 1) / sp.nch_col;
+    sp.nstrips = 2 * (sp.nch_row + sp.nch_col) * nhigh;
+  }
+  hipLaunchKernelGGL(k_divdamp_fused, dim3((unsigned)(sp.nblocks + sp.nstrips + ntx * nty * nhigh)), dim3(DD_NT), 0, st, g, m,
+                     rel_vort_agrid, skip_dead ? divg_d : delpc, divg_d, vort_b, ke, uc, vc, d2_bg_dev, dddmp, dd8, fabs(dt), kstart,
+                     nonzero_nord, ntx, ntx * nty, skip_dead ? 0 : 1, sp);
+  // the full contract: the halo of divg_d, uc, vc as the reference's in-place passes leave it
+  if (!skip_dead && nonzero_nord > 0) {
+    const bool mem = pace_env_on("PACE_DDH_MEM");  // (tests: the memory form on a small tile; read at every call)
+    if (DdhBand(g, DDH_M).total <= DDH_SLOTS && !mem)
+      hipLaunchKernelGGL(k_divdamp_halo_state_lds, dim3((unsigned)nhigh), dim3(DDH_NT), 0, st, g, m, delpc, divg_d, uc, vc, kstart, nonzero_nord,
+                         ddh_tab);
+    else
+      hipLaunchKernelGGL(k_divdamp_halo_state_mem, dim3((unsigned)nhigh), dim3(DDH_NT), 0, st, g, m, delpc, da, db, divg_d, uc, vc, kstart,
+                         nonzero_nord);
   }
   PACE_CHECK_LAUNCH();
   return PACE_OK;
@@ -1752,20 +1586,18 @@ int launch_d_sw(const Geo& g, const Met& m, const pace_column_t* col, const pace
   // and the call asks for scalars and winds together, the vorticity transport, the wind update and the dissipative heating are
   // the FIFTH PASS of that kernel (fvt_core.h): k_fvt<.., 0, 0> and k_heat_source, and the fields between them, disappear.
   // The kinetic energy, the vorticity and the divergence damping then have to run BEFORE the scalars.
-  static const bool separate_winds = getenv("PACE_DSW_SEPARATE_WINDS") != nullptr;  // (A/B measurements)
   const bool lean_scalars = cfg->hord_dp == cfg->hord_vt && cfg->hord_dp == cfg->hord_tm && transport_lean_covers(g, cfg->hord_dp);
   // (phases 256, a measurement aid: that kernel ALONE, on the kinetic energy / vorticity / damped vorticity a previous call left in
   // the workspace)
   const bool winds_in_scalars = lean_scalars && (((phases & 2) && (phases & 4) && (phases & 8)) || (phases & 256)) && dsw_scalars_take_winds() &&
-                                !separate_winds && nmax_v <= 2 && nmax_w <= 2 && nmax_t <= 2 && ((uintptr_t)W.wk & 15) == 0;
+                                nmax_v <= 2 && nmax_w <= 2 && nmax_t <= 2 && ((uintptr_t)W.wk & 15) == 0;
   // (separate wind outputs exist in that form only; a call that runs neither the scalars nor the heating does not touch them)
   if ((cfg->u_out != nullptr) && !winds_in_scalars && (phases & (2 | 8))) return PACE_ERR_UNSUPPORTED;
   const bool skip_dead = (cfg->flags & PACE_DSW_SKIP_DEAD_OUTPUTS) != 0;
   // ... and where the work fields are not asked for either, the divergence damping leaves `ke += damped vorticity` to that kernel
   // (it holds both at the tile's B-grid points): the damping then does not touch ke, 47 MB less, and it no longer depends on the
   // kinetic-energy kernel
-  // (the same predicate as launch_divergence_damping's `fused`: with the legacy A/B switch the damping adds to ke itself)
-  const bool ke_by_consumer = winds_in_scalars && skip_dead && nk - kstart > 0 && !legacy_divergence_damping();
+  const bool ke_by_consumer = winds_in_scalars && skip_dead && nk - kstart > 0;
   // (separate wind outputs: the halo of the output buffers is a copy of the inputs' -- taken along by the flux preparation's frame
   // workgroups when this call also runs the wind phase, else by a launch of its own below)
   FxWindHalo wind_halo{u, v, cfg->u_out, cfg->v_out, false};
@@ -1844,35 +1676,25 @@ int launch_d_sw(const Geo& g, const Met& m, const pace_column_t* col, const pace
   };
   if ((phases & 2) && !winds_in_scalars && (rc = scalar_phase())) return rc;
   if (phases & (4 | 64)) {
-  // winds A1: kinetic energy and relative vorticity (need only the flux preparation)
-  // (two point kernels.  The vorticity inside the kinetic-energy kernel: no faster, x02; both from LDS tiles of u and v: twice as
-  // slow, x06 -- profiles/r05_experiments)
+  // winds A1: kinetic energy and relative vorticity (need only the flux preparation), two kinds of workgroups of one launch
+  // (the vorticity inside the kinetic-energy point function: no faster, x02; both from LDS tiles of u and v: twice as slow, x06 --
+  // profiles/r05_experiments)
   const Regions rke = (g.n >= 8) ? bgrid_regions(g, 3) : a2b_regions(g);
   if (cfg->hord_mt != 5 && cfg->hord_mt != 6) return PACE_ERR_UNSUPPORTED;
-  const bool two_launches = getenv("PACE_KE_VORT_SPLIT") != nullptr;  // (read per call; A/B measurements, tests: round 5's two launches)
-  if (!two_launches && PATCH_W == 64) {
-    const int nbr = rke.first[rke.n];
-    const dim3 pg = patch_grid(g, 1);
-    const unsigned nbl = (unsigned)nbr + pg.x * pg.y;
-    const char* ke_ch_env = getenv("PACE_KE_LEVELS");  // (read per call; A/B measurements, tests: 1 or 2)
-    const int ke_ch = ke_ch_env ? (ke_ch_env[0] == '2' ? 2 : 1) : (nbl * (unsigned)nk >= KE_CH2_MIN_WGS ? 2 : 1);
+  const int nbr = rke.first[rke.n];
+  const dim3 pg = patch_grid(g, 1);
+  const unsigned nbl = (unsigned)nbr + pg.x * pg.y;
+  const char* ke_ch_env = getenv("PACE_KE_LEVELS");  // (read per call; a test lever: 1 or 2 levels per thread)
+  const int ke_ch = ke_ch_env ? (ke_ch_env[0] == '2' ? 2 : 1) : (nbl * (unsigned)nk >= KE_CH2_MIN_WGS ? 2 : 1);
 #define KE_GO(MORD, CH)                                                                                                                   \
   hipLaunchKernelGGL((k_ke_vorticity<MORD, CH>), dim3(nbl, 1, (unsigned)((nk + CH - 1) / CH)), dim3(64, 4), 0, st, g, m, uc, vc, u, v, W.ut, W.vt, \
                      W.ke, dt, rke, W.wk, nbr)
-    if (cfg->hord_mt == 5) {
-      if (ke_ch == 2) KE_GO(5, 2); else KE_GO(5, 1);
-    } else {
-      if (ke_ch == 2) KE_GO(6, 2); else KE_GO(6, 1);
-    }
-#undef KE_GO
-  } else {
   if (cfg->hord_mt == 5) {
-    hipLaunchKernelGGL(k_kinetic_energy<5>, regions_grid(rke, nk), dim3(64, 4), 0, st, g, m, uc, vc, u, v, W.ut, W.vt, W.ke, dt, rke, (real*)nullptr, rke.n);
+    if (ke_ch == 2) KE_GO(5, 2); else KE_GO(5, 1);
   } else {
-    hipLaunchKernelGGL(k_kinetic_energy<6>, regions_grid(rke, nk), dim3(64, 4), 0, st, g, m, uc, vc, u, v, W.ut, W.vt, W.ke, dt, rke, (real*)nullptr, rke.n);
+    if (ke_ch == 2) KE_GO(6, 2); else KE_GO(6, 1);
   }
-  hipLaunchKernelGGL(k_vorticity, patch_grid(g, nk), PATCH_BLOCK, 0, st, g, m, u, v, W.wk);
-  }
+#undef KE_GO
   // (with separate wind outputs the halo of the output buffers is copied here, by a launch of its own over the frame of the plane)
   if (winds_in_scalars && cfg->u_out != nullptr && !wind_halo.done) {
     const int frame = wind_halo_points(g);

@@ -1,7 +1,6 @@
 """DGridShallowWaterLagrangianDynamics + get_column_namelist
 (reference: fv3core/pace/fv3core/stencils/d_sw.py:614-683,726-1237)."""
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -115,16 +114,16 @@ class DGridShallowWaterLagrangianDynamics(Operator):
         # kernel of the production tilings, include/pace_hip.h pace_dsw_config_t) and swapped into the caller's Quantities.
         # (pace_d_sw_outputs_supported: the one predicate of what the launcher accepts, the column namelist's damping orders included)
         accepts = int(self.lib.cdll.pace_d_sw_outputs_supported(C.byref(self._geom), C.byref(self._col), C.byref(self._cfg)))
-        self._pingpong = bool(swap_scalar_storage) and not os.environ.get("PACE_DSW_INPLACE") and bool(accepts & 1)
+        self._pingpong = bool(swap_scalar_storage) and bool(accepts & 1)
         # ... and the winds, where the library updates them in the kernel that transports the scalars
         self._wind_outputs = self._pingpong and bool(accepts & 2)
         self._quantity_factory = quantity_factory
         self._spares = None
 
-    def _outputs_for(self, fields, winds: bool):
+    def _outputs_for(self, fields):
         """Point the config at the spare buffers (allocated at the first call as copies of the fields, so that the storage line
-        beyond the halo, which no kernel writes, holds what the fields hold).  fields: delp, pt, w, q_con, u, v; `winds`: the call
-        runs the whole of d_sw (the winds have outputs of their own only then).  Returns the (field, spare) pairs to swap."""
+        beyond the halo, which no kernel writes, holds what the fields hold).  fields: delp, pt, w, q_con, u, v.  Returns the
+        (field, spare) pairs to swap."""
         cfg = self._cfg
         cfg.delp_out = cfg.pt_out = cfg.w_out = cfg.q_con_out = cfg.u_out = cfg.v_out = None
         if not self._pingpong or not all(hasattr(f, "swap_storage") for f in fields):
@@ -138,7 +137,7 @@ class DGridShallowWaterLagrangianDynamics(Operator):
         sp = self._spares
         cfg.delp_out, cfg.pt_out, cfg.w_out, cfg.q_con_out = (dptr(x) for x in sp[:4])
         pairs = list(zip(fields[:4], sp[:4]))
-        if winds and self._wind_outputs:
+        if self._wind_outputs:
             cfg.u_out, cfg.v_out = dptr(sp[4]), dptr(sp[5])
             pairs += list(zip(fields[4:], sp[4:]))
         return pairs
@@ -180,22 +179,18 @@ class DGridShallowWaterLagrangianDynamics(Operator):
         ``join()`` before touching u, v, uc, vc, heat_source, diss_est, delpc or divgd again."""
         fields = (delpc, delp, pt, u, v, w, uc, vc, ua, va, divgd, mfx, mfy, cx, cy, crx, cry, xfx, yfx, q_con, zh,
                   heat_source, diss_est)
-        late_winds = bool(overlap_winds and not self._emu and os.environ.get("PACE_DSW_LATE_WINDS"))  # (phases in separate calls)
-        pairs = self._outputs_for((delp, pt, w, q_con, u, v), winds=not late_winds)
+        pairs = self._outputs_for((delp, pt, w, q_con, u, v))
         self._cfg.flags = _lib.DSW_SKIP_DEAD_OUTPUTS if skip_dead_outputs else 0
         args = self._args(fields, dt)
         # flux preparation: everything (1), or only its frame (32) if start_flux_preparation did the interior box (16)
         prep = 32 if self._prep_started else 1
         self._prep_started = False
 
-        def phases(mask, stream_ptr):
-            self.lib.call("pace_d_sw_phases", mask, C.byref(self._geom), *args, stream_ptr)
-
         if not overlap_winds or self._emu:
             if prep == 1:
                 self.call("pace_d_sw", *args, self.stream())
             else:
-                phases(prep | 14, self.stream())
+                self.lib.call("pace_d_sw_phases", prep | 14, C.byref(self._geom), *args, self.stream())
             self._swap_in(pairs)
             return
         if self._side is None:
@@ -210,27 +205,18 @@ class DGridShallowWaterLagrangianDynamics(Operator):
         # Winds A (kinetic energy, vorticity, divergence damping, vorticity transport: they need only the flux preparation) run
         # on the side stream NEXT TO the scalar transports, winds B (heating, final wind update: they need the new delp) after
         # them, next to whatever the caller launches next (the column solver).  Measured in round 3 (bench.py, C192 x 79, three
-        # alternating runs each): 1.137 ms against 1.191 ms for the round-2 order (all winds after the scalars), which
-        # PACE_DSW_LATE_WINDS=1 restores.  (Round 2 had measured no difference: the transport kernels have changed since.)
-        if not os.environ.get("PACE_DSW_LATE_WINDS"):
-            # (Round 3, rejected: kinetic energy + vorticity started already after the first half of the flux preparation,
-            # next to its streaming second half: 1.160 ms against 1.141 ms, four alternating runs -- profiles/r03_experiments/x14.)
-            # One call does the choreography (flux preparation, event, winds A on the side stream, scalars, event, winds B on the
-            # side stream, event) instead of four calls and three event operations from here.  (The host's 105 - 120 us per
-            # substep did not change with it: they are the runtime's dozen kernel launches, not this layer.)
-            if self._ev_handles is None:
-                for e in (self._ev_prep, self._ev_scalars, self._done):
-                    e.record(main)  # (torch creates the underlying event at its first record)
-                self._ev_handles = tuple(C.c_void_p(e.cuda_event) for e in (self._ev_prep, self._ev_scalars, self._done))
-            self.lib.call("pace_d_sw_overlapped", prep, C.byref(self._geom), *args, self.stream(), side_ptr, *self._ev_handles)
-            self._pending = True
-            self._swap_in(pairs)
-            return
-        phases(prep | 2, self.stream())  # flux preparation + scalar transport on the calling stream
-        self._ev_scalars.record(main)
-        side.wait_event(self._ev_scalars)
-        phases(12, side_ptr)            # the whole wind update on the side stream
-        self._done.record(side)
+        # alternating runs each): 1.137 ms against 1.191 ms for the round-2 order (all winds after the scalars; retired since).
+        # (Round 2 had measured no difference: the transport kernels have changed since.)
+        # (Round 3, rejected: kinetic energy + vorticity started already after the first half of the flux preparation,
+        # next to its streaming second half: 1.160 ms against 1.141 ms, four alternating runs -- profiles/r03_experiments/x14.)
+        # One call does the choreography (flux preparation, event, winds A on the side stream, scalars, event, winds B on the
+        # side stream, event) instead of four calls and three event operations from here.  (The host's 105 - 120 us per
+        # substep did not change with it: they are the runtime's dozen kernel launches, not this layer.)
+        if self._ev_handles is None:
+            for e in (self._ev_prep, self._ev_scalars, self._done):
+                e.record(main)  # (torch creates the underlying event at its first record)
+            self._ev_handles = tuple(C.c_void_p(e.cuda_event) for e in (self._ev_prep, self._ev_scalars, self._done))
+        self.lib.call("pace_d_sw_overlapped", prep, C.byref(self._geom), *args, self.stream(), side_ptr, *self._ev_handles)
         self._pending = True
         self._swap_in(pairs)
 

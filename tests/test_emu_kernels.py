@@ -300,10 +300,9 @@ def test_d_sw_separate_outputs_equal_in_place_emulated():
 
 
 def dsw_launch_structure_switches(gpu=False):
-    """The launch structure of d_sw is switchable for A/B measurements: the flux preparation as one launch
-    or three (+ the wind halo copy as a launch of its own), the kinetic energy and the vorticity as one launch or two.  Every
-    combination must leave the same bits in every argument over the whole storage (the separate-outputs contract, so that the
-    wind halo copy -- which moves between launches with the switches -- is compared too)."""
+    """The kinetic energy / vorticity launch of d_sw takes one or two levels per thread (2 on large tiles, 1 on small ones by
+    itself; PACE_KE_LEVELS=2 forces two).  Both forms must leave the same bits in every argument over the
+    whole storage (the separate-outputs contract, so that the wind halo copy inside the flux preparation is compared too)."""
     from pace_amd import _lib, synthetic
     from pace_amd.fv3core import DGridShallowWaterLagrangianDynamicsConfig
     from pace_amd.fv3core.stencils.d_sw import DGridShallowWaterLagrangianDynamics, get_column_namelist
@@ -316,10 +315,9 @@ def dsw_launch_structure_switches(gpu=False):
     env = Env(lib, "cuda" if gpu else "cpu", m, n, nz)
     cfg = DGridShallowWaterLagrangianDynamicsConfig()
     res = {}
-    # (PACE_KE_LEVELS: levels per thread of the kinetic energy / vorticity launch -- 2 on large tiles, 1 on small ones by itself)
-    for sw in ((), ("PACE_FXADV_SPLIT",), ("PACE_KE_VORT_SPLIT",), ("PACE_FXADV_SPLIT", "PACE_KE_VORT_SPLIT"), ("PACE_KE_LEVELS",)):
+    for sw in ((), ("PACE_KE_LEVELS",)):
         for k in sw:
-            os.environ[k] = "2" if k == "PACE_KE_LEVELS" else "1"
+            os.environ[k] = "2"
         try:
             op = DGridShallowWaterLagrangianDynamics(env.stencil_factory, env.qf, env.grid_data, env.damping, get_column_namelist(cfg, env.qf),
                                                     False, False, cfg, swap_scalar_storage=True)
@@ -1038,7 +1036,7 @@ def test_two_emulation_libraries_in_one_process_do_not_share_symbols():
 
 def test_d_sw_halo_state_memory_form_equals_lds_form():
     """k_divdamp_halo_state (the halo of divgd / uc / vc as the reference's in-place divergence damping leaves it: TranslateD_SW's
-    whole-storage windows) has two forms: the band's divergence planes in LDS (tiles up to C320), or in two scratch fields (larger
+    whole-storage windows) has two forms: the band's divergence planes in LDS (tiles up to about C200), or in two scratch fields (larger
     tiles; PACE_DDH_MEM=1 forces it).  C24: a band with an inside.  Both against the oracle, whole storage, bit for bit."""
     from helpers import DSW_CFG
     from oracle import dgrid_sw
@@ -1064,10 +1062,10 @@ def test_d_sw_halo_state_memory_form_equals_lds_form():
             assert np.array_equal(a[k][dsw_window(k, n, nz)], out[k][dsw_window(k, n, nz)]), (mem, k)
 
 
-def test_fxadv_one_launch_equals_the_four_launches_and_the_oracle():
+def test_fxadv_one_launch_equals_the_oracle():
     """FiniteVolumeFluxPrep as ONE launch (the frame's stages and fluxes in one workgroup per level beside the interior's blocks;
-    k_fxadv_fused) and as round 5's four launches (PACE_FXADV_SPLIT=1): both against the oracle, bit for bit, on the windows
-    TranslateFxAdv compares (translate_fxadv.py:49-72) and on the fluxes' whole domains.  C12 and C24 (levels per thread 1 .. 8)."""
+    k_fxadv_fused) against the oracle, bit for bit, on the windows TranslateFxAdv compares (translate_fxadv.py:49-72) and on the
+    fluxes' whole domains.  C12 and C24 (levels per thread 1 .. 8)."""
     from oracle import dgrid_sw
     from pace_amd import _lib, synthetic
     from pace_amd.fv3core.stencils.fxadv import FiniteVolumeFluxPrep
@@ -1079,18 +1077,12 @@ def test_fxadv_one_launch_equals_the_four_launches_and_the_oracle():
         dgrid_sw.fxadv(oracle_grid(m, n, nz), s["uc"], s["vc"], ref["crx"], ref["cry"], ref["xfx"], ref["yfx"], ref["ut"], ref["vt"], s["dt"])
         env = Env(_lib.Library(build_emu()), "cpu", m, n, nz)
         prep = FiniteVolumeFluxPrep(env.stencil_factory, env.grid_data)
-        for split in (False, True):
-            if split:
-                os.environ["PACE_FXADV_SPLIT"] = "1"
-            try:
-                uc, vc = env.q3(s["uc"]), env.q3(s["vc"])
-                out = {k: env.q3() for k in ref}
-                prep(uc, vc, out["crx"], out["cry"], out["xfx"], out["yfx"], out["ut"], out["vt"], s["dt"])
-            finally:
-                os.environ.pop("PACE_FXADV_SPLIT", None)
-            wins = {"crx": (slice(3, n + 4), slice(0, n + 6)), "xfx": (slice(3, n + 4), slice(0, n + 6)),
-                    "cry": (slice(0, n + 6), slice(3, n + 4)), "yfx": (slice(0, n + 6), slice(3, n + 4)),
-                    "ut": (slice(1, n + 6), slice(1, n + 5)), "vt": (slice(1, n + 5), slice(1, n + 6))}
-            for k, (wi, wj) in wins.items():
-                a, b = ref[k][wi, wj, :nz], out[k].numpy()[wi, wj, :nz]
-                assert np.array_equal(a, b), (n, split, k, float(np.abs(a - b).max()))
+        uc, vc = env.q3(s["uc"]), env.q3(s["vc"])
+        out = {k: env.q3() for k in ref}
+        prep(uc, vc, out["crx"], out["cry"], out["xfx"], out["yfx"], out["ut"], out["vt"], s["dt"])
+        wins = {"crx": (slice(3, n + 4), slice(0, n + 6)), "xfx": (slice(3, n + 4), slice(0, n + 6)),
+                "cry": (slice(0, n + 6), slice(3, n + 4)), "yfx": (slice(0, n + 6), slice(3, n + 4)),
+                "ut": (slice(1, n + 6), slice(1, n + 5)), "vt": (slice(1, n + 5), slice(1, n + 6))}
+        for k, (wi, wj) in wins.items():
+            a, b = ref[k][wi, wj, :nz], out[k].numpy()[wi, wj, :nz]
+            assert np.array_equal(a, b), (n, k, float(np.abs(a - b).max()))

@@ -699,8 +699,8 @@ def test_d_sw_separate_outputs_equal_in_place(lib):
 
 @pytest.mark.gpu
 def test_d_sw_launch_structure_switches_are_bit_identical(lib):
-    """The GPU twin of ..._emulated at C48 x 7: FiniteVolumeFluxPrep as one launch or three, the wind halo copy inside it or as a launch of
-    its own, kinetic energy + vorticity as one launch or two -- every argument of d_sw bit for bit over the whole storage."""
+    """The GPU twin of ..._emulated at C48 x 7: the kinetic energy / vorticity launch with one or two levels per thread -- every argument
+    of d_sw bit for bit over the whole storage."""
     from test_emu_kernels import dsw_launch_structure_switches
 
     dsw_launch_structure_switches(gpu=True)

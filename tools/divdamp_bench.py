@@ -1,5 +1,4 @@
-"""DivergenceDamping on its own at C192 x 79 (HIP events on the launch stream).  PACE_LEGACY_DIVERGENCE_DAMPING=1 for the
-per-pass kernels."""
+"""DivergenceDamping on its own at C192 x 79 (HIP events on the launch stream)."""
 import os
 import sys
 
@@ -35,4 +34,4 @@ for _ in range(reps):
     run()
 b.record()
 torch.cuda.synchronize()
-print(f"DivergenceDamping C{n}: {a.elapsed_time(b) / reps * 1e3:.1f} us  (legacy={bool(os.environ.get('PACE_LEGACY_DIVERGENCE_DAMPING'))})")
+print(f"DivergenceDamping C{n}: {a.elapsed_time(b) / reps * 1e3:.1f} us")

@@ -48,7 +48,7 @@ def main():
         if fused:  # the kernel alone (256), on the kinetic energy / vorticities of phase 4, with outputs of its own
             phase(4, f)
             torch.cuda.synchronize()
-            dsw._outputs_for(tuple(f[k] for k in ("delp", "pt", "w", "q_con", "u", "v")), winds=True)
+            dsw._outputs_for(tuple(f[k] for k in ("delp", "pt", "w", "q_con", "u", "v")))
             phase(256, f)
             dsw._cfg.delp_out = dsw._cfg.pt_out = dsw._cfg.w_out = dsw._cfg.q_con_out = dsw._cfg.u_out = dsw._cfg.v_out = None
         else:

@@ -1,5 +1,5 @@
 """The flux preparation of d_sw timed in its parts (hipEvents, median of N): the whole (pace_d_sw_phases 1), the interior box alone
-(16) and the frame alone (32), for the library in PACE_HIP_LIB (default: the product's) and, with PACE_FXADV_SPLIT=1, round 5's launches.
+(16) and the frame alone (32), for the library in PACE_HIP_LIB (default: the product's).
 
     python tools/fxadv_parts.py [--n 192] [--reps 30]
 """
@@ -52,7 +52,7 @@ def main():
             if r >= 3:
                 ts.append(e0.elapsed_time(e1) * 1e3)
         out.append(f"{label} {np.median(ts):.1f} (min {np.min(ts):.1f})")
-    print(f"C{n} fxadv us: " + "   ".join(out), "  split launches" if os.environ.get("PACE_FXADV_SPLIT") == "1" else "  one launch")
+    print(f"C{n} fxadv us: " + "   ".join(out))
 
 
 if __name__ == "__main__":

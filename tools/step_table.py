@@ -10,17 +10,18 @@ import json
 import re
 import sys
 
-# distinct 3-D fields per launch (in + out), by kernel-name fragment; the edge-strip kernel touches a few rows only
+# distinct 3-D fields per launch (in + out), by kernel-name fragment; the edge-strip kernel touches a few rows only.  The retired
+# kernels of round 5 stay listed so that the tool still reads the r05 artefacts under profiles/.
 FIELDS = [
     ("k_fxadv_fused", 10.65, "uc, vc, cx, cy -> crx, cry, xfx, yfx, cx, cy (ut, vt on the frame of the plane, 11 % of it): the frame's stages and the interior's stream in one launch"),
-    ("k_fxadv_frame", 0.45, "uc, vc -> ut, vt on the frame of the plane (11 % of it)"),
-    ("k_fxadv_edges", 0.2, "edge strips of ut, vt"),
-    ("k_fxadv_fluxes", 10, "uc, vc (ut, vt on the frame), cx, cy -> crx, cry, xfx, yfx, cx, cy"),
+    ("k_fxadv_frame", 0.45, "uc, vc -> ut, vt on the frame of the plane (11 % of it)"),  # round 5's, retired: profiles/r05_*
+    ("k_fxadv_edges", 0.2, "edge strips of ut, vt"),  # round 5's, retired: profiles/r05_*
+    ("k_fxadv_fluxes", 10, "uc, vc (ut, vt on the frame), cx, cy -> crx, cry, xfx, yfx, cx, cy"),  # round 5's, retired: profiles/r05_*
     ("k_fvt_scalars", 26, "delp, w, q_con, pt, crx, cry, xfx, yfx, mfx, mfy, vorticity, u, v, ke, damped vorticity, heat_source -> delp, w, "
                           "q_con, pt, mfx, mfy, diss_est, u, v, heat_source"),
     ("k_ke_vorticity", 6, "uc, vc, u, v -> ke, rel. vorticity (two kinds of workgroups of one launch)"),
-    ("k_kinetic_energy", 5, "uc, vc, u, v -> ke"),
-    ("k_vorticity", 3, "u, v -> rel. vorticity"),
+    ("k_kinetic_energy", 5, "uc, vc, u, v -> ke"),  # round 5's, retired: profiles/r05_*
+    ("k_vorticity", 3, "u, v -> rel. vorticity"),  # round 5's, retired: profiles/r05_*
     ("k_divdamp_fused", 3, "divgd, vorticity -> damped vorticity (+ the sponge levels: u, v, ua, va, uc, vc on two or three levels)"),
     ("k_riem_column", 13, "cappa, q_con, delp, pt, zh, pe, w -> delz, zh, pe, ppe, pk3, w"),
 ]
