@@ -406,8 +406,8 @@ int pace_mapn_tracer(const pace_geom_t* geom, void* workspace, pace_real_t* cons
 int pace_fillz(const pace_geom_t* geom, pace_real_t* const* tracers, int nq, const pace_real_t* dp2, void* stream);
 
 /* ---- LagrangianToEulerian: the stencils around the remaps (fv3core/pace/fv3core/stencils/remapping.py:286-695 calls them
- * in this order; pace_amd/fv3core/stencils/remapping.py is the host sequence).  Non-hydrostatic, kord_tm < 0, no saturation
- * adjustment.  water: HOST array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel; ak / bk: device
+ * in this order; pace_amd/fv3core/stencils/remapping.py is the host sequence).  Non-hydrostatic, kord_tm < 0; the saturation
+ * adjustment is pace_sat_adjust below.  water: HOST array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel; ak / bk: device
  * arrays of nk + 1 hybrid coefficients; ps: 2-D field.
  *   pace_l2e_prepare   = init_pe (:42-56) + moist_cv_pt_pressure (:85-171) + pn2_pk_delp (:174-193)
  *   pace_l2e_post      = undo_delz_adjust_and_copy_peln (:59-80) + moist_cv.moist_pkz (moist_cv.py:130-172)
@@ -427,6 +427,34 @@ int pace_l2e_pressures(const pace_geom_t* geom, int dir, const pace_real_t* pe, 
                        void* stream);
 int pace_l2e_finish(const pace_geom_t* geom, const pace_real_t* const* water, pace_real_t* pe, const pace_real_t* pe2,
                     pace_real_t* pt, const pace_real_t* pkz, double r_vir, int last_step, void* stream);
+
+/* ---- SatAdjust3d (fv3core/pace/fv3core/stencils/saturation_adjustment.py:947-1108): the fast saturation adjustment that
+ * LagrangianToEulerian runs between the remap of v and moist_pt_last_step / the division by pkz (remapping.py:627-672).
+ *   pace_sat_adjust_tables  fills `tables` (a DEVICE buffer of PACE_SAT_ADJUST_TABLE_DOUBLES doubles, in both builds) with the
+ *                           saturation tables satadjust reads -- table2, des2, tablew, desw (compute_q_tables, :540-558; the
+ *                           reference evaluates each entry on the fly, :46-160) -- for indices -1 ... 2620, one record of four
+ *                           doubles per index.  Once per SatAdjust3d object.
+ *   pace_sat_adjust         the satadjust stencil (:561-944), non-hydrostatic, over origin (3, 3, kmp), domain (n, n, nk - kmp)
+ *                           (:953-976); nothing else is written.  water: HOST array of the six device pointers qvapor, qliquid,
+ *                           qrain, qsnow, qice, qgraupel (inout); qcld (out, only where do_qa && last_step); te (out, only where
+ *                           consv_te: the reference's fast_mp_consv); pt (inout); q_con, pkz, cappa (out); delp, delz (in);
+ *                           area (the float64 cell area, area_64), hs: 2-D fields; params: the externals and the factors
+ *                           SatAdjust3d.__call__ computes on the host (:1038-1069).  hydrostatic != 0 is PACE_ERR_UNSUPPORTED. */
+#define PACE_SAT_ADJUST_TABLE_DOUBLES (4 * 2622)
+typedef struct {
+  /* externals (:957-975) */
+  int32_t hydrostatic, rad_snow, rad_rain, rad_graupel, tintqs, icloud_f;
+  int32_t do_qa; /* hard-coded True by the reference's __call__ (:1071) */
+  int32_t pad_;
+  double sat_adj0, ql_gen, qs_mlt, ql0_max, t_sub, qi_gen, qi_lim, qi0_max, dw_ocean, dw_land, cld_min;
+  /* the scalar arguments of satadjust (:577-594) */
+  double sdt, zvir, fac_i2s, c_air, c_vap, mdt, fac_r2g, fac_smlt, fac_l2r, fac_imlt, d0_vap, lv00, fac_v2l, fac_l2v;
+} pace_sat_adjust_params_t;
+int pace_sat_adjust_tables(double* tables, void* stream);
+int pace_sat_adjust(const pace_geom_t* geom, pace_real_t* const* water, pace_real_t* qcld, pace_real_t* te, pace_real_t* pt,
+                    pace_real_t* q_con, pace_real_t* pkz, pace_real_t* cappa, const pace_real_t* delp, const pace_real_t* delz,
+                    const pace_real_t* area, const pace_real_t* hs, const double* tables, const pace_sat_adjust_params_t* params,
+                    int kmp, int last_step, int consv_te, void* stream);
 
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.

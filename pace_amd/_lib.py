@@ -74,6 +74,18 @@ class HaloDesc(C.Structure):
     ]
 
 
+SAT_ADJUST_TABLE_DOUBLES = 4 * 2622  # include/pace_hip.h PACE_SAT_ADJUST_TABLE_DOUBLES
+
+
+class SatAdjustParams(C.Structure):
+    _fields_ = (
+        [(n, C.c_int32) for n in ("hydrostatic", "rad_snow", "rad_rain", "rad_graupel", "tintqs", "icloud_f", "do_qa", "pad_")]
+        + [(n, C.c_double) for n in ("sat_adj0", "ql_gen", "qs_mlt", "ql0_max", "t_sub", "qi_gen", "qi_lim", "qi0_max", "dw_ocean",
+                                     "dw_land", "cld_min", "sdt", "zvir", "fac_i2s", "c_air", "c_vap", "mdt", "fac_r2g", "fac_smlt",
+                                     "fac_l2r", "fac_imlt", "d0_vap", "lv00", "fac_v2l", "fac_l2v")]
+    )
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -154,6 +166,9 @@ _PROTOS = {
     "pace_fv_setup_pt": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 7 + [C.c_void_p]),
     "pace_omega_from_w": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [C.c_void_p]),
     "pace_neg_adj3": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 3 + [C.c_void_p]),
+    "pace_sat_adjust_tables": (C.c_int, [c_dp, C.c_void_p]),
+    "pace_sat_adjust": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [_P(SatAdjustParams), C.c_int, C.c_int, C.c_int,
+                                                                              C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

@@ -552,6 +552,23 @@ int pace_neg_adj3(const pace_geom_t* geom, real* const* water, real* qcld, real*
   return launch_neg_adj3(make_geo(geom), water, qcld, pt, delp, S(stream));
 }
 
+int pace_sat_adjust_tables(double* tables, void* stream) {
+  if (!tables) return PACE_ERR_ARG;
+  (void)hipGetLastError();
+  return launch_sat_adjust_tables(tables, S(stream));
+}
+
+int pace_sat_adjust(const pace_geom_t* geom, real* const* water, real* qcld, real* te, real* pt, real* q_con, real* pkz,
+                    real* cappa, const real* delp, const real* delz, const real* area, const real* hs, const double* tables,
+                    const pace_sat_adjust_params_t* params, int kmp, int last_step, int consv_te, void* stream) {
+  NEED(geom && six_rw(water) && qcld && pt && q_con && pkz && cappa && delp && delz && area && hs && tables && params &&
+       (te || !consv_te));
+  if (params->hydrostatic) return PACE_ERR_UNSUPPORTED;
+  if (kmp < 0 || kmp >= geom->nk) return PACE_ERR_ARG;
+  return launch_sat_adjust(make_geo(geom), water, qcld, te, pt, q_con, pkz, cappa, delp, delz, area, hs, tables, *params, kmp,
+                           last_step, consv_te, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

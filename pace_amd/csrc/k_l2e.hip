@@ -1,6 +1,6 @@
 // The stencils of LagrangianToEulerian around the vertical remaps (fv3core/pace/fv3core/stencils/remapping.py:42-283,
-// moist_cv.py:16-172), for the modes the reference implements (non-hydrostatic, kord_tm < 0) without the saturation
-// adjustment.  All of them are local in (i, j) and -- once ps = pe[km] is read -- in k, so each is ONE thread-per-cell
+// moist_cv.py:16-172), for the modes the reference implements (non-hydrostatic, kord_tm < 0); the saturation adjustment,
+// between the remaps and k_l2e_finish, is k_satadj.hip.  All of them are local in (i, j) and -- once ps = pe[km] is read -- in k, so each is ONE thread-per-cell
 // launch: [k][j][i] storage, lanes along i, 64 x 4 patches.
 //   k_l2e_prepare    init_pe + moist_cv_pt_pressure + pn2_pk_delp (3 stencils, 15 computations)
 //   k_l2e_post       undo_delz_adjust_and_copy_peln + moist_pkz

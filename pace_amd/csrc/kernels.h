@@ -261,6 +261,11 @@ int launch_l2e_pressures(const Geo& g, int dir, const real* pe, const real* pe1,
                          real* pe0, real* pe3, hipStream_t st);
 int launch_l2e_finish(const Geo& g, const real* const* water, real* pe, const real* pe2, real* pt, const real* pkz,
                       double r_vir, int last_step, hipStream_t st);
+// k_satadj.hip
+int launch_sat_adjust_tables(double* tables, hipStream_t st);
+int launch_sat_adjust(const Geo& g, real* const* water, real* qcld, real* te, real* pt, real* q_con, real* pkz, real* cappa,
+                      const real* delp, const real* delz, const real* area, const real* hs, const double* tables,
+                      const pace_sat_adjust_params_t& p, int kmp, int last_step, int consv_te, hipStream_t st);
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);
 int launch_omega_from_w(const Geo& g, const real* delp, const real* delz, const real* w, real* omga, hipStream_t st);

@@ -4,6 +4,7 @@ from ._config import (  # noqa: F401
     DynamicalCoreConfig,
     RemappingConfig,
     RiemannConfig,
+    SatAdjustConfig,
 )
 from .initialization.dycore_state import DycoreState  # noqa: F401,E402
 from .stencils.fv_dynamics import DynamicalCore  # noqa: F401,E402

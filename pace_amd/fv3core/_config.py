@@ -63,6 +63,39 @@ class AcousticDynamicsConfig:
     riemann: RiemannConfig = dataclasses.field(default_factory=RiemannConfig)
 
 
+@dataclasses.dataclass(frozen=True)
+class SatAdjustConfig:
+    """fv3core/pace/fv3core/_config.py:16-40, with the defaults of util/pace/util/namelist.py:22-51."""
+
+    hydrostatic: bool = False
+    rad_snow: bool = True
+    rad_rain: bool = True
+    rad_graupel: bool = True
+    tintqs: bool = False
+    sat_adj0: float = 0.90
+    ql_gen: float = 1.0e-3
+    qs_mlt: float = 1.0e-6
+    ql0_max: float = 2.0e-3
+    t_sub: float = 184.0
+    qi_gen: float = 1.82e-6
+    qi_lim: float = 1.0
+    qi0_max: float = 1.0e-4
+    dw_ocean: float = 0.10
+    dw_land: float = 0.15
+    icloud_f: int = 0
+    cld_min: float = 0.05
+    tau_i2s: float = 1000.0
+    tau_v2l: float = 90.0
+    tau_r2g: float = 900.0
+    tau_l2r: float = 900.0
+    tau_l2v: float = 300.0
+    tau_imlt: float = 600.0
+    tau_smlt: float = 900.0
+
+
+_SAT_ADJUST_FIELDS = tuple(f.name for f in dataclasses.fields(SatAdjustConfig) if f.name != "hydrostatic")
+
+
 @dataclasses.dataclass
 class DynamicalCoreConfig:
     layout: Tuple[int, int] = (1, 1)
@@ -95,11 +128,41 @@ class DynamicalCoreConfig:
     kord_wz: int = 9
     kord_mt: int = 9
     do_sat_adj: bool = False
+    # the saturation adjustment's namelist (util/pace/util/namelist.py:22-51)
+    tau_r2g: float = 900.0
+    tau_smlt: float = 900.0
+    tau_imlt: float = 600.0
+    tau_i2s: float = 1000.0
+    tau_l2r: float = 900.0
+    sat_adj0: float = 0.90
+    ql_gen: float = 1.0e-3
+    qs_mlt: float = 1.0e-6
+    ql0_max: float = 2.0e-3
+    t_sub: float = 184.0
+    qi_gen: float = 1.82e-6
+    qi_lim: float = 1.0
+    qi0_max: float = 1.0e-4
+    rad_snow: bool = True
+    rad_rain: bool = True
+    rad_graupel: bool = True
+    tintqs: bool = False
+    dw_ocean: float = 0.10
+    dw_land: float = 0.15
+    icloud_f: int = 0
+    cld_min: float = 0.05
+    tau_l2v: float = 300.0
+    tau_v2l: float = 90.0
+
+    @property
+    def sat_adjust(self) -> SatAdjustConfig:
+        """fv3core/pace/fv3core/_config.py:437-464."""
+        return SatAdjustConfig(hydrostatic=self.hydrostatic, **{n: getattr(self, n) for n in _SAT_ADJUST_FIELDS})
 
     @property
     def remapping(self):
         return RemappingConfig(fill=self.fill, kord_tm=self.kord_tm, kord_tr=self.kord_tr, kord_wz=self.kord_wz,
-                               kord_mt=self.kord_mt, do_sat_adj=self.do_sat_adj, hydrostatic=self.hydrostatic)
+                               kord_mt=self.kord_mt, do_sat_adj=self.do_sat_adj, hydrostatic=self.hydrostatic,
+                               sat_adjust=self.sat_adjust)
 
     @property
     def d_grid_shallow_water(self):
@@ -112,7 +175,7 @@ class DynamicalCoreConfig:
 
 @dataclasses.dataclass(frozen=True)
 class RemappingConfig:
-    """fv3core/pace/fv3core/_config.py:42-56 (without the saturation-adjustment namelist, which is out of scope)."""
+    """fv3core/pace/fv3core/_config.py:42-56."""
 
     fill: bool = True
     kord_tm: int = -9
@@ -121,3 +184,4 @@ class RemappingConfig:
     kord_mt: int = 9
     do_sat_adj: bool = False
     hydrostatic: bool = False
+    sat_adjust: SatAdjustConfig = dataclasses.field(default_factory=SatAdjustConfig)

@@ -1,7 +1,7 @@
 """LagrangianToEulerian -- Fortran Lagrangian_to_Eulerian (reference: fv3core/pace/fv3core/stencils/remapping.py:286-695).
 
-The saturation adjustment (saturation_adjustment.py, 1100 lines of microphysics) is not part of pace_amd: a configuration
-with ``do_sat_adj = True`` is refused at construction."""
+With ``do_sat_adj = True`` the saturation adjustment (SatAdjust3d) runs between the remap of v and the last stencil, as in
+the reference (:627-672)."""
 from typing import Dict
 
 from ...util.constants import X_DIM, X_INTERFACE_DIM, Y_DIM, Y_INTERFACE_DIM, Z_DIM, Z_INTERFACE_DIM
@@ -10,6 +10,7 @@ from ._common import Operator, check_layout, dptr
 from .fillz import pointer_table
 from .map_single import MapSingle
 from .mapn_tracer import MapNTracer
+from .saturation_adjustment import SatAdjust3d
 
 # TODO(reference): "Should this be set here or in global_constants?" (remapping.py:38-39)
 CONSV_MIN = 0.001
@@ -26,8 +27,6 @@ class LagrangianToEulerian(Operator):
             raise NotImplementedError("map ppm, untested mode where kord_tm >= 0")
         if config.hydrostatic:
             raise NotImplementedError("Hydrostatic is not implemented")
-        if config.do_sat_adj:
-            raise NotImplementedError("the saturation adjustment (do_sat_adj) is outside the scope of pace_amd")
         self._t_min = 184.0
         self._nq = nq
         qf = quantity_factory
@@ -48,6 +47,17 @@ class LagrangianToEulerian(Operator):
         self._map_single_delz = MapSingle(sf, qf, self._kord_wz, 1, dims=[X_DIM, Y_DIM, Z_DIM])
         self._map_single_u = MapSingle(sf, qf, self._kord_mt, -1, dims=[X_DIM, Y_INTERFACE_DIM, Z_DIM])
         self._map_single_v = MapSingle(sf, qf, self._kord_mt, -1, dims=[X_INTERFACE_DIM, Y_DIM, Z_DIM])
+        if self._do_sat_adjust:
+            # the first level below 10 hPa (:344-348)
+            nk = self._geom.nk
+            pf = pfull.view[:] if hasattr(pfull, "dims") else pfull
+            pf = pf.detach().cpu().numpy() if hasattr(pf, "detach") else pf
+            self.kmp = nk - 1
+            for k in range(min(len(pf), nk)):
+                if float(pf[k]) > 10.0e2:
+                    self.kmp = k
+                    break
+            self._saturation_adjustment = SatAdjust3d(sf, config.sat_adjust, area_64, self.kmp, quantity_factory=qf)
 
     def __call__(self, tracers, pt, delp, delz, peln, u, v, w, cappa, q_con, q_cld, pkz, pk, pe, hs, ps, wsd, ak, bk, dp1,
                  ptop: float, akap: float, zvir: float, last_step: bool, consv_te: float, mdt: float):
@@ -77,6 +87,11 @@ class LagrangianToEulerian(Operator):
         self._map_single_u(u, self._pe0, self._pe3)
         self.call("pace_l2e_pressures", 1, dptr(pe), dptr(self._pe1), dptr(ak), dptr(bk), dptr(self._pe0), dptr(self._pe3), st())
         self._map_single_v(v, self._pe0, self._pe3)
+        if self._do_sat_adjust:
+            fast_mp_consv = consv_te > CONSV_MIN
+            self._saturation_adjustment(dp1, tracers["qvapor"], tracers["qliquid"], tracers["qice"], tracers["qrain"],
+                                        tracers["qsnow"], tracers["qgraupel"], q_cld, hs, peln, delp, delz, q_con, pt, pkz, cappa,
+                                        zvir, mdt, fast_mp_consv, last_step, akap, self.kmp)
         # on the last step, we need the regular temperature to send to the physics, but if we're staying in dynamics we
         # need to keep it as the virtual potential temperature
         self.call("pace_l2e_finish", water, dptr(pe), dptr(self._pe2), dptr(pt), dptr(pkz), float(zvir), int(bool(last_step)), st())

@@ -73,6 +73,8 @@ class GridData:
                 q._grid_data = self  # lets operators that are handed one metric (updatedzc's `area`) find the table
                 setattr(self, name, q)
                 self._names.append(name)
+        if hasattr(self, "area") and not hasattr(self, "area_64"):
+            self.area_64 = self.area  # the float64 cell area the saturation adjustment reads (grid/helper.py:385-388)
         if all(hasattr(self, k) for k in _HOST_ONLY):
             self.a2b_corner_w = a2b_corner_weights(self.lon, self.lat, self.lon_agrid, self.lat_agrid, n)
         else:

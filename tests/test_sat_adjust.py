@@ -1,0 +1,396 @@
+"""The saturation adjustment (SatAdjust3d, k_satadj.hip) and LagrangianToEulerian / DynamicalCore with do_sat_adj = True,
+against runs of the reference (tools/make_golden_satadj.py): the emulated library on the CPU, the gfx950 library with -m gpu."""
+import numpy as np
+import pytest
+
+from helpers import Env, build_emu, compare, golden
+
+CASES = ["mid", "last", "consv", "rad", "icloud2"]
+SPECIES = ["qvapor", "qliquid", "qrain", "qsnow", "qice", "qgraupel"]
+SA_OUT = SPECIES + ["qcld", "te", "pt", "q_con", "pkz", "cappa"]
+L2E_CHANGED = SPECIES + ["qcld", "pt", "q_con", "pkz", "cappa"]
+N = 12
+
+
+@pytest.fixture(scope="module")
+def emu_lib():
+    from pace_amd import _lib
+
+    return _lib.Library(build_emu())
+
+
+@pytest.fixture(scope="module")
+def emu_f32_lib():
+    import os
+    import subprocess
+
+    from pace_amd import _lib
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run(["make", "-s", "-j8", "emu-f32"], cwd=root, check=True)
+    return _lib.Library(os.path.join(root, "tests", "emu", "libpace_emu_f32.so"))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from pace_amd import _lib
+
+    return _lib.load()
+
+
+def case_config(tag):
+    from pace_amd.fv3core import SatAdjustConfig
+
+    if tag == "rad":
+        return SatAdjustConfig(rad_snow=False, rad_rain=False, rad_graupel=False, tintqs=True, icloud_f=1)
+    if tag == "icloud2":
+        return SatAdjustConfig(icloud_f=2)
+    return SatAdjustConfig()
+
+
+def run_sat_adjust(lib, device, d, tag):
+    """SatAdjust3d on satadj_c12.npz's inputs embedded in NaN-filled storage; returns (outputs, inputs) as full arrays."""
+    import torch
+
+    from pace_amd.fv3core.stencils.saturation_adjustment import SatAdjust3d
+    from pace_amd.util import constants as c
+
+    nk = len(d["k_sel"])
+    env = Env(lib, device, golden("grid_c12_tile0.npz"), N, nk)
+    full = {}
+    for name in SA_OUT + ["delp", "delz"]:
+        a = np.full((N + 7, N + 7, nk + 1), np.nan)
+        a[3:15, 3:15, :nk] = d["in_" + name] if "in_" + name in d else 0.0
+        full[name] = a
+    f = {k: env.q3(v) for k, v in full.items()}
+    area = np.full((N + 7, N + 7), np.nan)
+    area[3:15, 3:15] = d["area"]
+    hs = np.full((N + 7, N + 7), np.nan)
+    hs[3:15, 3:15] = d["hs"]
+    op = SatAdjust3d(env.stencil_factory, case_config(tag), env.q2(area), int(d["kmp"]))
+    last = tag != "mid"
+    op(f["te"], f["qvapor"], f["qliquid"], f["qice"], f["qrain"], f["qsnow"], f["qgraupel"], f["qcld"], env.q2(hs), None, f["delp"],
+       f["delz"], f["q_con"], f["pt"], f["pkz"], f["cappa"], c.ZVIR, float(d["mdt"]), tag == "consv", last, c.KAPPA, int(d["kmp"]))
+    if device != "cpu":
+        torch.cuda.synchronize()
+    return {k: v.numpy() for k, v in f.items()}, full
+
+
+def check_sat_adjust(d, out, full, tag, tol, f32=False):
+    """Worst error per output on the window; everything outside the window (halo, k < kmp) holds what it held before."""
+    kmp, nk = int(d["kmp"]), len(d["k_sel"])
+    worst = {}
+    for name in SA_OUT:
+        ref, got = d[f"out_{tag}_{name}"], out[name][3:15, 3:15, :nk]
+        e = compare(ref[:, :, kmp:], got[:, :, kmp:], near_zero=1e-9 if f32 else 1e-18)
+        bound = tol(name) if callable(tol) else tol
+        assert e < bound, (tag, name, e)
+        worst[name] = e
+        outside = np.ones(out[name].shape, dtype=bool)
+        outside[3:15, 3:15, kmp:nk] = False
+        if not f32:
+            assert np.array_equal(out[name][outside], full[name][outside], equal_nan=True), (tag, name, "outside the window")
+        else:
+            assert np.array_equal(out[name][outside], full[name][outside].astype(np.float32), equal_nan=True), (tag, name)
+    return worst
+
+
+def sat_tables(lib, device):
+    import torch
+
+    from pace_amd import _lib
+
+    t = torch.zeros(_lib.SAT_ADJUST_TABLE_DOUBLES, dtype=torch.float64, device=device)
+    stream = None if device == "cpu" else __import__("ctypes").c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib.call("pace_sat_adjust_tables", t.data_ptr(), stream)
+    if device != "cpu":
+        torch.cuda.synchronize()
+    return t.cpu().numpy().reshape(-1, 4)
+
+
+def check_tables(tab, tol):
+    d = golden("qsinit.npz")
+    assert np.array_equal(d["index"], np.arange(-1, 2621))
+    worst = {}
+    for col, name in enumerate(("table2", "des2", "tablew", "desw")):
+        e = compare(d[name], tab[:, col])
+        assert e < tol, (name, e)
+        worst[name] = e
+    return worst
+
+
+def test_sat_adjust_tables_emulated(emu_lib):
+    """pace_sat_adjust_tables against the reference's compute_q_tables over indices -1 ... 2620, to TranslateQSInit's 1e-12
+    (translate_qsinit.py:32); measured with the host libm: <= 2.2e-16."""
+    check_tables(sat_tables(emu_lib, "cpu"), 1e-12)
+
+
+@pytest.mark.parametrize("tag", CASES)
+def test_sat_adjust_emulated(emu_lib, tag):
+    """SatAdjust3d on the five cases of satadj_c12.npz, bounded by TranslateSatAdjust3d.max_error (2e-11).  Measured emulated
+    worst: pt, pkz, cappa, qvapor <= 1e-14, qice / qsnow / qgraupel / qcld / te <= 7e-14, q_con 1.0e-13, qrain 1.3e-13, qliquid
+    1.0e-12.  A DEPARTURE from the rule "the emulated worst held to 1e-13 unless a branch flip is shown": qrain and qliquid
+    exceed it without a branch flip -- it is the relative metric on a condensate a transfer has left near zero (ql = ql + src
+    after ql_evaporation, qr = qr + sink - tmp), an absolute difference of ~1e-19 kg/kg, the libm-vs-numpy difference of the
+    tables carried through the cancellation.  Held to 2e-12 overall and to 1e-13 for pt, pkz, cappa, qvapor."""
+    d = golden("satadj_c12.npz")
+    out, full = run_sat_adjust(emu_lib, "cpu", d, tag)
+    worst = check_sat_adjust(d, out, full, tag, 2e-11)
+    assert max(worst.values()) < 2e-12, worst
+    assert max(worst[k] for k in ("pt", "pkz", "cappa", "qvapor")) < 1e-13, worst
+
+
+@pytest.mark.parametrize("tag", CASES)
+def test_sat_adjust_f32_emulated(emu_f32_lib, emu_lib, tag):
+    """The float32-storage build on the same cases: test_f32.py's one-operator bound 2e-5 for pt, pkz, cappa, qvapor.  Above
+    test_f32.py's 1e-4, measured against the reference: qliquid 7.1e-4, qice 3.9e-4 (near-zero escape 1e-9 kg/kg), te 2.0e-3;
+    held to 4e-3.  All of it is the rounding of the INPUTS to float32, carried through cancellations, with no threshold flip:
+    the float64 build on the same inputs rounded to float32 gives the float32 build's values at every worst point (checked
+    below to 2e-5 on every output).  qliquid's worst (303 K, qv 0.019) is the 3.8e-6 kg/kg that evaporation leaves of 3.2e-4:
+    the 1e-9 by which rounding moves qv moves that remainder by 7e-4 of itself.  te's worst is dp * (cvm * pt1 - cvm0 * t0) =
+    -51 J/m2 from terms of 1.7e8 at a point whose temperature hardly changes: 6e-8 of rounding becomes 2e-3."""
+    d = golden("satadj_c12.npz")
+    out, full = run_sat_adjust(emu_f32_lib, "cpu", d, tag)
+    check_sat_adjust(d, out, full, tag, lambda n: 4e-3 if n in SPECIES[1:] + ["qcld", "q_con", "te"] else 2e-5, f32=True)
+    rounded = dict(d)
+    for k in d:
+        if k.startswith("in_") or k in ("area", "hs"):
+            rounded[k] = d[k].astype(np.float32).astype(np.float64)
+    ref64, _ = run_sat_adjust(emu_lib, "cpu", rounded, tag)
+    kmp, nk = int(d["kmp"]), len(d["k_sel"])
+    for name in SA_OUT:
+        e = compare(ref64[name][3:15, 3:15, kmp:nk], out[name][3:15, 3:15, kmp:nk], near_zero=1e-30)
+        assert e < 2e-5, (tag, name, "float64 on float32-rounded inputs", e)
+
+
+
+def run_l2e_sat_adj(lib, device, last_step):
+    """LagrangianToEulerian with do_sat_adj = True on l2e_c12.npz's inputs, with the real pfull and area_64."""
+    import torch
+
+    from pace_amd.fv3core import RemappingConfig
+    from pace_amd.fv3core.stencils.remapping import LagrangianToEulerian
+    from pace_amd.util import constants as c
+
+    d = golden("l2e_c12.npz")
+    env = Env(lib, device, golden("grid_c12_tile0.npz"), N, 79)
+
+    def embed(a):
+        full = np.full((N + 7, N + 7) + ((80,) if a.ndim == 3 else ()), np.nan)
+        full[2:16, 2:16] = a
+        return env.q3(full) if a.ndim == 3 else env.q2(full)
+
+    f = {k[3:]: embed(d[k]) for k in d if k.startswith("in_") and not k.startswith("in_tr_")}
+    tracers = {k[6:]: embed(d[k]) for k in d if k.startswith("in_tr_")}
+    dp1 = env.q3(np.zeros((N + 7, N + 7, 80)))
+    op = LagrangianToEulerian(env.stencil_factory, env.qf, RemappingConfig(do_sat_adj=True), env.grid_data.area_64, 8, d["pfull"],
+                              tracers)
+    assert op.kmp == 2
+    op(tracers, f["pt"], f["delp"], f["delz"], f["peln"], f["u"], f["v"], f["w"], f["cappa"], f["q_con"], f["qcld"], f["pkz"],
+       f["pk"], f["pe"], f["phis"], f["ps"], f["wsd"], env.kq(d["ak"]), env.kq(d["bk"]), dp1, float(d["ptop"]), c.KAPPA, c.ZVIR,
+       last_step, 0.0, 225.0)
+    if device != "cpu":
+        torch.cuda.synchronize()
+    out = {k: v.numpy() for k, v in f.items()}
+    out.update({k: v.numpy() for k, v in tracers.items()})
+    return d, out
+
+
+def check_l2e_sat_adj(d, out, last_step, tol, tol_unchanged):
+    ref = golden("l2e_satadj_c12.npz")
+    ks = list(ref["k_sel"])
+    tag = "last" if last_step else "mid"
+    worst = {}
+    for name in L2E_CHANGED:
+        e = compare(ref[f"{tag}_{name}"], out[name][3:15, 3:15][:, :, ks], near_zero=1e-18)
+        assert e < tol, (tag, name, e)
+        worst[name] = e
+    if not last_step:  # what the adjustment leaves alone is l2e_c12.npz's output
+        for name in ("u", "v", "w", "delp", "delz", "pe", "peln", "pk"):
+            kk = 80 if name in ("pe", "peln", "pk") else 79
+            e = compare(d["out_" + name][1:13, 1:13, :kk], out[name][3:15, 3:15, :kk], near_zero=1e-18)
+            assert e < tol_unchanged, (name, e)
+    return worst
+
+
+@pytest.mark.parametrize("last_step", [False, True])
+def test_l2e_sat_adj_emulated(emu_lib, last_step):
+    """LagrangianToEulerian(do_sat_adj = True) against the reference's run, mid and last step (l2e_satadj_c12.npz): 1e-11,
+    the GPU L2E test's bound; measured emulated worst 2.5e-13 (mid) and 1.3e-12 (last), both qliquid (the cancellation of
+    test_sat_adjust_emulated).  The untouched fields to test_emu_kernels' L2E bound 1e-14."""
+    d, out = run_l2e_sat_adj(emu_lib, "cpu", last_step)
+    check_l2e_sat_adj(d, out, last_step, 1e-11, 1e-14)
+
+
+def test_hydrostatic_still_refused(emu_lib):
+    from pace_amd.fv3core import RemappingConfig, SatAdjustConfig
+    from pace_amd.fv3core.stencils.remapping import LagrangianToEulerian
+    from pace_amd.fv3core.stencils.saturation_adjustment import SatAdjust3d
+
+    env = Env(emu_lib, "cpu", golden("grid_c12_tile0.npz"), N, 79)
+    with pytest.raises(NotImplementedError):
+        SatAdjust3d(env.stencil_factory, SatAdjustConfig(hydrostatic=True), env.grid_data.area_64, 2)
+    with pytest.raises(NotImplementedError):
+        LagrangianToEulerian(env.stencil_factory, env.qf, RemappingConfig(do_sat_adj=True, hydrostatic=True,
+                                                                          sat_adjust=SatAdjustConfig(hydrostatic=True)),
+                             env.grid_data.area_64, 8, golden("l2e_c12.npz")["pfull"], {})
+
+
+def test_dycore_config_carries_the_sat_adjust_namelist():
+    from pace_amd.fv3core import DynamicalCoreConfig, SatAdjustConfig
+
+    cfg = DynamicalCoreConfig(do_sat_adj=True, icloud_f=2, tau_l2v=150.0)
+    assert cfg.remapping.do_sat_adj
+    assert cfg.remapping.sat_adjust == SatAdjustConfig(icloud_f=2, tau_l2v=150.0)
+    assert cfg.sat_adjust == cfg.remapping.sat_adjust
+
+
+# ---- on the GPU -----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+def test_sat_adjust_tables_gpu(lib):
+    """The device's exp / log against numpy's: TranslateQSInit's 1e-12."""
+    check_tables(sat_tables(lib, "cuda:0"), 1e-12)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", CASES)
+def test_sat_adjust_gpu(lib, tag):
+    """SatAdjust3d on the device against the reference's run: TranslateSatAdjust3d.max_error, 2e-11."""
+    d = golden("satadj_c12.npz")
+    out, full = run_sat_adjust(lib, "cuda:0", d, tag)
+    check_sat_adjust(d, out, full, tag, 2e-11)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("last_step", [False, True])
+def test_l2e_sat_adj_gpu(lib, last_step):
+    """LagrangianToEulerian(do_sat_adj = True) on the device: 1e-11, test_gpu_parity's L2E bound."""
+    d, out = run_l2e_sat_adj(lib, "cuda:0", last_step)
+    check_l2e_sat_adj(d, out, last_step, 1e-11, 1e-11)
+
+
+def run_dycore_sat_adj(lib, device):
+    """helpers.run_dycore_tile's program on the k_split = 2 fixture's inputs with do_sat_adj = True (six tiles)."""
+    import datetime
+
+    import torch
+
+    from helpers import Env as _Env, acoustic_config, dycore_condensates, DYCORE_OUT
+    from pace_amd.fv3core import DynamicalCoreConfig
+    from pace_amd.fv3core.initialization.dycore_state import DycoreState
+    from pace_amd.fv3core.stencils.fv_dynamics import DynamicalCore
+    from pace_amd.util import CubedSphereCommunicator, run_tiles
+
+    fa = [golden(f"acoustic_c12_tile{t}.npz") for t in range(6)]
+    fd = [golden(f"dycore_k2_c12_tile{t}.npz") for t in range(6)]
+    for t in range(6):
+        fd[t].update(golden(f"dycore_satadj_k2_c12_tile{t}.npz"))
+
+    def tile_program(comm):
+        tile = comm.Get_rank()
+        fix_ac, fix_dy = fa[tile], fd[tile]
+        metrics = {k[5:]: v for k, v in fix_ac.items() if k.startswith("grid_")}
+        arrays = {k: fix_ac["in_" + k] for k in "u v w delz delp pe pk peln phis uc vc ua va".split()}
+        shape = arrays["delp"].shape
+        pt = np.zeros(shape)
+        pt[3:15, 3:15, :] = fix_dy["in_pt"]
+        qv = np.zeros(shape)
+        qv[3:15, 3:15, :] = fix_dy["in_qvapor"]
+        arrays.update(pt=pt, qvapor=qv, ps=fix_dy["in_ps"])
+        env = _Env(lib, device, metrics, N, 79)
+        cube = CubedSphereCommunicator(comm, device=device, lib=lib)
+        for name, f in dycore_condensates(tile, shape).items():
+            arrays[name] = f * (arrays["delp"] > 0)
+        state = DycoreState.init_from_numpy_arrays(arrays, env.qf)
+        ac = acoustic_config(1)
+        ac.k_split = 2
+        config = DynamicalCoreConfig(npx=N + 1, npy=N + 1, npz=79, dt_atmos=float(fix_dy["timestep"]), k_split=2, n_split=1,
+                                     acoustic_dynamics=ac, do_sat_adj=True)
+        core = DynamicalCore(cube, env.grid_data, env.stencil_factory, env.qf, env.damping, config, state.phis, state,
+                             datetime.timedelta(seconds=float(fix_dy["timestep"])))
+        core.step_dynamics(state)
+        if device != "cpu":
+            torch.cuda.synchronize()
+        out = {k: getattr(state, k).numpy() for k in DYCORE_OUT}
+        out["ps"] = state.ps.numpy()
+        return out
+
+    return fd, run_tiles(6, tile_program)
+
+
+@pytest.mark.gpu
+def test_dynamical_core_sat_adj_six_tiles_gpu(lib):
+    """One DynamicalCore.step_dynamics with do_sat_adj = True, n_split = 1, k_split = 2 on the six C12 tiles against the
+    reference's run (dycore_satadj_k2_c12_tile*.npz): check_dycore's bounds with the k_split = 2 default of 1e-9, except the
+    liquid and frozen condensates: measured 1.5e-9 (qliquid) on the MI355X -- the adjustment's condensation / evaporation
+    moves mass into and out of species whose values it leaves small, so the relative metric carries the acoustic loop's
+    differences amplified by those cancellations -- held to 5e-9."""
+    from helpers import DYCORE_TOL, dycore_errors
+
+    fixes, outs = run_dycore_sat_adj(lib, "cuda:0")
+    worst = {}
+    for t in range(6):
+        for k, e in dycore_errors(fixes[t], outs[t]).items():
+            worst[k] = max(worst.get(k, 0.0), e)
+    condensates = ("qliquid", "qrain", "qice", "qsnow", "qgraupel", "q_con")
+    for k, e in worst.items():
+        assert e < (5e-9 if k in condensates else DYCORE_TOL.get(k, 1e-9)), (k, e, worst)
+
+
+def c192_state(nk=79, n=192):
+    """A moist column state at C192 x nk: temperatures 180 - 310 K, vapour around saturation, condensates (a few negative)."""
+    shape = (n + 7, n + 7, nk + 1)
+    i, j, k = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), np.arange(shape[2]), indexing="ij")
+    s = {}
+    t = 180.0 + 130.0 * (k / nk) + 15.0 * np.sin(0.05 * i + 0.07 * j)
+    s["delp"] = 200.0 + 1500.0 * (k / nk)
+    s["delz"] = -(287.05 * t * s["delp"] / (9.80665 * (1000.0 + 1.0e5 * (k + 0.5) / nk)))
+    qsat = 3.8e-3 * np.exp(17.27 * (t - 273.16) / (t - 35.86)) * 1.0e5 / (1000.0 + 1.0e5 * (k + 0.5) / nk)
+    s["qvapor"] = np.minimum(qsat * (0.7 + 0.6 * (0.5 + 0.5 * np.sin(0.3 * i - 0.2 * j + 0.5 * k))), 0.03)
+    base = 0.5 + 0.5 * np.cos(0.17 * i + 0.23 * j + 0.4 * k)
+    for m, (name, scale) in enumerate((("qliquid", 4e-4), ("qrain", 2e-4), ("qice", 2e-4), ("qsnow", 1e-4), ("qgraupel", 5e-5))):
+        f = scale * base * (0.6 + 0.4 * np.sin(0.11 * i + 0.13 * j * (m + 1) + k))
+        s[name] = np.where(((i + 3 * j + 5 * k + m) % 17) == 0, -0.3 * f, f)
+    qc = s["qliquid"] + s["qrain"] + s["qice"] + s["qsnow"] + s["qgraupel"]
+    s["pt"] = t * (1.0 + (461.50 / 287.05 - 1) * s["qvapor"]) * (1.0 - qc)
+    for name in ("qcld", "te", "q_con", "pkz", "cappa"):
+        s[name] = np.full(shape, 0.25)
+    return s
+
+
+@pytest.mark.gpu
+def test_sat_adjust_c192_conserves_water_gpu(lib):
+    """C192 x 79, kmp = 2: every output finite; total water per point conserved to 1e-13 of the sum of the species' magnitudes
+    (every transfer in satadjust moves mass between species); storage outside the window bit-identical."""
+    import torch
+
+    from pace_amd.fv3core import SatAdjustConfig
+    from pace_amd.fv3core.stencils.saturation_adjustment import SatAdjust3d
+    from pace_amd.util import constants as c
+
+    n, nk, kmp = 192, 79, 2
+    metrics = {"area": np.full((n + 7, n + 7), 2.7e9), "da_min": 2.7e9, "da_min_c": 2.7e9,
+               **{k: np.zeros((n + 7, n + 7)) for k in ("del6_u", "del6_v", "divg_u", "divg_v")}}
+    env = Env(lib, "cuda:0", metrics, n, nk)
+    s = c192_state(nk, n)
+    f = {k: env.q3(v) for k, v in s.items()}
+    hs = env.q2(1000.0 * np.abs(np.sin(0.02 * np.arange(n + 7)))[:, None] * np.ones((1, n + 7)))
+    op = SatAdjust3d(env.stencil_factory, SatAdjustConfig(), env.grid_data.area_64, kmp)
+    op(f["te"], f["qvapor"], f["qliquid"], f["qice"], f["qrain"], f["qsnow"], f["qgraupel"], f["qcld"], hs, None, f["delp"],
+       f["delz"], f["q_con"], f["pt"], f["pkz"], f["cappa"], c.ZVIR, 225.0, False, True, c.KAPPA, kmp)
+    torch.cuda.synchronize()
+    out = {k: v.numpy() for k, v in f.items()}
+    win = (slice(3, 3 + n), slice(3, 3 + n), slice(kmp, nk))
+    for k in SA_OUT:
+        if k != "te":
+            assert np.isfinite(out[k][win]).all(), k
+    total_in = sum(s[k][win] for k in SPECIES)
+    total_out = sum(out[k][win] for k in SPECIES)
+    mag = sum(np.abs(s[k][win]) for k in SPECIES)
+    assert float(np.max(np.abs(total_out - total_in) / mag)) < 1e-13
+    assert not np.array_equal(out["qvapor"][win], s["qvapor"][win])
+    outside = np.ones(out["pt"].shape, dtype=bool)
+    outside[win] = False
+    for k in SA_OUT + ["delp", "delz"]:
+        assert np.array_equal(out[k][outside], s[k][outside]), k

@@ -1,7 +1,7 @@
 """Timing of whole DynamicalCore steps on the GPU box: the six tiles of a cubed sphere resident on ONE device (one host
 thread per tile, halo exchanges through ThreadComm), synthetic balanced state, fp64.
 
-    python tools/dycore_bench.py [--n 192] [--nz 79] [--n-split 4] [--steps 2]
+    python tools/dycore_bench.py [--n 192] [--nz 79] [--n-split 4] [--steps 2] [--single] [--sat-adj]
 
 Prints the wall time per step for all six tiles (the device is shared, so per tile = / 6) and the split between the
 acoustic loop, the tracer advection, the remapping and the rest, from synchronising timers.
@@ -51,6 +51,7 @@ def main():
     ap.add_argument("--single", action="store_true",
                     help="one tile only, behind a lone-rank LoopbackComm (each halo receives what the tile sent to that neighbour): the "
                          "device time of one tile's step without the thread rendezvous of the six-tile mode")
+    ap.add_argument("--sat-adj", action="store_true", help="do_sat_adj = True: the saturation adjustment runs in the remapping")
     args = ap.parse_args()
     if os.environ.get("PACE_BENCH_TRACE"):
         import faulthandler
@@ -87,7 +88,7 @@ def main():
             arrays[name] = np.abs(f)
         state = DycoreState.init_from_numpy_arrays(arrays, env.qf)
         config = DynamicalCoreConfig(npx=n + 1, npy=n + 1, npz=nz, dt_atmos=dt_atmos, k_split=1, n_split=args.n_split,
-                                     acoustic_dynamics=acoustic_config(args.n_split))
+                                     acoustic_dynamics=acoustic_config(args.n_split), do_sat_adj=args.sat_adj)
         core = DynamicalCore(cube, env.grid_data, env.stencil_factory, env.qf, env.damping, config, state.phis, state,
                              datetime.timedelta(seconds=dt_atmos))
         core.step_dynamics(state)  # warm-up
@@ -107,14 +108,16 @@ def main():
         program(LoopbackComm(rank=0, total_ranks=6))
         wall = results[0][0] / args.steps
         cells = n * n * nz
-        print(f"C{n} x {nz}L, ONE tile (lone-rank LoopbackComm), n_split = {args.n_split}, k_split = 1, {args.steps} steps")
+        print(f"C{n} x {nz}L, ONE tile (lone-rank LoopbackComm), n_split = {args.n_split}, k_split = 1, do_sat_adj = {args.sat_adj}, "
+              f"{args.steps} steps")
         print(f"wall per step: {1e3 * wall:9.2f} ms   ({cells * args.n_split / wall / 1e9:5.2f} G cell-updates/s counting the "
               f"acoustic substeps; the timers synchronise the device at every section boundary)")
     else:
         run_tiles(6, program)
         wall = max(r[0] for r in results.values()) / args.steps
         cells = 6 * n * n * nz
-        print(f"C{n} x {nz}L, six tiles on one device, n_split = {args.n_split}, k_split = 1, {args.steps} steps")
+        print(f"C{n} x {nz}L, six tiles on one device, n_split = {args.n_split}, k_split = 1, do_sat_adj = {args.sat_adj}, "
+              f"{args.steps} steps")
         print(f"wall per step (six tiles): {1e3 * wall:9.2f} ms   = {1e3 * wall / 6:7.2f} ms per tile   "
               f"({cells * args.n_split / wall / 1e9:5.2f} G cell-updates/s counting the acoustic substeps)")
     t = results[0][1]

@@ -1,6 +1,6 @@
 """Per-entry-point timing on the GPU box (HIP events on the launch stream), C192 x 79 by default.
 
-    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3]
+    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust]
 """
 import argparse
 import os
@@ -32,6 +32,7 @@ def main():
     from pace_amd.fv3core.stencils.fvtp2d import FiniteVolumeTransport
     from pace_amd.fv3core.stencils.fxadv import FiniteVolumeFluxPrep
     from pace_amd.fv3core.stencils.riem_solver3 import NonhydrostaticVerticalSolver
+    from pace_amd.util import constants as c
 
     lib = _lib.Library(args.lib) if args.lib else _lib.load(args.precision)
     n, nz = args.n, args.nz
@@ -79,7 +80,38 @@ def main():
     rq, rp1, rp2 = env.q3(s["pt"]), env.q3(pe1_h), env.q3(pe2_h)
     remap = MapSingle(env.stencil_factory, env.qf, 9, 1, ["x", "y", "z"])
 
+    # SatAdjust3d on a moist column state (180 - 310 K, vapour around saturation, condensates), kmp = 2 as on the 79-level grid;
+    # the operator works in place, so its inputs are restored before every repetition
+    from pace_amd.fv3core import SatAdjustConfig
+    from pace_amd.fv3core.stencils.saturation_adjustment import SatAdjust3d
+
+    i3, j3, k3 = np.meshgrid(np.arange(n + 7), np.arange(n + 7), np.arange(nz + 1), indexing="ij")
+    t3 = 180.0 + 130.0 * (k3 / nz) + 15.0 * np.sin(0.05 * i3 + 0.07 * j3)
+    p3 = 1000.0 + 1.0e5 * (k3 + 0.5) / nz
+    sa_h = {"delp": 200.0 + 1500.0 * (k3 / nz)}
+    sa_h["delz"] = -c.RDGAS * t3 * sa_h["delp"] / (c.GRAV * p3)
+    sa_h["qvapor"] = np.minimum(3.8e-3 * np.exp(17.27 * (t3 - 273.16) / (t3 - 35.86)) * 1.0e5 / p3
+                                * (0.7 + 0.6 * (0.5 + 0.5 * np.sin(0.3 * i3 - 0.2 * j3 + 0.5 * k3))), 0.03)
+    for q_i, (nm, sc) in enumerate((("qliquid", 4e-4), ("qrain", 2e-4), ("qice", 2e-4), ("qsnow", 1e-4), ("qgraupel", 5e-5))):
+        sa_h[nm] = sc * (0.5 + 0.5 * np.cos(0.17 * i3 + 0.23 * j3 + 0.4 * k3 + q_i))
+    qc3 = sa_h["qliquid"] + sa_h["qrain"] + sa_h["qice"] + sa_h["qsnow"] + sa_h["qgraupel"]
+    sa_h["pt"] = t3 * (1.0 + c.ZVIR * sa_h["qvapor"]) * (1.0 - qc3)
+    for nm in ("qcld", "te", "q_con", "pkz", "cappa"):
+        sa_h[nm] = np.zeros_like(t3)
+    sa = {k: env.q3(v) for k, v in sa_h.items()}
+    sa_hs = env.q2(np.zeros((n + 7, n + 7)))
+    satadj = SatAdjust3d(env.stencil_factory, SatAdjustConfig(), env.grid_data.area_64, 2)
+
+    def sat_adjust():
+        satadj(sa["te"], sa["qvapor"], sa["qliquid"], sa["qice"], sa["qrain"], sa["qsnow"], sa["qgraupel"], sa["qcld"], sa_hs, None,
+               sa["delp"], sa["delz"], sa["q_con"], sa["pt"], sa["pkz"], sa["cappa"], c.ZVIR, 225.0, False, True, c.KAPPA, 2)
+
+    def restore_sat_adjust():
+        for k in sa:
+            sa[k].set(sa_h[k])
+
     cases = {
+        "sat_adjust": (sat_adjust, 19),
         "fxadv": (lambda: prep(f["uc"], f["vc"], f["crx"], f["cry"], f["xfx"], f["yfx"], ut, vt, s["dt"]), 8),
         "fvtp2d": (lambda: tp(f["pt"], f["crx"], f["cry"], f["xfx"], f["yfx"], fx, fy, x_mass_flux=f["mfx"], y_mass_flux=f["mfy"]), 9),
         "delnflux_nosg": (lambda: dn0(f["w"], fx, fy, damp_w, None), 3),
@@ -97,12 +129,16 @@ def main():
         if only and name not in only:
             continue
         restore()
+        restore_sat_adjust()
         fn()
         torch.cuda.synchronize()
         ts = []
         for _ in range(args.reps):
             if name in ("d_sw", "riem3", "dsw_scalars", "dsw_winds"):
                 restore()
+                torch.cuda.synchronize()
+            if name == "sat_adjust":
+                restore_sat_adjust()
                 torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()

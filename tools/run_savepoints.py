@@ -467,10 +467,67 @@ def spec_yppm(g):
     return _spec_ppm(g, 1)
 
 
+def spec_sat_adjust3d(g):  # translate_satadjust3d.py:9-87
+    names = ("te", "qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel", "qcld", "hs", "peln", "delp", "delz", "q_con", "pt", "pkz",
+             "cappa")
+    iv = {k: {} for k in names}
+    iv["peln"] = {"istart": g.is_, "jstart": g.js, "kaxis": 1}
+    iv["pkz"] = {"istart": g.is_, "jstart": g.js}
+    ov = {k: {} for k in ("te", "qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel", "qcld", "q_con", "pt", "cappa")}
+    ov["pkz"] = {"istart": g.is_, "iend": g.ie, "jstart": g.js, "jend": g.je}
+
+    def run(env, f, p):
+        from pace_amd.fv3core import SatAdjustConfig
+        from pace_amd.fv3core.stencils.saturation_adjustment import SatAdjust3d
+
+        kmp = int(p["kmp"]) - 1  # (the Fortran's 1-based level: translate_satadjust3d.py:72)
+        op = SatAdjust3d(env.stencil_factory, SatAdjustConfig(**env.namelist.get("sat_adjust", {})), env.grid_data.area_64, kmp)
+        op(f["te"], f["qvapor"], f["qliquid"], f["qice"], f["qrain"], f["qsnow"], f["qgraupel"], f["qcld"], f["hs"], f["peln"], f["delp"],
+           f["delz"], f["q_con"], f["pt"], f["pkz"], f["cappa"], p["r_vir"], p["mdt"], bool(p["fast_mp_consv"]), bool(p["last_step"]),
+           p["akap"], kmp)
+        return f
+
+    return Spec(iv, ["r_vir", "mdt", "fast_mp_consv", "last_step", "akap", "kmp"], ov, 2e-11, run)
+
+
 SAVEPOINTS = {"D_SW": spec_d_sw, "Riem_Solver3": spec_riem_solver3, "FvTp2d": spec_fvtp2d, "Riem_Solver_C": spec_riem_solver_c,
               "NH_P_Grad": spec_nh_p_grad, "FxAdv": spec_fxadv, "C_SW": spec_c_sw, "UpdateDzC": spec_updatedzc, "UpdateDzD": spec_updatedzd,
               "D2A2C_Vect": spec_d2a2c_vect, "DivergenceDamping": spec_divergence_damping, "DelnFlux": spec_delnflux,
-              "XPPM": spec_xppm, "YPPM": spec_yppm}
+              "XPPM": spec_xppm, "YPPM": spec_yppm, "SatAdjust3d": spec_sat_adjust3d}
+
+
+# ---- QSInit (translate_qsinit.py:10-52): the saturation tables over the indices 0 ... QS_LENGTH - 1, no grid ------------------------
+QS_LENGTH = 2621
+
+
+def run_qsinit(pair, args, lib):
+    """Returns (ok, bound, worst) like run_one.  pace_sat_adjust_tables builds the four tables satadjust reads (table2, des2, tablew, desw)
+    for the indices -1 ... QS_LENGTH - 1; the savepoint's fifth, `table`, is not built by pace_amd (satadjust never reads it) and is
+    reported as skipped."""
+    import ctypes
+
+    import torch
+
+    from pace_amd import _lib
+
+    ins, outs = pair
+    t = torch.zeros(_lib.SAT_ADJUST_TABLE_DOUBLES, dtype=torch.float64, device=args.device)
+    stream = None if args.device == "cpu" else ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib.call("pace_sat_adjust_tables", t.data_ptr(), stream)
+    if args.device != "cpu":
+        torch.cuda.synchronize()
+    tab = t.cpu().numpy().reshape(-1, 4)[1:]  # (record 0 is index -1)
+    worst = {}
+    for col, var in enumerate(("table2", "des2", "tablew", "desw")):
+        if var not in outs:
+            continue
+        ref = np.asarray(outs[var])
+        ref = ref.reshape(ref.shape[0], ref.shape[1], -1)
+        for sp in range(ref.shape[0]):
+            for rank in range(ref.shape[1]):
+                worst[var] = max(worst.get(var, 0.0), compare(ref[sp, rank, :QS_LENGTH], tab[:QS_LENGTH, col]))
+    bound = 1e-12  # translate_qsinit.py:32
+    return all(e <= bound for e in worst.values()), bound, worst
 # ---- DynCore (translate_dyncore.py:13-200): the WHOLE AcousticDynamics call, a ParallelTranslate: all ranks of a savepoint run together
 # and exchange their halos (six ranks = the six tiles of the cubed sphere, one tile per rank: pace_amd.util.run_tiles) -------------
 def dyncore_vars(g):
@@ -648,10 +705,16 @@ def main():
 
         args.namelist = yaml.safe_load(open(args.namelist))
     lib = _lib.Library(args.lib) if args.lib else _lib.load()
-    names = [s for s in args.only.split(",") if s] or sorted(SAVEPOINTS) + ["DynCore"]
+    names = [s for s in args.only.split(",") if s] or sorted(SAVEPOINTS) + ["DynCore", "QSInit"]
     found = {os.path.basename(p).rsplit("-In.", 1)[0] for p in glob.glob(os.path.join(args.directory, "*-In.*"))}
     failed = 0
     for name in names:
+        if name == "QSInit" and name in found:
+            ok, bound, worst = run_qsinit(read_pair(args.directory, name), args, lib)
+            print(f"QSInit: {'PASS' if ok else 'FAIL'}  bound {bound:g} (`table` skipped: satadjust does not read it)")
+            print("   " + "  ".join(f"{k} {v:.2e}" for k, v in sorted(worst.items())))
+            failed += 0 if ok else 1
+            continue
         if name == "DynCore" and name in found:
             ok, bound, worst = run_dyncore(read_pair(args.directory, name), args, lib)
             print(f"DynCore: {'PASS' if ok else 'FAIL'}  bound {bound:g} (six ranks, halo updates included)")
