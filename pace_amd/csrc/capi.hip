@@ -2,6 +2,7 @@
 // struct unpacking only; kernels live in k_*.hip.
 #include "common.h"
 #include "kernels.h"
+#include "thermo.h"
 
 #include <cstdio>
 
@@ -364,7 +365,7 @@ int pace_gz_from_surface_height_and_thicknesses(const pace_geom_t* geom, const r
 
 int pace_compute_geopotential(const pace_geom_t* geom, const real* zh, real* gz, void* stream) {
   NEED(geom && zh && gz);
-  return launch_scale_copy(make_geo(geom), zh, gz, 9.80665, 1, 2, geom->nk + 1, S(stream));
+  return launch_scale_copy(make_geo(geom), zh, gz, phys::GRAV, 1, 2, geom->nk + 1, S(stream));
 }
 
 int pace_copy(const pace_geom_t* geom, const real* src, real* dst, void* stream) {

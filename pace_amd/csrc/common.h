@@ -520,6 +520,19 @@ static inline dim3 patch_grid(const Geo& g, int nlev) {
   const int j = (int)blockIdx.y * PATCH_H + (int)threadIdx.y;     \
   const int k = (int)blockIdx.z;                                  \
   if (j >= (g).nj || i >= (g).ni) return;
+// thread of a 64 x 4 patch (launch with dim3(64, 4)) -> cell i, j of the compute domain widened by (DI, DJ) at its high end,
+// level k = K0 + blockIdx.z, with c2 = its index in a plane and c = in the field
+#define CELL_IJK(g, DI, DJ, K0)                                   \
+  const int i = (g).is + blockIdx.x * 64 + threadIdx.x;           \
+  const int j = (g).js + blockIdx.y * 4 + threadIdx.y;            \
+  const int k = (K0) + blockIdx.z;                                \
+  if (i > (g).ie + (DI) || j > (g).je + (DJ)) return;             \
+  const long c2 = IDX2(g, i, j);                                  \
+  const long c = c2 + (long)k * (g).sk;                           \
+  (void)c2
+static inline dim3 cell_grid(const Geo& g, int di, int dj, int nlev) {
+  return dim3((unsigned)((g.n + di + 63) / 64), (unsigned)((g.n + dj + 3) / 4), (unsigned)nlev);
+}
 // flattened plane index -> (i, j); returns false for pad lanes / out of plane
 #define PLANE_IJK(g)                                                  \
   const long p__ = (long)blockIdx.x * 256 + threadIdx.x;             \

@@ -13,13 +13,7 @@
 
 #include "common.h"
 #include "kernels.h"
-
-#define GRAV 9.80665
-#define RDGAS 287.05
-#define CP_AIR 1004.6
-#define CV_AIR (CP_AIR - RDGAS)
-#define RDG (-RDGAS / GRAV)
-#define DZ_MIN 2.0
+#include "thermo.h"
 
 // fill_corners_2cells_{x,y} with unit multipliers as read-side maps (corners.py:129-305); same maps as k_csw.hip
 __device__ __forceinline__ long zc_xfill(const Geo& g, int i, int j) {
@@ -146,7 +140,7 @@ k_updatedzc_column(Geo g, const real* __restrict__ zs, const real* __restrict__ 
 #pragma unroll
     for (int t = 0; t < CHC; ++t)
       if (k0 - t >= 0) {
-        const double lim = below + DZ_MIN;
+        const double lim = below + phys::DZ_MIN;
         below = (v[t] > lim) ? v[t] : lim;
         gz[c0 + (long)(k0 - t) * g.sk] = below;
       }
@@ -269,7 +263,6 @@ k_spline_to_interfaces_lds(Geo g, SplineK s, const real* __restrict__ q0, const 
   }
 }
 
-
 // The same with the forward sweep's values in REGISTERS (km <= 80): the LDS form holds 48 KB per 64 columns -- three waves per
 // CU, each a serial chain of km divisions: 86 us at C192 x 79 for 205 MB moved.  160 registers of forward values leave two
 // waves per SIMD (eight per CU), and the levels are read sixteen at a time ahead of the chain.
@@ -361,7 +354,7 @@ k_height_column(Geo g, const real* __restrict__ zs, const real* zin, real* zh, r
     for (int t = 0; t < CHZ; ++t) {
       const int k = k0 - t;
       if (k >= 0) {
-        const double other = below + DZ_MIN;
+        const double other = below + phys::DZ_MIN;
         const double v = (z_[t] > other) ? z_[t] : other;
         zh[c0 + (long)k * g.sk] = v;
         below = v;
@@ -970,8 +963,8 @@ k_diffusive_heating(Geo g, const real* __restrict__ delp, const real* __restrict
   PLANE_IJK(g);
   if (i < g.is || i > g.ie || j < g.js || j > g.je) return;
   const long c = IDX3(g, i, j, k);
-  const double pkz = pow(RDG * delp[c] / delz[c] * pt[c], cappa[c] / (1.0 - cappa[c]));
-  const double dtmp = heat_source[c] / (CV_AIR * delp[c]);
+  const double pkz = pow(phys::RDG * delp[c] / delz[c] * pt[c], cappa[c] / (1.0 - cappa[c]));
+  const double dtmp = heat_source[c] / (phys::CV_AIR * delp[c]);
   const double fac = (k == 0) ? 0.1 : (k == 1) ? 0.5 : 1.0;
   const double lim = delt_time_factor * fac;
   const double mag = fmin(lim, fabs(dtmp));

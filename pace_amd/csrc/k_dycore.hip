@@ -10,48 +10,22 @@
 //   k_c2l             CubedToLatLon, both orders (stencils/pace/stencils/c2l_ord.py:15-112)
 #include "common.h"
 #include "kernels.h"
-
-#define PACE_GRAV 9.80665
-#define PACE_RDGAS 287.05
-#define PACE_RVGAS 461.50
-#define PACE_CP_AIR 1004.6
-#define PACE_CV_AIR (PACE_CP_AIR - PACE_RDGAS)
-#define PACE_RDG (-PACE_RDGAS / PACE_GRAV)
-#define PACE_ZVIR (PACE_RVGAS / PACE_RDGAS - 1)
-#define PACE_CV_VAP (3.0 * PACE_RVGAS)
-#define PACE_C_ICE 1972.0
-#define PACE_C_LIQ 4.1855e3
-#define PACE_HLV 2.5e6
-#define PACE_HLF 3.3358e5
-#define PACE_TICE 273.16
-#define PACE_DC_ICE (PACE_C_LIQ - PACE_C_ICE)
-#define PACE_LI0 (PACE_HLF - PACE_DC_ICE * PACE_TICE)
-
-struct Water6 {
-  real *qvapor, *qliquid, *qrain, *qsnow, *qice, *qgraupel;
-};
-
-#define CELL_IJK()                                     \
-  const int i = g.is + blockIdx.x * 64 + threadIdx.x;  \
-  const int j = g.js + blockIdx.y * 4 + threadIdx.y;   \
-  const int k = blockIdx.z;                            \
-  if (i > g.ie || j > g.je) return;                    \
-  const long c = IDX3(g, i, j, k)
+#include "thermo.h"
 
 __global__ void __launch_bounds__(256)
 k_fv_setup_pt(Geo g, Water6 q, real* __restrict__ q_con, real* __restrict__ pkz, real* __restrict__ pt,
               real* __restrict__ cappa, const real* __restrict__ delp, const real* __restrict__ delz,
               real* __restrict__ dp1) {
-  CELL_IJK();
+  CELL_IJK(g, 0, 0, 0);
   const double qv = q.qvapor[c];
   const double ql = q.qliquid[c] + q.qrain[c];
   const double qs = q.qice[c] + q.qsnow[c] + q.qgraupel[c];
   const double gz = ql + qs;
-  const double cvm = (1.0 - (qv + gz)) * PACE_CV_AIR + qv * PACE_CV_VAP + ql * PACE_C_LIQ + qs * PACE_C_ICE;
-  const double d1 = PACE_ZVIR * qv;
-  const double cp = PACE_RDGAS / (PACE_RDGAS + cvm / (1.0 + d1));
+  const double cvm = moist_cvm(qv + gz, qv, ql, qs);
+  const double d1 = phys::ZVIR * qv;
+  const double cp = moist_cappa(cvm, 1.0 + d1);
   const double p = pt[c];
-  const double pz = exp(cp * log(PACE_RDG * delp[c] * p * (1.0 + d1) * (1.0 - gz) / delz[c]));
+  const double pz = exp(cp * log(phys::RDG * delp[c] * p * (1.0 + d1) * (1.0 - gz) / delz[c]));
   q_con[c] = gz;
   dp1[c] = d1;
   cappa[c] = cp;
@@ -62,20 +36,20 @@ k_fv_setup_pt(Geo g, Water6 q, real* __restrict__ q_con, real* __restrict__ pkz,
 __global__ void __launch_bounds__(256)
 k_omega_from_w(Geo g, const real* __restrict__ delp, const real* __restrict__ delz, const real* __restrict__ w,
                real* __restrict__ omga) {
-  CELL_IJK();
+  CELL_IJK(g, 0, 0, 0);
   omga[c] = delp[c] / delz[c] * w[c];
 }
 
 __global__ void __launch_bounds__(256)
 k_fix_neg_water(Geo g, Water6 q, real* __restrict__ ptf, double lv00, double d0_vap) {
-  CELL_IJK();
+  CELL_IJK(g, 0, 0, 0);
   double qv = q.qvapor[c], ql = q.qliquid[c], qr = q.qrain[c], qs = q.qsnow[c], qi = q.qice[c], qg = q.qgraupel[c];
   double pt = ptf[c];
   const double q_liq = 0.0 > ql + qr ? 0.0 : ql + qr;
   const double q_sol = 0.0 > qi + qs ? 0.0 : qi + qs;
-  const double cpm = (1.0 - (qv + q_liq + q_sol)) * PACE_CV_AIR + qv * PACE_CV_VAP + q_liq * PACE_C_LIQ + q_sol * PACE_C_ICE;
+  const double cpm = moist_cvm(qv + q_liq + q_sol, qv, q_liq, q_sol);
   const double lcpk = (lv00 + d0_vap * pt) / cpm;
-  const double icpk = (PACE_LI0 + PACE_DC_ICE * pt) / cpm;
+  const double icpk = (phys::LI00 + phys::DC_ICE * pt) / cpm;
   double dq;
   // fix_negative_ice (neg_adj3.py:13-54)
   {
@@ -316,29 +290,26 @@ k_c2l(Geo g, Met m, const real* __restrict__ u, const real* __restrict__ v, cons
   va[c] = a21[c2] * ut + a22[c2] * vt;
 }
 
-static dim3 cell_grid(const Geo& g, int pad) { return dim3((g.n + 2 * pad + 63) / 64, (g.n + 2 * pad + 3) / 4, g.nk); }
-
-static Water6 water6(real* const* w) { return Water6{w[0], w[1], w[2], w[3], w[4], w[5]}; }
-
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st) {
-  hipLaunchKernelGGL(k_fv_setup_pt, cell_grid(g, 0), dim3(64, 4), 0, st, g, water6(water), q_con, pkz, pt, cappa, delp, delz, dp1);
+  hipLaunchKernelGGL(k_fv_setup_pt, cell_grid(g, 0, 0, g.nk), dim3(64, 4), 0, st, g, water6(water), q_con, pkz, pt, cappa, delp, delz,
+                     dp1);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }
 
 int launch_omega_from_w(const Geo& g, const real* delp, const real* delz, const real* w, real* omga, hipStream_t st) {
-  hipLaunchKernelGGL(k_omega_from_w, cell_grid(g, 0), dim3(64, 4), 0, st, g, delp, delz, w, omga);
+  hipLaunchKernelGGL(k_omega_from_w, cell_grid(g, 0, 0, g.nk), dim3(64, 4), 0, st, g, delp, delz, w, omga);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }
 
 int launch_neg_adj3(const Geo& g, real* const* water, real* qcld, real* pt, const real* delp, hipStream_t st) {
   if (g.nk < 4) return PACE_ERR_UNSUPPORTED;
-  const double d0_vap = PACE_CV_VAP - PACE_C_LIQ;        // non-hydrostatic (neg_adj3.py:327-332)
-  const double lv00 = PACE_HLV - d0_vap * PACE_TICE;
+  const double d0_vap = phys::CV_VAP - phys::C_LIQ;  // non-hydrostatic (neg_adj3.py:327-332)
+  const double lv00 = phys::HLV - d0_vap * phys::TICE;
   const Water6 q = water6(water);
-  hipLaunchKernelGGL(k_fix_neg_water, cell_grid(g, 0), dim3(64, 4), 0, st, g, q, pt, lv00, d0_vap);
+  hipLaunchKernelGGL(k_fix_neg_water, cell_grid(g, 0, 0, g.nk), dim3(64, 4), 0, st, g, q, pt, lv00, d0_vap);
   hipLaunchKernelGGL(k_neg_columns, dim3((g.n + 63) / 64, g.n, 4), dim3(64), 0, st, g, q.qgraupel, q.qrain, q.qvapor, qcld, delp);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
@@ -346,8 +317,9 @@ int launch_neg_adj3(const Geo& g, real* const* water, real* qcld, real* pt, cons
 
 int launch_c2l(const Geo& g, const Met& m, int order, const real* u, const real* v, const real* a11, const real* a12,
                const real* a21, const real* a22, real* ua, real* va, hipStream_t st) {
-  if (order == 2) hipLaunchKernelGGL(k_c2l<2>, cell_grid(g, 1), dim3(64, 4), 0, st, g, m, u, v, a11, a12, a21, a22, ua, va);
-  else hipLaunchKernelGGL(k_c2l<4>, cell_grid(g, 0), dim3(64, 4), 0, st, g, m, u, v, a11, a12, a21, a22, ua, va);
+  // order 2: the compute domain and one cell around it, n + 2 points from is - 1
+  if (order == 2) hipLaunchKernelGGL(k_c2l<2>, cell_grid(g, 2, 2, g.nk), dim3(64, 4), 0, st, g, m, u, v, a11, a12, a21, a22, ua, va);
+  else hipLaunchKernelGGL(k_c2l<4>, cell_grid(g, 0, 0, g.nk), dim3(64, 4), 0, st, g, m, u, v, a11, a12, a21, a22, ua, va);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }

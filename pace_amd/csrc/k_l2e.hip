@@ -8,50 +8,25 @@
 //   k_l2e_finish     update_ua + copy_from_below, then moist_pt_last_step or the division by pkz
 #include "common.h"
 #include "kernels.h"
-
-// util/pace/util/constants.py:36-75 (GFS_PHYS branch)
-#define PACE_GRAV 9.80665
-#define PACE_RDGAS 287.05
-#define PACE_RVGAS 461.50
-#define PACE_CP_AIR 1004.6
-#define PACE_CV_AIR (PACE_CP_AIR - PACE_RDGAS)
-#define PACE_RDG (-PACE_RDGAS / PACE_GRAV)
-#define PACE_CV_VAP (3.0 * PACE_RVGAS)
-#define PACE_C_ICE 1972.0
-#define PACE_C_LIQ 4.1855e3
-
-struct L2eWater {
-  const real *qvapor, *qliquid, *qrain, *qsnow, *qice, *qgraupel;
-};
+#include "thermo.h"
 
 // moist_cv_nwat6_fn + moist_cvm + set_cappa (moist_cv.py:16-46)
-__device__ __forceinline__ void moist_cv(const L2eWater& q, long c, double r_vir, double& gz, double& cappa) {
+__device__ __forceinline__ void moist_cv(const Water6Const& q, long c, double r_vir, double& gz, double& cappa) {
   const double qv = q.qvapor[c];
   const double ql = q.qliquid[c] + q.qrain[c];
   const double qs = q.qice[c] + q.qsnow[c] + q.qgraupel[c];
   gz = ql + qs;
-  const double cvm = (1.0 - (qv + gz)) * PACE_CV_AIR + qv * PACE_CV_VAP + ql * PACE_C_LIQ + qs * PACE_C_ICE;
-  cappa = PACE_RDGAS / (PACE_RDGAS + cvm / (1.0 + r_vir * qv));
+  cappa = moist_cappa(moist_cvm(qv + gz, qv, ql, qs), 1.0 + r_vir * qv);
 }
 
-#define L2E_CELL(NJX, NKX)                                       \
-  const int i = g.is + blockIdx.x * 64 + threadIdx.x;            \
-  const int j = g.js + blockIdx.y * 4 + threadIdx.y;             \
-  const int k = blockIdx.z;                                      \
-  (void)k;                                                       \
-  if (i > g.ie || j > g.je + (NJX)) return;                      \
-  const long c2 = IDX2(g, i, j);                                 \
-  const long c = c2 + (long)k * g.sk;                            \
-  const int km = g.nk;                                           \
-  (void)km
-
 __global__ void __launch_bounds__(256)
-k_l2e_prepare(Geo g, L2eWater q, real* __restrict__ q_con, real* __restrict__ pt, real* __restrict__ cappa,
+k_l2e_prepare(Geo g, Water6Const q, real* __restrict__ q_con, real* __restrict__ pt, real* __restrict__ cappa,
               real* __restrict__ delp, real* __restrict__ delz, const real* __restrict__ pe, real* __restrict__ pe1,
               real* __restrict__ pe2, const real* __restrict__ ak, const real* __restrict__ bk, real* __restrict__ dp2,
               real* __restrict__ ps, real* __restrict__ pn2, const real* __restrict__ peln, real* __restrict__ pk,
               double ptop, double akap, double r_vir) {
-  L2E_CELL(1, 1);
+  CELL_IJK(g, 0, 1, 0);
+  const int km = g.nk;
   // init_pe over the compute domain + the extra row je+1 (remapping.py:42-56)
   pe1[c] = pe[c];
   if (k == 0) pe2[c] = ptop;
@@ -69,7 +44,7 @@ k_l2e_prepare(Geo g, L2eWater q, real* __restrict__ q_con, real* __restrict__ pt
   q_con[c] = gz;
   cappa[c] = cp;
   const double p = pt[c], dpo = delp[c], dzo = delz[c];
-  pt[c] = p * exp(cp / (1.0 - cp) * log(PACE_RDG * dpo / dzo * p));
+  pt[c] = p * exp(cp / (1.0 - cp) * log(phys::RDG * dpo / dzo * p));
   delz[c] = -dzo / dpo;
   // pressure_updates + pn2_pk_delp (remapping.py:155-193)
   const double e0 = (k == 0) ? ptop : ak[k] + bk[k] * psv;
@@ -84,10 +59,11 @@ k_l2e_prepare(Geo g, L2eWater q, real* __restrict__ q_con, real* __restrict__ pt
 }
 
 __global__ void __launch_bounds__(256)
-k_l2e_post(Geo g, L2eWater q, real* __restrict__ q_con, real* __restrict__ pkz, const real* __restrict__ pt,
+k_l2e_post(Geo g, Water6Const q, real* __restrict__ q_con, real* __restrict__ pkz, const real* __restrict__ pt,
            real* __restrict__ cappa, const real* __restrict__ delp, real* __restrict__ delz, real* __restrict__ peln,
            real* __restrict__ pe0, const real* __restrict__ pn2, double r_vir) {
-  L2E_CELL(0, 1);
+  CELL_IJK(g, 0, 0, 0);
+  const int km = g.nk;
   pe0[c] = peln[c];
   peln[c] = pn2[c];
   if (k == km) return;
@@ -97,7 +73,7 @@ k_l2e_post(Geo g, L2eWater q, real* __restrict__ q_con, real* __restrict__ pkz, 
   moist_cv(q, c, r_vir, gz, cp);
   q_con[c] = gz;
   cappa[c] = cp;
-  pkz[c] = exp(cp * log(PACE_RDG * delp[c] / dz * pt[c]));
+  pkz[c] = moist_pkz(cp, delp[c], dz, pt[c]);
 }
 
 // dir 0: pressures_mapu (neighbour to the south, window + 1 row); dir 1: pressures_mapv (neighbour to the west, + 1 column)
@@ -105,13 +81,8 @@ template <int DIR>
 __global__ void __launch_bounds__(256)
 k_l2e_pressures(Geo g, const real* __restrict__ pe, const real* __restrict__ pe1, const real* __restrict__ ak,
                 const real* __restrict__ bk, real* __restrict__ pe0, real* __restrict__ pe3) {
-  const int i = g.is + blockIdx.x * 64 + threadIdx.x;
-  const int j = g.js + blockIdx.y * 4 + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i > g.ie + (DIR == 1 ? 1 : 0) || j > g.je + (DIR == 0 ? 1 : 0)) return;
+  CELL_IJK(g, DIR == 1 ? 1 : 0, DIR == 0 ? 1 : 0, 0);
   const int km = g.nk;
-  const long c2 = IDX2(g, i, j);
-  const long c = c2 + (long)k * g.sk;
   const long nb = DIR == 0 ? -(long)g.sj : -1L;
   const long cb = c2 + (long)km * g.sk;
   if (DIR == 0) {
@@ -131,9 +102,10 @@ k_l2e_pressures(Geo g, const real* __restrict__ pe, const real* __restrict__ pe1
 }
 
 __global__ void __launch_bounds__(256)
-k_l2e_finish(Geo g, L2eWater q, real* __restrict__ pe, const real* __restrict__ pe2, real* __restrict__ pt,
+k_l2e_finish(Geo g, Water6Const q, real* __restrict__ pe, const real* __restrict__ pe2, real* __restrict__ pt,
              const real* __restrict__ pkz, double r_vir, int last_step) {
-  L2E_CELL(0, 1);
+  CELL_IJK(g, 0, 0, 0);
+  const int km = g.nk;
   if (k >= 1 && k < km) pe[c] = pe2[c];  // update_ua + copy_from_below: pe becomes the Eulerian interfaces
   if (last_step) {
     // moist_pt_last_step over km + 1 levels with dtmp = 0 (moist_cv.py:73-122, remapping.py:680-692)
@@ -144,14 +116,12 @@ k_l2e_finish(Geo g, L2eWater q, real* __restrict__ pe, const real* __restrict__ 
   }
 }
 
-static dim3 l2e_grid(const Geo& g, int xi, int xj, int nlev) { return dim3((g.n + xi + 63) / 64, (g.n + xj + 3) / 4, nlev); }
-
 int launch_l2e_prepare(const Geo& g, const real* const* water, real* q_con, real* pt, real* cappa, real* delp,
                        real* delz, const real* pe, real* pe1, real* pe2, const real* ak, const real* bk, real* dp2,
                        real* ps, real* pn2, const real* peln, real* pk, double ptop, double akap, double r_vir,
                        hipStream_t st) {
-  L2eWater q{water[0], water[1], water[2], water[3], water[4], water[5]};
-  hipLaunchKernelGGL(k_l2e_prepare, l2e_grid(g, 0, 1, g.nk + 1), dim3(64, 4), 0, st, g, q, q_con, pt, cappa, delp, delz, pe, pe1,
+  const Water6Const q = water6(water);
+  hipLaunchKernelGGL(k_l2e_prepare, cell_grid(g, 0, 1, g.nk + 1), dim3(64, 4), 0, st, g, q, q_con, pt, cappa, delp, delz, pe, pe1,
                      pe2, ak, bk, dp2, ps, pn2, peln, pk, ptop, akap, r_vir);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
@@ -159,8 +129,8 @@ int launch_l2e_prepare(const Geo& g, const real* const* water, real* q_con, real
 
 int launch_l2e_post(const Geo& g, const real* const* water, real* q_con, real* pkz, const real* pt, real* cappa,
                     const real* delp, real* delz, real* peln, real* pe0, const real* pn2, double r_vir, hipStream_t st) {
-  L2eWater q{water[0], water[1], water[2], water[3], water[4], water[5]};
-  hipLaunchKernelGGL(k_l2e_post, l2e_grid(g, 0, 0, g.nk + 1), dim3(64, 4), 0, st, g, q, q_con, pkz, pt, cappa, delp, delz, peln,
+  const Water6Const q = water6(water);
+  hipLaunchKernelGGL(k_l2e_post, cell_grid(g, 0, 0, g.nk + 1), dim3(64, 4), 0, st, g, q, q_con, pkz, pt, cappa, delp, delz, peln,
                      pe0, pn2, r_vir);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
@@ -168,16 +138,16 @@ int launch_l2e_post(const Geo& g, const real* const* water, real* q_con, real* p
 
 int launch_l2e_pressures(const Geo& g, int dir, const real* pe, const real* pe1, const real* ak, const real* bk,
                          real* pe0, real* pe3, hipStream_t st) {
-  if (dir == 0) hipLaunchKernelGGL(k_l2e_pressures<0>, l2e_grid(g, 0, 1, g.nk + 1), dim3(64, 4), 0, st, g, pe, pe1, ak, bk, pe0, pe3);
-  else hipLaunchKernelGGL(k_l2e_pressures<1>, l2e_grid(g, 1, 0, g.nk + 1), dim3(64, 4), 0, st, g, pe, pe1, ak, bk, pe0, pe3);
+  if (dir == 0) hipLaunchKernelGGL(k_l2e_pressures<0>, cell_grid(g, 0, 1, g.nk + 1), dim3(64, 4), 0, st, g, pe, pe1, ak, bk, pe0, pe3);
+  else hipLaunchKernelGGL(k_l2e_pressures<1>, cell_grid(g, 1, 0, g.nk + 1), dim3(64, 4), 0, st, g, pe, pe1, ak, bk, pe0, pe3);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }
 
 int launch_l2e_finish(const Geo& g, const real* const* water, real* pe, const real* pe2, real* pt, const real* pkz,
                       double r_vir, int last_step, hipStream_t st) {
-  L2eWater q{water[0], water[1], water[2], water[3], water[4], water[5]};
-  hipLaunchKernelGGL(k_l2e_finish, l2e_grid(g, 0, 0, g.nk + 1), dim3(64, 4), 0, st, g, q, pe, pe2, pt, pkz, r_vir, last_step);
+  const Water6Const q = water6(water);
+  hipLaunchKernelGGL(k_l2e_finish, cell_grid(g, 0, 0, g.nk + 1), dim3(64, 4), 0, st, g, q, pe, pe2, pt, pkz, r_vir, last_step);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }

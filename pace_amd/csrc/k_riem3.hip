@@ -14,12 +14,8 @@
 // temporaries (delta_mass, gamma, g_rat, bb, dd, pe_init, log p) are never stored.
 #include "common.h"
 #include "kernels.h"
+#include "thermo.h"
 
-#define RDGAS 287.05
-#define GRAV 9.80665
-#define RGRAV (1.0 / GRAV)
-#define CP_AIR 1004.6
-#define KAPPA (RDGAS / CP_AIR)
 #ifndef RIEM_CH
 #define RIEM_CH 8
 #endif
@@ -94,7 +90,7 @@ k_riem3_parallel_pre(Geo g, Riem3Work W, int last_call, double peln1, double ptk
     if (last_call) peln[c] = peln1;
   } else {
     const double logp = log(W.pem[c]);
-    pk3[c] = exp(KAPPA * logp);
+    pk3[c] = exp(phys::KAPPA * logp);
     if (last_call) peln[c] = logp;
   }
   if (k < km) {
@@ -105,9 +101,9 @@ k_riem3_parallel_pre(Geo g, Riem3Work W, int last_call, double peln1, double ptk
     W.pm[c] = pmk;
     const double dz = zh[c + g.sk] - zh[c];
     delz[c] = dz;
-    const double dm = delp[c] * RGRAV;
+    const double dm = delp[c] * phys::RGRAV;
     const double gm = 1.0 / (1.0 - cappa[c]);
-    ppe[c] = exp(gm * log(-dm / dz * RDGAS * pt[c])) - pmk;
+    ppe[c] = exp(gm * log(-dm / dz * phys::RDGAS * pt[c])) - pmk;
   }
 }
 
@@ -122,7 +118,7 @@ k_riem3_tridiag(Geo g, Riem3Work W, double dt, const real* __restrict__ cappa, c
                 T* __restrict__ w) {
   COLUMN_IJH(g, CG);
   const double t1g = 2.0 * dt * dt, rdt = 1.0 / dt;
-#define DM(x) (CG ? (x) / GRAV : (x)*RGRAV)
+#define DM(x) (CG ? (x) / phys::GRAV : (x)*phys::RGRAV)
   // ---- sweep 1 (forward): gam, pp of the first system
   {
     double dm_k = DM(delp[AT(0)]), dm_n = DM(delp[AT(1)]);
@@ -343,11 +339,11 @@ k_riem3_parallel_post(Geo g, Riem3Work W, int last_call, const real* __restrict_
   if (i < g.is || i > g.ie || j < g.js || j > g.je) return;
   const long c = IDX3(g, i, j, k);
   if (k < g.nk) {
-    const double dm = delp[c] * RGRAV;
+    const double dm = delp[c] * phys::RGRAV;
     const double p1 = W.pp[c], pmk = W.pm[c];
     // NB: the reference tests p_fac * delta_mass (sim1_solver.py:134), kept as is
     const double maxp = (p_fac * dm > p1 + pmk) ? p_fac * pmk : p1 + pmk;
-    delz[c] = -dm * RDGAS * pt[c] * exp((cappa[c] - 1.0) * log(maxp));
+    delz[c] = -dm * phys::RDGAS * pt[c] * exp((cappa[c] - 1.0) * log(maxp));
   }
   if (last_call) {
     pk[c] = pk3[c];
@@ -393,7 +389,7 @@ int launch_riem_solver3(const Geo& g, void* ws, int last_call, double dt, const 
   W.pp = p + 4 * field;
   W.aa = p + 5 * field;
   const double peln1 = log(ptop);
-  const double ptk = exp(KAPPA * peln1);
+  const double ptk = exp(phys::KAPPA * peln1);
   const dim3 cgrid((g.n + 63) / 64, g.n, 1), cblock(64);
   const dim3 pgrid = plane_grid(g, g.nk + 1), pblock(256);
   hipLaunchKernelGGL(k_riem3_prefix<0>, cgrid, cblock, 0, st, g, W, ptop, delp, q_con);
@@ -432,9 +428,9 @@ k_riemc_parallel_pre(Geo g, RiemCWork W, const real* __restrict__ cappa, const r
   W.r.pm[c] = pmk;
   const double dz = gz[c + g.sk] - gz[c];
   W.dz[c] = dz;
-  const double dm = delpc[c] / GRAV;
+  const double dm = delpc[c] / phys::GRAV;
   const double gm = 1.0 / (1.0 - cappa[c]);
-  W.pe[c] = exp(gm * log(-dm / dz * RDGAS * ptc[c])) - pmk;
+  W.pe[c] = exp(gm * log(-dm / dz * phys::RDGAS * ptc[c])) - pmk;
   W.w[c] = w3[c];
 }
 
@@ -446,10 +442,10 @@ k_riemc_parallel_post(Geo g, RiemCWork W, double ptop, const real* __restrict__ 
   if (i < g.is - 1 || i > g.ie + 1 || j < g.js - 1 || j > g.je + 1) return;
   const long c = IDX3(g, i, j, k);
   if (k < g.nk) {
-    const double dm = delpc[c] / GRAV;
+    const double dm = delpc[c] / phys::GRAV;
     const double p1 = W.r.pp[c], pmk = W.r.pm[c];
     const double maxp = (p_fac * dm > p1 + pmk) ? p_fac * pmk : p1 + pmk;
-    W.dz[c] = -dm * RDGAS * ptc[c] * exp((cappa[c] - 1.0) * log(maxp));
+    W.dz[c] = -dm * phys::RDGAS * ptc[c] * exp((cappa[c] - 1.0) * log(maxp));
   }
   pef[c] = (k == 0) ? ptop : W.pe[c] + W.r.pem[c];
 }
@@ -470,7 +466,7 @@ k_riemc_gz(Geo g, const real* __restrict__ hs, const wreal* __restrict__ dz, rea
     for (int t = 0; t < CH; ++t) {
       const int k = k0 - t;
       if (k >= 0) {
-        z = z - d_[t] * GRAV;
+        z = z - d_[t] * phys::GRAV;
         gz[AT(k)] = z;
       }
     }

@@ -26,12 +26,8 @@
 // row, so every line fetched is used completely by the workgroup (through the CU's vector L1 / the L2).
 #include "common.h"
 #include "kernels.h"
+#include "thermo.h"
 
-#define RDGAS 287.05
-#define GRAV 9.80665
-#define RGRAV (1.0 / GRAV)
-#define CP_AIR 1004.6
-#define KAPPA (RDGAS / CP_AIR)
 #define ROW 16  // lanes per column
 
 namespace {
@@ -453,7 +449,7 @@ k_riem_column(Geo g, int last_call, double dt, double ptop, double p_fac, double
 #define LEV(t) (k0 + (t))
 #define ON(t) (LEV(t) < km)
 #define CL(k) ((k) < km ? (k) : km - 1)
-#define DM(x) (CG ? (x) / GRAV : (x) * RGRAV)
+#define DM(x) (CG ? (x) / phys::GRAV : (x) * phys::RGRAV)
 
   RIEM_STAMP(0);
   // ---------------- loads ----------------
@@ -524,7 +520,7 @@ k_riem_column(Geo g, int last_call, double dt, double ptop, double p_fac, double
         pm_[t] = (pg_[t + 1] - pg_[t]) / (lg - lg_prev);
         lg_prev = lg;
       }
-      pe0_[t] = col_exp<CG>(gm_[t] * col_log<CG>(-dm_[t] / dz_[t] * RDGAS * pt_[t])) - pm_[t];
+      pe0_[t] = col_exp<CG>(gm_[t] * col_log<CG>(-dm_[t] / dz_[t] * phys::RDGAS * pt_[t])) - pm_[t];
     }
   }
   RIEM_STAMP(2);
@@ -544,7 +540,7 @@ k_riem_column(Geo g, int last_call, double dt, double ptop, double p_fac, double
           pk3v = ptk;
         } else {
           logp = col_log<CG>(pem_[t]);
-          pk3v = col_exp<CG>(KAPPA * logp);
+          pk3v = col_exp<CG>(phys::KAPPA * logp);
         }
         MINE(0, k) = pk3v;
         if (last_call) {
@@ -786,8 +782,8 @@ k_riem_column(Geo g, int last_call, double dt, double ptop, double p_fac, double
   for (int t = 0; t < L; ++t) {
     // NB: the reference tests p_fac * delta_mass (sim1_solver.py:134), kept as is
     const double maxp = (p_fac * dm_[t] > p1_[t] + pm_[t]) ? p_fac * pm_[t] : p1_[t] + pm_[t];
-    dzn_[t] = -dm_[t] * RDGAS * pt_[t] * col_exp<CG>((ca_[t] - 1.0) * col_log<CG>(maxp));
-    if (ON(t)) sdz = sdz + (CG ? dzn_[t] * GRAV : dzn_[t]);
+    dzn_[t] = -dm_[t] * phys::RDGAS * pt_[t] * col_exp<CG>((ca_[t] - 1.0) * col_log<CG>(maxp));
+    if (ON(t)) sdz = sdz + (CG ? dzn_[t] * phys::GRAV : dzn_[t]);
   }
   RIEM_STAMP(9);
   {
@@ -799,7 +795,7 @@ k_riem_column(Geo g, int last_call, double dt, double ptop, double p_fac, double
     for (int t = L - 1; t >= 0; --t) {
       if (!ON(t)) continue;
       if (LEV(t) == km - 1) MINE(0, km) = z;
-      z = z - (CG ? dzn_[t] * GRAV : dzn_[t]);
+      z = z - (CG ? dzn_[t] * phys::GRAV : dzn_[t]);
       MINE(0, LEV(t)) = z;
     }
   }
@@ -848,7 +844,7 @@ static int launch_column(const Geo& g, int last_call, double dt, double ptop, do
                          const real* ws, const real* q_con, const real* delp, const real* pt, real* delz, real* zh,
                          real* pe, real* ppe, real* pk3, real* pk, real* peln, real* w, hipStream_t st) {
   const double peln1 = log(ptop);
-  const double ptk = exp(KAPPA * peln1);
+  const double ptk = exp(phys::KAPPA * peln1);
   const int ncol = g.n + 2 * CG;
   const dim3 grid(ColumnWindows(g.is - CG, g.ie + CG).workgroups(), ncol), block(256);
 #define GO(L)                                                                                                                  \

@@ -8,29 +8,7 @@
 // Arithmetic is fp64 in both builds, in the reference's order of operations (no division folded into a reciprocal).
 #include "common.h"
 #include "kernels.h"
-
-// util/pace/util/constants.py:36-97 (GFS_PHYS branch)
-#define PACE_GRAV 9.80665
-#define PACE_RDGAS 287.05
-#define PACE_RVGAS 461.50
-#define PACE_RDG (-PACE_RDGAS / PACE_GRAV)
-#define PACE_HLV 2.5e6
-#define PACE_HLF 3.3358e5
-#define PACE_C_ICE 1972.0
-#define PACE_C_LIQ 4.1855e3
-#define PACE_CP_VAP (4.0 * PACE_RVGAS)
-#define PACE_TICE 273.16
-#define PACE_DC_ICE (PACE_C_LIQ - PACE_C_ICE)
-#define PACE_DC_VAP (PACE_CP_VAP - PACE_C_LIQ)
-#define PACE_D2ICE (PACE_DC_VAP + PACE_DC_ICE)
-#define PACE_LV0 (PACE_HLV - PACE_DC_VAP * PACE_TICE)
-#define PACE_LI00 (PACE_HLF - PACE_DC_ICE * PACE_TICE)
-#define PACE_LI2 (PACE_LV0 + PACE_LI00)
-#define PACE_E00 611.21
-#define PACE_T_WFR (PACE_TICE - 40.0)
-#define PACE_TICE0 (PACE_TICE - 0.01)
-#define PACE_T_SAT_MIN (PACE_TICE - 160.0)
-#define PACE_LAT2 ((PACE_HLV + PACE_HLF) * (PACE_HLV + PACE_HLF))
+#include "thermo.h"
 
 // saturation_adjustment.py:27-33
 #define SA_DELT 0.1
@@ -41,11 +19,11 @@
 
 // ---- the tables, as the reference evaluates them on the fly (:36-160) ----------------------------------------------------
 __device__ __forceinline__ double sa_q_table_oneline(double dhc, double lhc, double tem) {
-  return PACE_E00 * exp((dhc * log(tem / PACE_TICE) + (tem - PACE_TICE) / (tem * PACE_TICE) * lhc) / PACE_RVGAS);
+  return phys::E00 * exp((dhc * log(tem / phys::TICE) + (tem - phys::TICE) / (tem * phys::TICE) * lhc) / phys::RVGAS);
 }
-__device__ __forceinline__ double sa_vapor(double tem) { return sa_q_table_oneline(PACE_DC_VAP, PACE_LV0, tem); }
-__device__ __forceinline__ double sa_ice(double tem) { return sa_q_table_oneline(PACE_D2ICE, PACE_LI2, tem); }
-__device__ __forceinline__ double sa_tem_lower(double i) { return PACE_T_SAT_MIN + SA_DELT * i; }
+__device__ __forceinline__ double sa_vapor(double tem) { return sa_q_table_oneline(phys::DC_VAP, phys::LV0, tem); }
+__device__ __forceinline__ double sa_ice(double tem) { return sa_q_table_oneline(phys::D2ICE, phys::LI2, tem); }
+__device__ __forceinline__ double sa_tem_lower(double i) { return phys::T_SAT_MIN + SA_DELT * i; }
 __device__ __forceinline__ double sa_tem_upper(double i) { return 253.16 + SA_DELT * i; }
 
 // qs_table2_fn (:84-121), with its blend of the ice and water tables at i = 1599 and 1600
@@ -55,7 +33,7 @@ __device__ double sa_table2(int i) {
   if (i == 1599) {
     double table = sa_ice(tem0);
     tem0 = sa_tem_upper(i - 1400);
-    table = (0.05 * (PACE_TICE - tem0)) * table + (0.05 * (tem0 - 253.16)) * sa_vapor(tem0);
+    table = (0.05 * (phys::TICE - tem0)) * table + (0.05 * (tem0 - 253.16)) * sa_vapor(tem0);
     const double m1 = sa_ice(sa_tem_lower(1598));
     const double p1 = sa_vapor(sa_tem_lower(1600));
     table2 = 0.25 * (m1 + 2.0 * table + p1);
@@ -90,10 +68,6 @@ __global__ void __launch_bounds__(256) k_sat_adjust_tables(double* __restrict__ 
 }
 
 // ---- satadjust -------------------------------------------------------------------------------------------------------------
-struct SatWater {
-  real *qvapor, *qliquid, *qrain, *qsnow, *qice, *qgraupel;
-};
-
 struct SatTab {
   double t, d;  // table2 / des2 (ice phase, T = 0) or tablew / desw (water, T = 2)
 };
@@ -107,7 +81,7 @@ __device__ __forceinline__ double sa_dim(double a, double b) { return a - b > 0 
 
 // ap1_for_wqs2 (:502-505); the index is clamped to the tables (it only matters for a non-finite temperature)
 __device__ __forceinline__ double sa_ap1(double ta) {
-  const double ap1 = 10.0 * sa_dim(ta, PACE_T_SAT_MIN) + 1.0;
+  const double ap1 = 10.0 * sa_dim(ta, phys::T_SAT_MIN) + 1.0;
   return fmin(ap1, (double)SA_QS_LENGTH) - 1;
 }
 __device__ __forceinline__ int sa_idx(double f) {
@@ -123,7 +97,7 @@ __device__ __forceinline__ void sa_wqs2(const double* __restrict__ tab, double t
   const SatTab a = sa_rec<T>(tab, sa_idx(it));
   const double d2 = sa_rec<T>(tab, sa_idx(it2)).d, d2p1 = sa_rec<T>(tab, sa_idx(it2 + 1)).d;
   const double es = a.t + (ap1 - it) * a.d;
-  const double denom = PACE_RVGAS * ta * den;
+  const double denom = phys::RVGAS * ta * den;
   wqsat = es / denom;
   dqdt = 10.0 * (d2 + (ap1 - it2) * (d2p1 - d2));
   dqdt = dqdt / denom;
@@ -134,24 +108,19 @@ template <int T>
 __device__ __forceinline__ double sa_wqs1(const double* __restrict__ tab, double it, double ap1, double ta, double den) {
   const SatTab a = sa_rec<T>(tab, sa_idx(it));
   const double es = a.t + (ap1 - it) * a.d;
-  return es / (PACE_RVGAS * ta * den);
+  return es / (phys::RVGAS * ta * den);
 }
 
 __device__ __forceinline__ double sa_cvm(double mc_air, double qv, double c_vap, double q_liq, double q_sol) {
-  return mc_air + qv * c_vap + q_liq * PACE_C_LIQ + q_sol * PACE_C_ICE;
+  return mc_air + qv * c_vap + q_liq * phys::C_LIQ + q_sol * phys::C_ICE;
 }
 
 __global__ void __launch_bounds__(256)
-k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te0_out, real* __restrict__ ptf,
+k_sat_adjust(Geo g, Water6 q, real* __restrict__ qa_out, real* __restrict__ te0_out, real* __restrict__ ptf,
              real* __restrict__ q_con_out, real* __restrict__ pkz_out, real* __restrict__ cappa_out, const real* __restrict__ dpf,
              const real* __restrict__ delzf, const real* __restrict__ areaf, const real* __restrict__ hsf,
              const double* __restrict__ tab, pace_sat_adjust_params_t p, int kmp, int last_step, int consv_te) {
-  const int i = g.is + blockIdx.x * 64 + threadIdx.x;
-  const int j = g.js + blockIdx.y * 4 + threadIdx.y;
-  const int k = kmp + blockIdx.z;
-  if (i > g.ie || j > g.je) return;
-  const long c2 = IDX2(g, i, j);
-  const long c = c2 + (long)k * g.sk;
+  CELL_IJK(g, 0, 0, kmp);
 
   double qv = q.qvapor[c], ql = q.qliquid[c], qi = q.qice[c], qr = q.qrain[c], qs = q.qsnow[c], qg = q.qgraupel[c];
   const double dp = dpf[c], delz = delzf[c];
@@ -163,10 +132,10 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
   double pt1 = ptf[c] / ((1.0 + p.zvir * qv) * (1.0 - qpz));
   const double t0 = pt1;
   qpz = qpz + qv;
-  const double den = -dp / (PACE_GRAV * delz);
+  const double den = -dp / (phys::GRAV * delz);
   const double mc_air = (1.0 - qpz) * c_air;
   double cvm = sa_cvm(mc_air, qv, c_vap, q_liq, q_sol);
-  double lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  double lhi = phys::LI00 + phys::DC_ICE * pt1;
   double icp2 = lhi / cvm;
   double lhl, lcp2;
   double te0 = 0.0;
@@ -177,8 +146,8 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
     qi = 0.0;
   }
   // melt_cloud_ice (:183-197)
-  if ((qi > 1.0e-8) && (pt1 > PACE_TICE)) {
-    const double factmp = p.fac_imlt * (pt1 - PACE_TICE) / icp2;
+  if ((qi > 1.0e-8) && (pt1 > phys::TICE)) {
+    const double factmp = p.fac_imlt * (pt1 - phys::TICE) / icp2;
     double sink = qi < factmp ? qi : factmp;
     qi = qi - sink;
     ql = ql + sink;
@@ -188,7 +157,7 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
     sink = -sink;
     pt1 = pt1 + sink * lhi / cvm;
   }
-  lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  lhi = phys::LI00 + phys::DC_ICE * pt1;
   icp2 = lhi / cvm;
   // fix_negative_snow (:200-209)
   if (qs < 0.0) {
@@ -211,7 +180,7 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
   }
   // complete_freezing (:227-238)
   {
-    const double dtmp = PACE_TICE - 48.0 - pt1;
+    const double dtmp = phys::TICE - 48.0 - pt1;
     if (ql > 0.0 && dtmp > 0.0) {
       const double sink = fmin(ql, dtmp / icp2);
       ql = ql - sink;
@@ -226,9 +195,9 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
   sa_wqs2<2>(tab, pt1, den, wqsat, dq2dt);
   lhl = p.lv00 + p.d0_vap * pt1;
   lcp2 = lhl / cvm;
-  lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  lhi = phys::LI00 + phys::DC_ICE * pt1;
   icp2 = lhi / cvm;
-  double tcp3 = lcp2 + icp2 * fmin(1.0, sa_dim(PACE_TICE, pt1) / 48.0);
+  double tcp3 = lcp2 + icp2 * fmin(1.0, sa_dim(phys::TICE, pt1) / 48.0);
   double dq0 = (qv - wqsat) / (1.0 + tcp3 * dq2dt);
   double src;
   if (dq0 > 0) {  // whole grid - box saturated
@@ -245,9 +214,9 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
   pt1 = pt1 + src * lhl / cvm;
   lhl = p.lv00 + p.d0_vap * pt1;
   lcp2 = lhl / cvm;
-  lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  lhi = phys::LI00 + phys::DC_ICE * pt1;
   icp2 = lhi / cvm;
-  tcp3 = lcp2 + icp2 * fmin(1.0, sa_dim(PACE_TICE, pt1) / 48.0);
+  tcp3 = lcp2 + icp2 * fmin(1.0, sa_dim(phys::TICE, pt1) / 48.0);
   if (last_step) {
     sa_wqs2<2>(tab, pt1, den, wqsat, dq2dt);
     dq0 = (qv - wqsat) / (1.0 + tcp3 * dq2dt);
@@ -264,12 +233,12 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
     pt1 = pt1 + src * lhl / cvm;
     lhl = p.lv00 + p.d0_vap * pt1;
     lcp2 = lhl / cvm;
-    lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+    lhi = phys::LI00 + phys::DC_ICE * pt1;
     icp2 = lhi / cvm;
   }
   // homogenous_freezing (:241-253)
   {
-    const double dtmp = PACE_T_WFR - pt1;
+    const double dtmp = phys::T_WFR - pt1;
     if (ql > 0.0 && dtmp > 0.0) {
       double sink = fmin(ql, dtmp / icp2);
       sink = fmin(sink, ql * dtmp * 0.125);
@@ -281,12 +250,12 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
       pt1 = pt1 + sink * lhi / cvm;
     }
   }
-  lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  lhi = phys::LI00 + phys::DC_ICE * pt1;
   icp2 = lhi / cvm;
   // heterogeneous_freezing, the Bigg mechanism (:257-272)
   {
-    const double exptc = exp(0.66 * (PACE_TICE0 - pt1));
-    const double tc = PACE_TICE0 - pt1;
+    const double exptc = exp(0.66 * (phys::TICE0 - pt1));
+    const double tc = phys::TICE0 - pt1;
     if (ql > 0.0 && tc > 0.0) {
       double sink = 3.3333e-10 * p.mdt * (exptc - 1.0) * den * (ql * ql);
       sink = fmin(ql, sink);
@@ -299,11 +268,11 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
       pt1 = pt1 + sink * lhi / cvm;
     }
   }
-  lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  lhi = phys::LI00 + phys::DC_ICE * pt1;
   icp2 = lhi / cvm;
   // make_graupel (:275-290)
   {
-    const double dtmp = (PACE_TICE - 0.1) - pt1;
+    const double dtmp = (phys::TICE - 0.1) - pt1;
     if (qr > 1e-7 && dtmp > 0.0) {
       const double rainfac = (dtmp * 0.025) * (dtmp * 0.025);
       const double tmp = 1.0 < rainfac ? qr : rainfac * qr;
@@ -316,11 +285,11 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
       pt1 = pt1 + sink * lhi / cvm;
     }
   }
-  lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  lhi = phys::LI00 + phys::DC_ICE * pt1;
   icp2 = lhi / cvm;
   // melt_snow (:293-314)
   {
-    const double dtmp = pt1 - (PACE_TICE + 0.1);
+    const double dtmp = pt1 - (phys::TICE + 0.1);
     const double dimqs = sa_dim(p.qs_mlt, ql);
     if (qs > 1e-7 && dtmp > 0.0) {
       const double snowfac = (dtmp * 0.1) * (dtmp * 0.1);
@@ -347,7 +316,7 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
   const double expsubl = exp(0.875 * log(qi * den));
   lhl = p.lv00 + p.d0_vap * pt1;
   lcp2 = lhl / cvm;
-  lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+  lhi = phys::LI00 + phys::DC_ICE * pt1;
   icp2 = lhi / cvm;
   const double tcp2 = lcp2 + icp2;
   const double adj_fac = last_step ? 1.0 : p.sat_adj0;
@@ -356,18 +325,18 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
     double src = 0.0;
     if (pt1 < p.t_sub) {
       src = sa_dim(qv, 1e-6);
-    } else if (pt1 < PACE_TICE0) {
+    } else if (pt1 < phys::TICE0) {
       const double dq = qv - iqs2;
       const double sink = adj_fac * dq / (1.0 + tcp2 * dqsdt);
       double pidep;
       if (qi > 1.0e-8) {
         pidep = p.sdt * dq * 349138.78 * expsubl /
-                (iqs2 * den * PACE_LAT2 / (0.0243 * PACE_RVGAS * (pt1 * pt1)) + 4.42478e4);
+                (iqs2 * den * phys::LAT2 / (0.0243 * phys::RVGAS * (pt1 * pt1)) + 4.42478e4);
       } else {
         pidep = 0.0;
       }
       if (dq > 0.0) {
-        const double tmp = PACE_TICE - pt1;
+        const double tmp = phys::TICE - pt1;
         const double qi_crt = p.qi_lim < 0.1 * tmp ? p.qi_gen * p.qi_lim / den : p.qi_gen * 0.1 * tmp / den;
         const double maxtmp = qi_crt - qi > pidep ? qi_crt - qi : pidep;
         src = sink < maxtmp ? sink : maxtmp;
@@ -390,7 +359,7 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
   const double q_con = q_liq + q_sol;
   double tmp = 1.0 + p.zvir * qv;
   const double pt = pt1 * tmp * (1.0 - q_con);
-  tmp *= PACE_RDGAS;
+  tmp *= phys::RDGAS;
   const double cappa = tmp / (tmp + cvm);
   // fix negative graupel with available cloud ice
   if (qg < 0) {
@@ -410,7 +379,7 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
     cvm = mc_air + (qv + q_liq + q_sol) * c_vap;
     lhl = p.lv00 + p.d0_vap * pt1;
     lcp2 = lhl / cvm;
-    lhi = PACE_LI00 + PACE_DC_ICE * pt1;
+    lhi = phys::LI00 + phys::DC_ICE * pt1;
     icp2 = lhi / cvm;
     // combine water species
     if (p.rad_snow) q_sol = p.rad_graupel ? qi + qs + qg : qi + qs;
@@ -423,16 +392,16 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
     const double wqs1 = sa_wqs1<2>(tab, it, ap1, tin, den);
     const double iqs1 = sa_wqs1<0>(tab, it, ap1, tin, den);
     double qstar;
-    if (tin < PACE_T_WFR) {
+    if (tin < phys::T_WFR) {
       qstar = iqs1;
-    } else if (tin >= PACE_TICE) {
+    } else if (tin >= phys::TICE) {
       qstar = wqs1;
     } else {
-      const double rqi = q_cond > 1e-6 ? q_sol / q_cond : (PACE_TICE - tin) / (PACE_TICE - PACE_T_WFR);
+      const double rqi = q_cond > 1e-6 ? q_sol / q_cond : (phys::TICE - tin) / (phys::TICE - phys::T_WFR);
       qstar = rqi * iqs1 + (1.0 - rqi) * wqs1;
     }
     // higher than 10 m is "land", with more subgrid variability; "scale-aware": 100 km as the base
-    const double mindw = fmin(1.0, fabs((double)hsf[c2]) / (10.0 * PACE_GRAV));
+    const double mindw = fmin(1.0, fabs((double)hsf[c2]) / (10.0 * phys::GRAV));
     const double dw = p.dw_ocean + (p.dw_land - p.dw_ocean) * mindw;
     const double dbl_sqrt_area = dw * sqrt(sqrt((double)areaf[c2]) / 100.0e3);
     const double hvar = fmin(0.2, fmax(0.01, dbl_sqrt_area));
@@ -478,7 +447,7 @@ k_sat_adjust(Geo g, SatWater q, real* __restrict__ qa_out, real* __restrict__ te
   q_con_out[c] = q_con;
   cappa_out[c] = cappa;
   // compute_pkz_func (moist_cv.py:125-127)
-  pkz_out[c] = exp(cappa * log(PACE_RDG * dp / delz * pt));
+  pkz_out[c] = moist_pkz(cappa, dp, delz, pt);
 }
 
 int launch_sat_adjust_tables(double* tables, hipStream_t st) {
@@ -490,8 +459,7 @@ int launch_sat_adjust_tables(double* tables, hipStream_t st) {
 int launch_sat_adjust(const Geo& g, real* const* water, real* qcld, real* te, real* pt, real* q_con, real* pkz, real* cappa,
                       const real* delp, const real* delz, const real* area, const real* hs, const double* tables,
                       const pace_sat_adjust_params_t& p, int kmp, int last_step, int consv_te, hipStream_t st) {
-  SatWater q{water[0], water[1], water[2], water[3], water[4], water[5]};
-  hipLaunchKernelGGL(k_sat_adjust, dim3((g.n + 63) / 64, (g.n + 3) / 4, g.nk - kmp), dim3(64, 4), 0, st, g, q, qcld, te, pt,
+  hipLaunchKernelGGL(k_sat_adjust, cell_grid(g, 0, 0, g.nk - kmp), dim3(64, 4), 0, st, g, water6(water), qcld, te, pt,
                      q_con, pkz, cappa, delp, delz, area, hs, tables, p, kmp, last_step, consv_te);
   PACE_CHECK_LAUNCH();
   return PACE_OK;

@@ -5,8 +5,7 @@
 // (five fields), written for the stand-alone class and its test.
 #include "common.h"
 #include "kernels.h"
-
-#define RDGAS 287.05  // constants.py:RDGAS (as in k_riem3.hip)
+#include "thermo.h"
 
 struct Sim1Work {
   real *pp, *gam, *aa, *w1, *p1;
@@ -29,7 +28,7 @@ k_sim1_solver(Geo g, Sim1Work W, int halo, double dt, double p_fac, const real* 
 #define AT(k) (c0 + (long)(k)*g.sk)
   // :57-62 (PARALLEL): the pressure of the layers, w1 = w
   for (int k = 0; k < km; ++k) {
-    pe[AT(k)] = exp(gm[AT(k)] * log(-dm[AT(k)] / dz[AT(k)] * RDGAS * pt[AT(k)])) - pm[AT(k)];
+    pe[AT(k)] = exp(gm[AT(k)] * log(-dm[AT(k)] / dz[AT(k)] * phys::RDGAS * pt[AT(k)])) - pm[AT(k)];
     W.w1[AT(k)] = w[AT(k)];
   }
   // :63-87: first system (pp on interfaces), forward
@@ -99,7 +98,7 @@ k_sim1_solver(Geo g, Sim1Work W, int halo, double dt, double p_fac, const real* 
     const double p1 = W.p1[AT(k)];
     // NB the reference compares p_fac * delta_mass (not p_fac * pm) -- sim1_solver.py:134
     const double maxp = (p_fac * dm[AT(k)] > p1 + pm[AT(k)]) ? p_fac * pm[AT(k)] : p1 + pm[AT(k)];
-    dz[AT(k)] = -dm[AT(k)] * RDGAS * pt[AT(k)] * exp((cp3[AT(k)] - 1.0) * log(maxp));
+    dz[AT(k)] = -dm[AT(k)] * phys::RDGAS * pt[AT(k)] * exp((cp3[AT(k)] - 1.0) * log(maxp));
   }
 #undef AT
 }

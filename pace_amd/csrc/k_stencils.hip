@@ -8,6 +8,7 @@
 // write only inside it, as in GT4Py.  Point kernels over the window, i fastest: HBM-bound streaming passes.
 #include "common.h"
 #include "kernels.h"
+#include "thermo.h"
 
 namespace {
 
@@ -78,7 +79,6 @@ __global__ void k_st_bke(Geo g, Met m, Win w, const real* uc, const real* vc, co
   out[c] = v * dt;
 }
 
-
 // xtp_u_stencil_defn / ytp_v_stencil_defn (tests/savepoint/translate/translate_xtp_u.py:13-23, translate_ytp_v.py): the 1-D
 // advection of a D-grid wind component by the (contravariant wind x dt) on the cell corners, as a stencil of its own
 template <int AXIS, int MORD>
@@ -115,16 +115,7 @@ __global__ void k_st_moist_pt_last_step(Geo g, Win w, const real* qv, const real
 
 // moist_pkz (moist_cv.py:130-172) and the test-side stencil around moist_pt_func (moist_cv.py:48-70;
 // tests/savepoint/translate/translate_moistcvpluspt_2d.py:9-37), nwat = 6: the condensate, the moist heat capacity, cappa, and pkz /
-// the moist potential temperature.  Constants: util/pace/util/constants.py.
-#define ST_RDGAS 287.05
-#define ST_RVGAS 461.50
-#define ST_GRAV 9.80665
-#define ST_CP_AIR 1004.6
-#define ST_CV_AIR (ST_CP_AIR - ST_RDGAS)
-#define ST_RDG (-ST_RDGAS / ST_GRAV)
-#define ST_CV_VAP (3.0 * ST_RVGAS)
-#define ST_C_ICE 1972.0
-#define ST_C_LIQ 4.1855e3
+// the moist potential temperature.
 template <int PT>  // 0: moist_pkz, 1: moist_pt
 __global__ void k_st_moist_cv(Geo g, Win w, const real* qv_, const real* ql_, const real* qr_, const real* qs_, const real* qi_,
                               const real* qg_, real* q_con, real* gz_, real* cvm_, real* pkz, real* pt, real* cappa_, const real* delp,
@@ -135,17 +126,17 @@ __global__ void k_st_moist_cv(Geo g, Win w, const real* qv_, const real* ql_, co
   const double ql = ql_[c] + qr_[c];
   const double qs = qi_[c] + qs_[c] + qg_[c];
   const double gz = ql + qs;
-  const double cvm = (1.0 - (qv + gz)) * ST_CV_AIR + qv * ST_CV_VAP + ql * ST_C_LIQ + qs * ST_C_ICE;
-  const double cappa = ST_RDGAS / (ST_RDGAS + cvm / (1.0 + r_vir * qv));
+  const double cvm = moist_cvm(qv + gz, qv, ql, qs);
+  const double cappa = moist_cappa(cvm, 1.0 + r_vir * qv);
   q_con[c] = gz;
   cappa_[c] = cappa;
   if (PT == 0) {
     gz_[c] = gz;
     cvm_[c] = cvm;
-    pkz[c] = exp(cappa * log(ST_RDG * delp[c] / delz[c] * pt[c]));
+    pkz[c] = moist_pkz(cappa, delp[c], delz[c], pt[c]);
   } else {
     const double p = pt[c];
-    pt[c] = p * exp(cappa / (1.0 - cappa) * log(ST_RDG * delp[c] / delz[c] * p));
+    pt[c] = p * exp(cappa / (1.0 - cappa) * log(phys::RDG * delp[c] / delz[c] * p));
   }
 }
 

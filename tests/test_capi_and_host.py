@@ -20,6 +20,25 @@ def test_header_and_binding_agree():
     assert _declared_symbols() == sorted(_lib.EXPORTED_SYMBOLS)
 
 
+def test_device_constants_are_the_python_constants():
+    """pace_amd/csrc/thermo.h is the one place where the device code defines the physical constants: each has exactly the value
+    of the attribute of the same name in pace_amd/util/constants.py, and no other source repeats a base literal."""
+    from pace_amd.util import constants
+
+    csrc = os.path.join(ROOT, "pace_amd", "csrc")
+    scope = {}
+    for name, expr in re.findall(r"^constexpr double (\w+) = ([^;]+);$", open(os.path.join(csrc, "thermo.h")).read(), re.M):
+        scope[name] = eval(expr, {"__builtins__": {}}, scope)  # plain arithmetic on the names defined before
+        assert scope[name] == getattr(constants, name), name
+    assert {"GRAV", "RDGAS", "RVGAS", "CP_AIR", "CV_AIR", "CV_VAP", "KAPPA", "RDG", "ZVIR", "C_ICE", "C_LIQ", "HLV", "HLF",
+            "TICE", "E00", "LI00", "LAT2"} <= set(scope)
+    literals = ["287.05", "461.5", "9.80665", "1004.6", "1972.0", "4.1855e3", "2.5e6", "3.3358e5", "273.16", "611.21"]
+    for fn in sorted(os.listdir(csrc)):
+        if fn != "thermo.h":
+            text = open(os.path.join(csrc, fn)).read()
+            assert [x for x in literals if x in text] == [], fn
+
+
 def test_library_exports_declared_symbols():
     from pace_amd import _lib
 
