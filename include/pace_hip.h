@@ -456,6 +456,18 @@ int pace_sat_adjust(const pace_geom_t* geom, pace_real_t* const* water, pace_rea
                     const pace_real_t* area, const pace_real_t* hs, const double* tables, const pace_sat_adjust_params_t* params,
                     int kmp, int last_step, int consv_te, void* stream);
 
+/* ---- DryConvectiveAdjustment (fv3core/pace/fv3core/stencils/fv_subgridz.py:740-964, the Fortran fv_subgrid_z): the dry
+ * convective adjustment a driver with fv_sg_adj > 0 applies to the dycore state once per physics step, non-hydrostatic.  One
+ * launch, no host synchronisation: init, the three m_loop sweeps and finalize over origin (3, 3, 0), domain (n, n, k_sponge);
+ * nothing else is written.  tracers: HOST array of the nine device pointers qvapor, qliquid, qrain, qice, qsnow, qgraupel,
+ * qo3mr, qsgs_tke, qcld (inout); pt, ua, va, w (inout); u_dt, v_dt (out: overwritten, not accumulated); delp, delz, pkz (in);
+ * peln, pe (in, interface fields; of pe only element (3, 3, 0) is read, on the device, to choose t_min as :867 does on the
+ * host).  3 <= k_sponge <= nk; nwat == 0 sets xvir = 0, any other value ZVIR; fv_sg_adj and timestep in seconds, both > 0. */
+int pace_dry_convective_adjust(const pace_geom_t* geom, pace_real_t* const* tracers, pace_real_t* pt, pace_real_t* ua,
+                               pace_real_t* va, pace_real_t* w, pace_real_t* u_dt, pace_real_t* v_dt, const pace_real_t* delp,
+                               const pace_real_t* delz, const pace_real_t* pkz, const pace_real_t* peln, const pace_real_t* pe,
+                               int k_sponge, int nwat, double fv_sg_adj, double timestep, void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

@@ -169,6 +169,8 @@ _PROTOS = {
     "pace_sat_adjust_tables": (C.c_int, [c_dp, C.c_void_p]),
     "pace_sat_adjust": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [_P(SatAdjustParams), C.c_int, C.c_int, C.c_int,
                                                                               C.c_void_p]),
+    "pace_dry_convective_adjust": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [C.c_int, C.c_int, C.c_double, C.c_double,
+                                                                                         C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

@@ -570,6 +570,20 @@ int pace_sat_adjust(const pace_geom_t* geom, real* const* water, real* qcld, rea
                            last_step, consv_te, S(stream));
 }
 
+int pace_dry_convective_adjust(const pace_geom_t* geom, real* const* tracers, real* pt, real* ua, real* va, real* w,
+                               real* u_dt, real* v_dt, const real* delp, const real* delz, const real* pkz, const real* peln,
+                               const real* pe, int k_sponge, int nwat, double fv_sg_adj, double timestep, void* stream) {
+  NEED(geom && tracers && pt && ua && va && w && u_dt && v_dt && delp && delz && pkz && peln && pe);
+  for (int n = 0; n < 9; ++n)
+    if (!tracers[n]) return PACE_ERR_ARG;
+  if (k_sponge < 3 || k_sponge > geom->nk || !(fv_sg_adj > 0.0) || !(timestep > 0.0)) return PACE_ERR_ARG;
+  // the externals of m_loop (fv_subgridz.py:794-801)
+  const double t_max = k_sponge < (geom->nk < 24 ? geom->nk : 24) ? 315.0 : 325.0;
+  const double xvir = nwat == 0 ? 0.0 : phys::ZVIR;
+  return launch_dry_convective_adjust(make_geo(geom), tracers, pt, ua, va, w, u_dt, v_dt, delp, delz, pkz, peln, pe, k_sponge,
+                                      xvir, t_max, fv_sg_adj, timestep, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

@@ -266,6 +266,12 @@ int launch_sat_adjust_tables(double* tables, hipStream_t st);
 int launch_sat_adjust(const Geo& g, real* const* water, real* qcld, real* te, real* pt, real* q_con, real* pkz, real* cappa,
                       const real* delp, const real* delz, const real* area, const real* hs, const double* tables,
                       const pace_sat_adjust_params_t& p, int kmp, int last_step, int consv_te, hipStream_t st);
+
+// k_subgridz.hip
+int launch_dry_convective_adjust(const Geo& g, real* const* tracers, real* pt, real* ua, real* va, real* w, real* u_dt,
+                                 real* v_dt, const real* delp, const real* delz, const real* pkz, const real* peln,
+                                 const real* pe, int k_sponge, double xvir, double t_max, double fv_sg_adj, double timestep,
+                                 hipStream_t st);
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);
 int launch_omega_from_w(const Geo& g, const real* delp, const real* delz, const real* w, real* omga, hipStream_t st);

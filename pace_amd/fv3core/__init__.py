@@ -8,3 +8,4 @@ from ._config import (  # noqa: F401
 )
 from .initialization.dycore_state import DycoreState  # noqa: F401,E402
 from .stencils.fv_dynamics import DynamicalCore  # noqa: F401,E402
+from .stencils.fv_subgridz import DryConvectiveAdjustment  # noqa: F401,E402

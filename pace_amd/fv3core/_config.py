@@ -152,6 +152,17 @@ class DynamicalCoreConfig:
     cld_min: float = 0.05
     tau_l2v: float = 300.0
     tau_v2l: float = 90.0
+    # the dry convective adjustment's time scale in seconds (util/pace/util/namelist.py: fv_sg_adj = -1, off)
+    fv_sg_adj: int = -1
+
+    @property
+    def n_sponge(self) -> int:
+        return self.acoustic_dynamics.d_grid_shallow_water.n_sponge
+
+    @property
+    def do_dry_convective_adjustment(self) -> bool:
+        """fv3core/pace/fv3core/_config.py: fv_sg_adj > 0."""
+        return self.fv_sg_adj > 0
 
     @property
     def sat_adjust(self) -> SatAdjustConfig:

@@ -232,3 +232,38 @@ def acoustic_state(metrics, n, nz=79, n_halo=3, dt=3.571):
     s["ws"] = 0.01 * np.sin(2 * lon[:, :, 0])
     s["dt"] = dt
     return s
+
+
+def convective_state(n, nk):
+    """Inputs of DryConvectiveAdjustment at any size (full arrays of (n + 7, n + 7, nk + 1)): a moist state with columns that are unstable in places: temperature with a level-to-level zigzag in a third
+    of the columns, a few hot and cold points, sheared winds, condensates (a few negative)."""
+    shape = (n + 7, n + 7, nk + 1)
+    i, j, k = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), np.arange(shape[2]), indexing="ij")
+    s = {}
+    pe = 300.0 + (1.0e5 - 300.0) * (k / nk) ** 1.6 * (1.0 + 0.02 * np.sin(0.05 * i + 0.03 * j))
+    s["pe"] = pe
+    s["peln"] = np.log(pe)
+    delp = np.empty(shape)
+    delp[:, :, :nk] = pe[:, :, 1:] - pe[:, :, :-1]
+    delp[:, :, nk] = delp[:, :, nk - 1]
+    s["delp"] = delp
+    pmid = pe + 0.5 * delp
+    t = 215.0 + 75.0 * (pmid / 1.0e5) + 10.0 * np.sin(0.04 * i + 0.06 * j)
+    t = t + np.where((i + 2 * j) % 3 == 0, 5.0 * np.where(k % 2 == 0, 1.0, -1.0) * (0.5 + 0.5 * np.sin(0.3 * i + 0.2 * j + 0.5 * k)), 0.0)
+    t = np.where(((i + j) % 11 == 3) & (k % 7 == 2), 330.0, t)
+    t = np.where(((i + j) % 11 == 7) & (k % 7 == 5), 150.0, t)
+    s["pt"] = t
+    s["delz"] = -(287.05 * t * delp / (9.80665 * pmid))
+    s["pkz"] = np.exp((287.05 / 1004.6) * np.log(pmid))
+    s["qvapor"] = 0.015 * (pmid / 1.0e5) ** 3 * (0.6 + 0.4 * np.sin(0.3 * i - 0.2 * j + 0.5 * k))
+    base = 0.5 + 0.5 * np.cos(0.17 * i + 0.23 * j + 0.4 * k)
+    for m, (name, scale) in enumerate((("qliquid", 4e-4), ("qrain", 2e-4), ("qice", 2e-4), ("qsnow", 1e-4), ("qgraupel", 5e-5),
+                                       ("qo3mr", 1e-6), ("qsgs_tke", 1e-2), ("qcld", 0.3))):
+        f = scale * (0.2 + base * (0.6 + 0.4 * np.sin(0.11 * i + 0.13 * j * (m + 1) + k)))
+        s[name] = np.where((((i + 3 * j + 5 * k + m) % 17) == 0) & (m < 5), -0.3 * f, f)
+    s["ua"] = 20.0 * np.sin(0.03 * i + 0.02 * j) + 0.3 * (nk - k) + 3.0 * np.sin(0.7 * k + 0.1 * i)
+    s["va"] = 6.0 * np.cos(0.02 * i - 0.04 * j) + 2.0 * np.cos(0.5 * k + 0.1 * j)
+    s["w"] = 0.4 * np.sin(0.05 * i + 0.07 * j + 0.9 * k)
+    s["u_dt"] = np.full(shape, 0.25)
+    s["v_dt"] = np.full(shape, 0.25)
+    return s

@@ -1,7 +1,7 @@
 """Timing of whole DynamicalCore steps on the GPU box: the six tiles of a cubed sphere resident on ONE device (one host
 thread per tile, halo exchanges through ThreadComm), synthetic balanced state, fp64.
 
-    python tools/dycore_bench.py [--n 192] [--nz 79] [--n-split 4] [--steps 2] [--single] [--sat-adj]
+    python tools/dycore_bench.py [--n 192] [--nz 79] [--n-split 4] [--steps 2] [--single] [--sat-adj] [--sg-adj]
 
 Prints the wall time per step for all six tiles (the device is shared, so per tile = / 6) and the split between the
 acoustic loop, the tracer advection, the remapping and the rest, from synchronising timers.
@@ -52,6 +52,9 @@ def main():
                     help="one tile only, behind a lone-rank LoopbackComm (each halo receives what the tile sent to that neighbour): the "
                          "device time of one tile's step without the thread rendezvous of the six-tile mode")
     ap.add_argument("--sat-adj", action="store_true", help="do_sat_adj = True: the saturation adjustment runs in the remapping")
+    ap.add_argument("--sg-adj", action="store_true",
+                    help="fv_sg_adj = 600: the dry convective adjustment runs on the state after each step, as the reference's driver "
+                         "does once per physics step; its share is reported as dry_conv_adjust")
     args = ap.parse_args()
     if os.environ.get("PACE_BENCH_TRACE"):
         import faulthandler
@@ -60,7 +63,7 @@ def main():
     from helpers import Env, acoustic_config, dycore_condensates
 
     from pace_amd import _lib, synthetic
-    from pace_amd.fv3core import DynamicalCoreConfig
+    from pace_amd.fv3core import DryConvectiveAdjustment, DynamicalCoreConfig
     from pace_amd.fv3core.initialization.dycore_state import DycoreState
     from pace_amd.fv3core.stencils.fv_dynamics import DynamicalCore
     from pace_amd.util import CubedSphereCommunicator, LoopbackComm, constants as c, run_tiles
@@ -88,9 +91,15 @@ def main():
             arrays[name] = np.abs(f)
         state = DycoreState.init_from_numpy_arrays(arrays, env.qf)
         config = DynamicalCoreConfig(npx=n + 1, npy=n + 1, npz=nz, dt_atmos=dt_atmos, k_split=1, n_split=args.n_split,
-                                     acoustic_dynamics=acoustic_config(args.n_split), do_sat_adj=args.sat_adj)
+                                     acoustic_dynamics=acoustic_config(args.n_split), do_sat_adj=args.sat_adj,
+                                     fv_sg_adj=600 if args.sg_adj else -1)
         core = DynamicalCore(cube, env.grid_data, env.stencil_factory, env.qf, env.damping, config, state.phis, state,
                              datetime.timedelta(seconds=dt_atmos))
+        dry_adj = None
+        if config.do_dry_convective_adjustment:  # (driver: stencils/pace/stencils/update_atmos_state.py:174-197)
+            dry_adj = DryConvectiveAdjustment(env.stencil_factory, env.qf, config.nwat, config.fv_sg_adj, min(config.n_sponge, nz),
+                                              config.hydrostatic)
+            u_dt, v_dt = env.q3(), env.q3()
         core.step_dynamics(state)  # warm-up
         torch.cuda.synchronize()
         comm.barrier()
@@ -98,6 +107,9 @@ def main():
         t0 = time.perf_counter()
         for _ in range(args.steps):
             core.step_dynamics(state, timer)
+            if dry_adj is not None:
+                with timer.clock("dry_conv_adjust"):
+                    dry_adj(state, u_dt, v_dt, dt_atmos)
         torch.cuda.synchronize()
         comm.barrier()
         wall = time.perf_counter() - t0

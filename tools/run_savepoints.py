@@ -490,10 +490,32 @@ def spec_sat_adjust3d(g):  # translate_satadjust3d.py:9-87
     return Spec(iv, ["r_vir", "mdt", "fast_mp_consv", "last_step", "akap", "kmp"], ov, 2e-11, run)
 
 
+def spec_fv_subgridz(g):  # translate_fvsubgridz.py:14-199 (no bound of its own: the base class's 1e-14, near-zero tracers ignored)
+    tracers = ("qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel", "qo3mr", "qsgs_tke", "qcld")
+    iv = {k: {} for k in ("delp", "delz", "ua", "va", "w", "pt") + tracers + ("u_dt", "v_dt")}
+    iv["pe"] = {"istart": g.is_ - 1, "jstart": g.js - 1, "kaxis": 1}
+    iv["peln"] = {"istart": g.is_, "jstart": g.js, "kaxis": 1}
+    iv["pkz"] = {"istart": g.is_, "jstart": g.js}
+    ov = {k: {} for k in ("ua", "va", "w", "pt") + tracers + ("u_dt", "v_dt")}
+
+    def run(env, f, p):
+        import types
+
+        from pace_amd.fv3core import DryConvectiveAdjustment
+
+        # the namelist the data were made with: {fv_subgridz: {nwat: 6, fv_sg_adj: 600, n_sponge: 48, hydrostatic: false}}
+        nml = {"nwat": 6, "fv_sg_adj": 600, "n_sponge": 48, "hydrostatic": False, **env.namelist.get("fv_subgridz", {})}
+        op = DryConvectiveAdjustment(env.stencil_factory, env.qf, nml["nwat"], nml["fv_sg_adj"], nml["n_sponge"], nml["hydrostatic"])
+        op(types.SimpleNamespace(**f), f["u_dt"], f["v_dt"], p["dt"])
+        return f
+
+    return Spec(iv, ["dt"], ov, 1e-14, run, ignore_near_zero={k: 1e-18 for k in tracers})
+
+
 SAVEPOINTS = {"D_SW": spec_d_sw, "Riem_Solver3": spec_riem_solver3, "FvTp2d": spec_fvtp2d, "Riem_Solver_C": spec_riem_solver_c,
               "NH_P_Grad": spec_nh_p_grad, "FxAdv": spec_fxadv, "C_SW": spec_c_sw, "UpdateDzC": spec_updatedzc, "UpdateDzD": spec_updatedzd,
               "D2A2C_Vect": spec_d2a2c_vect, "DivergenceDamping": spec_divergence_damping, "DelnFlux": spec_delnflux,
-              "XPPM": spec_xppm, "YPPM": spec_yppm, "SatAdjust3d": spec_sat_adjust3d}
+              "XPPM": spec_xppm, "YPPM": spec_yppm, "SatAdjust3d": spec_sat_adjust3d, "FVSubgridZ": spec_fv_subgridz}
 
 
 # ---- QSInit (translate_qsinit.py:10-52): the saturation tables over the indices 0 ... QS_LENGTH - 1, no grid ------------------------
