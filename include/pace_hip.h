@@ -468,6 +468,33 @@ int pace_dry_convective_adjust(const pace_geom_t* geom, pace_real_t* const* trac
                                const pace_real_t* delz, const pace_real_t* pkz, const pace_real_t* peln, const pace_real_t* pe,
                                int k_sponge, int nwat, double fv_sg_adj, double timestep, void* stream);
 
+/* ---- The end of a dycore-only step: UpdateAtmosphereState / ApplyPhysicsToDycore (stencils/pace/stencils/
+ * update_atmos_state.py:19-37, fv_update_phys.py:30-74, update_dwind_phys.py:446-653; the Fortran fv_update_phys and
+ * update_dwinds_phys).  fp64 arithmetic in the reference's order; no scratch field.
+ *   pace_fill_gfs_delp         fill_gfs_delp(delp, q, q_min) over the FULL domain, halo included: origin (0, 0, 0), domain
+ *                              (n + 6, n + 6, nk + 1); levels 0 .. nk - 1 of q may change, level nk is not touched; nk >= 2.
+ *                              q_min is used in the storage type (float(q_min) in the float32 build)
+ *   pace_phys_thermo_pressure  moist_cv and update_pressure_and_surface_winds in one launch over origin (3, 3, 0), domain
+ *                              (n, n, nk + 1).  water: HOST array of the six device pointers qvapor, qliquid, qrain, qsnow, qice,
+ *                              qgraupel (in).  pt += t_dt * dt * CP_AIR / cvm and t_dt = 0 on nk + 1 levels; pe[k] = pe[k - 1] +
+ *                              delp[k - 1], peln = log(pe), pk = exp(KAPPA * peln) for k >= 1 (level 0 of the three is kept);
+ *                              ps = pe[nk]; u_srf, v_srf = ua, va at level nk - 1 (2-D fields)
+ *   pace_update_dwinds_phys    AGrid2DGridPhysics.__call__: u += dt5 * (ue . es1) on origin (3, 3, 0), domain (n, n + 1, nk),
+ *                              v += dt5 * (ve . ew2) on (n + 1, n, nk), with the four tile-edge blends; then u_dt = v_dt = 0
+ *                              on origin (2, 2, 0), domain (n + 2, n + 2, nk) (a second launch on the same stream).  The
+ *                              one-point halo of u_dt, v_dt must be up to date.  vlon, vlat, es1, ew2: HOST arrays of the three
+ *                              device pointers of their Cartesian components (2-D fields); edge_vect_*: 1-D device arrays of
+ *                              n + 7 entries indexed like the fields.  n even, n >= 4. */
+int pace_fill_gfs_delp(const pace_geom_t* geom, const pace_real_t* delp, pace_real_t* q, double q_min, void* stream);
+int pace_phys_thermo_pressure(const pace_geom_t* geom, const pace_real_t* const* water, pace_real_t* pt, pace_real_t* t_dt,
+                              pace_real_t* pe, const pace_real_t* delp, pace_real_t* peln, pace_real_t* pk, const pace_real_t* ua,
+                              const pace_real_t* va, pace_real_t* ps, pace_real_t* u_srf, pace_real_t* v_srf, double dt,
+                              void* stream);
+int pace_update_dwinds_phys(const pace_geom_t* geom, pace_real_t* u, pace_real_t* v, pace_real_t* u_dt, pace_real_t* v_dt,
+                            const pace_real_t* const* vlon, const pace_real_t* const* vlat, const pace_real_t* const* es1,
+                            const pace_real_t* const* ew2, const pace_real_t* edge_vect_w, const pace_real_t* edge_vect_e,
+                            const pace_real_t* edge_vect_s, const pace_real_t* edge_vect_n, double dt5, void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

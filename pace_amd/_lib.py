@@ -171,6 +171,9 @@ _PROTOS = {
                                                                               C.c_void_p]),
     "pace_dry_convective_adjust": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [C.c_int, C.c_int, C.c_double, C.c_double,
                                                                                          C.c_void_p]),
+    "pace_fill_gfs_delp": (C.c_int, [_P(Geom), c_dp, c_dp, C.c_double, C.c_void_p]),
+    "pace_phys_thermo_pressure": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [C.c_double, C.c_void_p]),
+    "pace_update_dwinds_phys": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [_P(C.c_void_p)] * 4 + [c_dp] * 4 + [C.c_double, C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

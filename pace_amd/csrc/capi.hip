@@ -584,6 +584,35 @@ int pace_dry_convective_adjust(const pace_geom_t* geom, real* const* tracers, re
                                       xvir, t_max, fv_sg_adj, timestep, S(stream));
 }
 
+int pace_fill_gfs_delp(const pace_geom_t* geom, const real* delp, real* q, double q_min, void* stream) {
+  NEED(geom && delp && q);
+  if (geom->nk < 2) return PACE_ERR_ARG;
+  return launch_fill_gfs_delp(make_geo(geom), delp, q, q_min, S(stream));
+}
+
+int pace_phys_thermo_pressure(const pace_geom_t* geom, const real* const* water, real* pt, real* t_dt, real* pe,
+                              const real* delp, real* peln, real* pk, const real* ua, const real* va, real* ps, real* u_srf,
+                              real* v_srf, double dt, void* stream) {
+  NEED(geom && water && pt && t_dt && pe && delp && peln && pk && ua && va && ps && u_srf && v_srf);
+  for (int n = 0; n < 6; ++n)
+    if (!water[n]) return PACE_ERR_ARG;
+  if (geom->nk < 2) return PACE_ERR_ARG;
+  return launch_phys_thermo_pressure(make_geo(geom), water, pt, t_dt, pe, delp, peln, pk, ua, va, ps, u_srf, v_srf, dt,
+                                     S(stream));
+}
+
+int pace_update_dwinds_phys(const pace_geom_t* geom, real* u, real* v, real* u_dt, real* v_dt, const real* const* vlon,
+                            const real* const* vlat, const real* const* es1, const real* const* ew2, const real* edge_vect_w,
+                            const real* edge_vect_e, const real* edge_vect_s, const real* edge_vect_n, double dt5,
+                            void* stream) {
+  NEED(geom && u && v && u_dt && v_dt && vlon && vlat && es1 && ew2 && edge_vect_w && edge_vect_e && edge_vect_s && edge_vect_n);
+  for (int m = 0; m < 3; ++m)
+    if (!vlon[m] || !vlat[m] || !es1[m] || !ew2[m]) return PACE_ERR_ARG;
+  if (geom->n < 4 || geom->n % 2) return PACE_ERR_ARG;  // the edge vectors need a midpoint (geometry.py:726-729)
+  return launch_update_dwinds_phys(make_geo(geom), u, v, u_dt, v_dt, vlon, vlat, es1, ew2, edge_vect_w, edge_vect_e,
+                                   edge_vect_s, edge_vect_n, dt5, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

@@ -272,6 +272,15 @@ int launch_dry_convective_adjust(const Geo& g, real* const* tracers, real* pt, r
                                  real* v_dt, const real* delp, const real* delz, const real* pkz, const real* peln,
                                  const real* pe, int k_sponge, double xvir, double t_max, double fv_sg_adj, double timestep,
                                  hipStream_t st);
+// k_updphys.hip
+int launch_fill_gfs_delp(const Geo& g, const real* delp, real* q, double q_min, hipStream_t st);
+int launch_phys_thermo_pressure(const Geo& g, const real* const* water, real* pt, real* t_dt, real* pe, const real* delp,
+                                real* peln, real* pk, const real* ua, const real* va, real* ps, real* u_srf, real* v_srf,
+                                double dt, hipStream_t st);
+int launch_update_dwinds_phys(const Geo& g, real* u, real* v, real* u_dt, real* v_dt, const real* const* vlon,
+                              const real* const* vlat, const real* const* es1, const real* const* ew2, const real* edge_vect_w,
+                              const real* edge_vect_e, const real* edge_vect_s, const real* edge_vect_n, double dt5,
+                              hipStream_t st);
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);
 int launch_omega_from_w(const Geo& g, const real* delp, const real* delz, const real* w, real* omga, hipStream_t st);

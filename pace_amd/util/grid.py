@@ -120,6 +120,70 @@ class DampingCoefficients:
             setattr(self, n, getattr(grid_data, n))
 
 
+_DRIVER_2D = ("vlon", "vlat", "es1", "ew2")
+_DRIVER_1D = ("edge_vect_w", "edge_vect_e", "edge_vect_s", "edge_vect_n")
+
+
+class DriverGridData:
+    """helper.py:639-733: the terms ApplyPhysicsToDycore applies tendencies with.  vlon1..3, vlat1..3 (unit vectors towards
+    east and north at cell centres), es1_1..3, ew2_1..3 (grid-local unit vectors at the south / west faces) are 2-D device
+    Quantities; edge_vect_w, edge_vect_e (indexed by j) and edge_vect_s, edge_vect_n (indexed by i) are 1-D device tensors of
+    nx + 7 entries, like GridData.edge_w.
+
+    One deliberate departure: the reference's new_from_metric_terms passes `vlat=metric_terms.vlon` (helper.py:683); this one
+    passes the real vlat.  The operators use whatever grid_info they are handed."""
+
+    FIELDS = tuple(f"{n}{m}" for n in ("vlon", "vlat") for m in (1, 2, 3)) + _DRIVER_1D + tuple(
+        f"{n}_{m}" for n in ("es1", "ew2") for m in (1, 2, 3))
+
+    def __init__(self, **fields):
+        if sorted(fields) != sorted(self.FIELDS):
+            raise TypeError(f"DriverGridData takes exactly the fields {self.FIELDS}")
+        for name, value in fields.items():
+            setattr(self, name, value)
+
+    @classmethod
+    def new_from_metric_terms(cls, metric_terms) -> "DriverGridData":
+        t = metric_terms.terms
+        if "edge_vect_w" not in t:
+            raise ValueError("the edge vectors of DriverGridData need a tile with an even number of cells along an edge "
+                             "(util/pace/util/grid/geometry.py:726-729 refuses an odd one)")
+        return cls.new_from_grid_variables(vlon=t["vlon"], vlat=t["vlat"], edge_vect_n=t["edge_vect_n"], edge_vect_s=t["edge_vect_s"],
+                                           edge_vect_e=t["edge_vect_e"], edge_vect_w=t["edge_vect_w"], es1=t["es1"], ew2=t["ew2"],
+                                           quantity_factory=metric_terms.quantity_factory)
+
+    @classmethod
+    def new_from_grid_variables(cls, vlon, vlat, edge_vect_n, edge_vect_s, edge_vect_e, edge_vect_w, es1, ew2,
+                                quantity_factory=None) -> "DriverGridData":
+        """The reference's arguments as host arrays -- (nx + 7, ny + 7, 3) for the four vector fields, nx + 7 entries (or a 2-D
+        field constant along i, as the reference's edge_vect_w / _e are) for the edge vectors -- and the quantity factory that
+        allocates the device fields."""
+        import torch
+
+        if quantity_factory is None:
+            raise ValueError("DriverGridData needs the field layout: a quantity factory")
+        qf = quantity_factory
+        given = dict(vlon=vlon, vlat=vlat, es1=es1, ew2=ew2, edge_vect_w=edge_vect_w, edge_vect_e=edge_vect_e,
+                     edge_vect_s=edge_vect_s, edge_vect_n=edge_vect_n)
+        size = qf.sizer.nx + 1 + 2 * qf.sizer.n_halo
+        fields = {}
+        for name in _DRIVER_2D:
+            a = np.asarray(given[name], dtype=float)
+            if a.shape != (size, size, 3):
+                raise ValueError(f"{name} of shape {a.shape}: expected {(size, size, 3)}")
+            for m in range(3):
+                q = qf.zeros([c.X_DIM, c.Y_DIM], units="")
+                q.set(a[:, :, m])
+                fields[f"{name}{m + 1}" if name in ("vlon", "vlat") else f"{name}_{m + 1}"] = q
+        for name in _DRIVER_1D:
+            a = np.asarray(given[name], dtype=float)
+            a = a[0, :] if a.ndim == 2 else a
+            if a.shape != (size,):
+                raise ValueError(f"{name} of shape {a.shape}: expected {(size,)}")
+            fields[name] = torch.as_tensor(np.ascontiguousarray(a), dtype=qf.real, device=qf.device)
+        return cls(**fields)
+
+
 def geom_struct(quantity_factory) -> _lib.Geom:
     s = quantity_factory.sizer
     g = _lib.Geom(s.nx, s.nz, quantity_factory.row_stride, 0, quantity_factory.level_stride)

@@ -347,6 +347,9 @@ def _angles(g, n):
     z21, z22 = (ec2h * vlon).sum(axis=-1), (ec2h * vlat).sum(axis=-1)
     g["a11"], g["a12"] = pad(0.5 * z22 / sin_sg5), pad(-0.5 * z12 / sin_sg5)
     g["a21"], g["a22"] = pad(-0.5 * z21 / sin_sg5), pad(0.5 * z11 / sin_sg5)
+    # the same two unit vectors are what ApplyPhysicsToDycore projects the A-grid wind tendencies on (generation.py:2248-2259)
+    g["vlon"], g["vlat"] = np.zeros((size, size, 3)), np.zeros((size, size, 3))
+    g["vlon"][:-1, :-1], g["vlat"][:-1, :-1] = vlon, vlat
 
     # ---- unit vectors the initial state projects the zonal wind on (geometry.py:60-150,294-345): along x / y at the
     #      compute-domain corner points (ee1, ee2; one-sided on the tile edges), along the south faces (es1) and the west
@@ -383,3 +386,29 @@ def _angles(g, n):
     es_[ci] = edge_weights(LO[ci, O], LT[ci, O], LA[cc, O - 1], TA[cc, O - 1], LA[cc, O], TA[cc, O])
     en[ci] = edge_weights(LO[ci, e], LT[ci, e], LA[cc, e], TA[cc, e], LA[cc, e - 1], TA[cc, e - 1])
     g["edge_w"], g["edge_e"], g["edge_s"], g["edge_n"] = ew, ee_, es_, en
+
+    # ---- A -> C vector interpolation weights on the four tile edges (efactor_a2c_v, geometry.py:703-871), which the wind
+    #      update of ApplyPhysicsToDycore blends with: for the faces j = 2 .. N + 3 of the west edge, d1 / (d1 + d2) with d1 the
+    #      arc from the face's midpoint to the midpoint (across the edge) of its own pair of cell centres and d2 the arc to the
+    #      next pair's -- the pair at j + 1 up to the tile's midpoint, at j - 1 beyond it.  The other edges through mirrored and
+    #      transposed views.  1e8 outside [2:-2]; the two entries next to each corner copy their inner neighbour.
+    def west_edge_vect(lo, lt, la, ta):
+        py = to_lonlat(unit(to_xyz(la[O - 1, 1:-1], ta[O - 1, 1:-1]) + to_xyz(la[O, 1:-1], ta[O, 1:-1])))
+        p2 = to_lonlat(unit(to_xyz(lo[O, 1:-2], lt[O, 1:-2]) + to_xyz(lo[O, 2:-1], lt[O, 2:-1])))
+        m = n // 2
+        d1, d2 = np.zeros(n + 2), np.zeros(n + 2)
+        d1[:m + 1] = R * arc(py[0][1:m + 2], py[1][1:m + 2], p2[0][1:m + 2], p2[1][1:m + 2])
+        d2[:m + 1] = R * arc(py[0][2:m + 3], py[1][2:m + 3], p2[0][1:m + 2], p2[1][1:m + 2])
+        d1[m + 1:] = R * arc(py[0][m + 2:-1], py[1][m + 2:-1], p2[0][m + 2:-1], p2[1][m + 2:-1])
+        d2[m + 1:] = R * arc(py[0][m + 1:-2], py[1][m + 1:-2], p2[0][m + 2:-1], p2[1][m + 2:-1])
+        out = np.full(size - 1, BIG)
+        out[2:-2] = d1 / (d2 + d1)
+        out[O - 1], out[-O] = out[O], out[-O - 1]
+        return np.append(out, 0.0)  # (the reference's storage has one more entry than the values it sets)
+
+    if n % 2 == 0:  # (the reference refuses an odd tile size here, geometry.py:728)
+        A, B = LA[:-1, :-1], TA[:-1, :-1]
+        g["edge_vect_w"] = west_edge_vect(LO, LT, A, B)
+        g["edge_vect_e"] = west_edge_vect(LO[::-1], LT[::-1], A[::-1], B[::-1])
+        g["edge_vect_s"] = west_edge_vect(LO.T, LT.T, A.T, B.T)
+        g["edge_vect_n"] = west_edge_vect(LO[:, ::-1].T, LT[:, ::-1].T, A[:, ::-1].T, B[:, ::-1].T)

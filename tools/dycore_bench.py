@@ -53,8 +53,9 @@ def main():
                          "device time of one tile's step without the thread rendezvous of the six-tile mode")
     ap.add_argument("--sat-adj", action="store_true", help="do_sat_adj = True: the saturation adjustment runs in the remapping")
     ap.add_argument("--sg-adj", action="store_true",
-                    help="fv_sg_adj = 600: the dry convective adjustment runs on the state after each step, as the reference's driver "
-                         "does once per physics step; its share is reported as dry_conv_adjust")
+                    help="fv_sg_adj = 600: the reference driver's end of a dycore-only step runs after each step -- DycoreToPhysics (the "
+                         "dry convective adjustment, reported as dry_conv_adjust), then UpdateAtmosphereState (fill_gfs_delp and "
+                         "ApplyPhysicsToDycore with its halo updates, reported as update_atmos_state)")
     args = ap.parse_args()
     if os.environ.get("PACE_BENCH_TRACE"):
         import faulthandler
@@ -63,7 +64,7 @@ def main():
     from helpers import Env, acoustic_config, dycore_condensates
 
     from pace_amd import _lib, synthetic
-    from pace_amd.fv3core import DryConvectiveAdjustment, DynamicalCoreConfig
+    from pace_amd.fv3core import DynamicalCoreConfig
     from pace_amd.fv3core.initialization.dycore_state import DycoreState
     from pace_amd.fv3core.stencils.fv_dynamics import DynamicalCore
     from pace_amd.util import CubedSphereCommunicator, LoopbackComm, constants as c, run_tiles
@@ -75,6 +76,11 @@ def main():
     dt_atmos = float(s["dt"]) * args.n_split
     results = {}
     lock = threading.Lock()
+    driver_terms = None
+    if args.sg_adj:  # the driver grid terms of the six tiles, generated once for all tile threads
+        from pace_amd.util import gridgen
+
+        driver_terms = gridgen.tiles(n, nz)
 
     def program(comm):
         tile = comm.Get_rank()
@@ -95,11 +101,21 @@ def main():
                                      fv_sg_adj=600 if args.sg_adj else -1)
         core = DynamicalCore(cube, env.grid_data, env.stencil_factory, env.qf, env.damping, config, state.phis, state,
                              datetime.timedelta(seconds=dt_atmos))
-        dry_adj = None
-        if config.do_dry_convective_adjustment:  # (driver: stencils/pace/stencils/update_atmos_state.py:174-197)
-            dry_adj = DryConvectiveAdjustment(env.stencil_factory, env.qf, config.nwat, config.fv_sg_adj, min(config.n_sponge, nz),
-                                              config.hydrostatic)
-            u_dt, v_dt = env.q3(), env.q3()
+        to_physics = None
+        if config.do_dry_convective_adjustment:  # (driver: driver/pace/driver/driver.py:618-640)
+            import types
+
+            from pace_amd.stencils import DycoreToPhysics, UpdateAtmosphereState
+            from pace_amd.util.grid import DriverGridData
+
+            terms = driver_terms[tile]
+            info = DriverGridData.new_from_grid_variables(**{k: terms[k] for k in ("vlon", "vlat", "es1", "ew2", "edge_vect_w", "edge_vect_e",
+                                                                                    "edge_vect_s", "edge_vect_n")}, quantity_factory=env.qf)
+            tend = types.SimpleNamespace(u_dt=env.q3(), v_dt=env.q3(), pt_dt=env.q3())
+            adj = types.SimpleNamespace(nwat=config.nwat, fv_sg_adj=config.fv_sg_adj, n_sponge=min(config.n_sponge, nz),
+                                        hydrostatic=config.hydrostatic, layout=config.layout)
+            to_physics = DycoreToPhysics(env.stencil_factory, env.qf, adj, True, True)
+            update = UpdateAtmosphereState(env.stencil_factory, env.grid_data, config, cube, info, state, env.qf, True, True, tend)
         core.step_dynamics(state)  # warm-up
         torch.cuda.synchronize()
         comm.barrier()
@@ -107,9 +123,11 @@ def main():
         t0 = time.perf_counter()
         for _ in range(args.steps):
             core.step_dynamics(state, timer)
-            if dry_adj is not None:
+            if to_physics is not None:
                 with timer.clock("dry_conv_adjust"):
-                    dry_adj(state, u_dt, v_dt, dt_atmos)
+                    to_physics(state, None, tend, dt_atmos)
+                with timer.clock("update_atmos_state"):
+                    update(state, None, tend.u_dt, tend.v_dt, tend.pt_dt, dt_atmos)
         torch.cuda.synchronize()
         comm.barrier()
         wall = time.perf_counter() - t0

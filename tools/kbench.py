@@ -1,6 +1,6 @@
 """Per-entry-point timing on the GPU box (HIP events on the launch stream), C192 x 79 by default.
 
-    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust]
+    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust,apply_physics]
 """
 import argparse
 import os
@@ -126,7 +126,50 @@ def main():
         for k in cv:
             cv[k].set(cv_h[k])
 
+    apply_physics = ("fill_gfs_delp", "phys_thermo_pressure", "update_dwinds_phys")
+    only = [x for x in args.only.split(",") if x]
+    if "apply_physics" in only:
+        only += list(apply_physics)
+    ap_cases = {}
+
+    def build_apply_physics():
+        # The end-of-step update (k_updphys.hip), each kernel alone on the convective state's fields with pace_amd's own driver grid
+        # terms: fill_gfs_delp (delp, q read, q written where it changes), the column kernel (14 field passes) and the wind kernel
+        # with its zeroing launch (8).  `--only apply_physics` selects the three.
+        from pace_amd.fv3core.stencils.fillz import pointer_table
+        from pace_amd.util import gridgen
+        from pace_amd.util.grid import DriverGridData, geom_struct
+
+        terms = gridgen.tiles(n, nz)[0]
+        info = DriverGridData.new_from_grid_variables(**{k: terms[k] for k in ("vlon", "vlat", "es1", "ew2", "edge_vect_w", "edge_vect_e",
+                                                                                "edge_vect_s", "edge_vect_n")}, quantity_factory=env.qf)
+        geom = geom_struct(env.qf)
+        ap_t_dt, ap_pk, ap_u, ap_v = env.q3(), env.q3(), env.q3(), env.q3()
+        ap_2d = [env.q2(), env.q2(), env.q2()]
+        ap_vec = [pointer_table([getattr(info, f"{nm}{m}") for m in (1, 2, 3)]) for nm in ("vlon", "vlat", "es1_", "ew2_")]
+        ap_edges = [C.c_void_p(e.data_ptr()) for e in (info.edge_vect_w, info.edge_vect_e, info.edge_vect_s, info.edge_vect_n)]
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        water = pointer_table([cv[k] for k in ("qvapor", "qliquid", "qrain", "qsnow", "qice", "qgraupel")])
+
+        def fill_gfs_delp():
+            lib.call("pace_fill_gfs_delp", C.byref(geom), dptr(cv["delp"]), dptr(cv["qvapor"]), 1.0e-9, stream)
+
+        def phys_thermo_pressure():
+            lib.call("pace_phys_thermo_pressure", C.byref(geom), water, dptr(cv["pt"]), dptr(ap_t_dt), dptr(cv["pe"]), dptr(cv["delp"]),
+                     dptr(cv["peln"]), dptr(ap_pk), dptr(cv["ua"]), dptr(cv["va"]), *[dptr(x) for x in ap_2d], 225.0, stream)
+
+        def update_dwinds_phys():
+            lib.call("pace_update_dwinds_phys", C.byref(geom), dptr(ap_u), dptr(ap_v), dptr(cv["u_dt"]), dptr(cv["v_dt"]), *ap_vec, *ap_edges,
+                     112.5, stream)
+        ap_cases.update(fill_gfs_delp=fill_gfs_delp, phys_thermo_pressure=phys_thermo_pressure, update_dwinds_phys=update_dwinds_phys,
+                        grid_info=info)  # (the pointer tables hold addresses of grid_info's fields)
+
+    if not only or set(only) & set(apply_physics):  # (the driver grid terms take a grid generation: only when they are timed)
+        build_apply_physics()
     cases = {
+        "fill_gfs_delp": (ap_cases.get("fill_gfs_delp"), 3),
+        "phys_thermo_pressure": (ap_cases.get("phys_thermo_pressure"), 14),
+        "update_dwinds_phys": (ap_cases.get("update_dwinds_phys"), 8),
         "dry_convective_adjust": (lambda: dry_adj(cv_state, cv["u_dt"], cv["v_dt"], 225.0), 32.0 * ks / nz),
         "sat_adjust": (sat_adjust, 19),
         "fxadv": (lambda: prep(f["uc"], f["vc"], f["crx"], f["cry"], f["xfx"], f["yfx"], ut, vt, s["dt"]), 8),
@@ -140,7 +183,6 @@ def main():
         "dsw_winds": (lambda: dsw_phase(12), 20),
         "d_sw": (lambda: dsw(*[f[k] for k in DSW_ARGS], s["dt"]), 32),
     }
-    only = [x for x in args.only.split(",") if x]
     print(f"{'case':22s} {'us':>10s} {'alg GB/s':>10s} {'%8TB/s':>8s}")
     for name, (fn, nfields) in cases.items():
         if only and name not in only:
@@ -158,7 +200,7 @@ def main():
             if name == "sat_adjust":
                 restore_sat_adjust()
                 torch.cuda.synchronize()
-            if name == "dry_convective_adjust":
+            if name == "dry_convective_adjust" or name in apply_physics:
                 restore_dry_adj()
                 torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

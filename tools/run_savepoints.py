@@ -14,6 +14,10 @@ For every savepoint name it knows and finds in <dir>, and every (savepoint, rank
     arrays in the reference's metric (util/pace/util/testing/comparison.py:6-68) against the class's max_error / the overrides
     of fv3core/tests/savepoint/translate/overrides/standard.yaml.
 
+The end-of-step savepoints of the physics test data (physics/tests/savepoint/translate): `UpdateDWindsPhys` runs through the same
+table; `FVUpdatePhys` (a ParallelTranslate: six ranks with their halo updates, like `DynCore`) and `FillGFS` (the physics' column
+arrays, levels from the surface up) have runners of their own.  Their grid terms: `--metrics` may hold `{rank}`.
+
 Files: NetCDF-4 through h5py / netCDF4 / xarray (whichever imports), NetCDF-3 classic through scipy.io (`nccopy -k classic`
 converts), or `.npz` pairs with the same variable names and the same leading (savepoint, rank) axes (what
 tests/test_savepoint_runner.py writes).  Grid: the metric terms of the rank's tile from pace_amd's own generator (checked against
@@ -512,7 +516,42 @@ def spec_fv_subgridz(g):  # translate_fvsubgridz.py:14-199 (no bound of its own:
     return Spec(iv, ["dt"], ov, 1e-14, run, ignore_near_zero={k: 1e-18 for k in tracers})
 
 
-SAVEPOINTS = {"D_SW": spec_d_sw, "Riem_Solver3": spec_riem_solver3, "FvTp2d": spec_fvtp2d, "Riem_Solver_C": spec_riem_solver_c,
+def driver_grid_info(env):
+    """DriverGridData of the rank's tile from the metric terms the environment was built with (pace_amd's own, or --metrics,
+    which then has to hold vlon, vlat, es1, ew2 and the four edge_vect_* as well)."""
+    from pace_amd.util.grid import DriverGridData
+
+    m = env.metric_terms
+    return DriverGridData.new_from_grid_variables(**{k: m[k] for k in ("vlon", "vlat", "es1", "ew2", "edge_vect_w", "edge_vect_e",
+                                                                        "edge_vect_s", "edge_vect_n")}, quantity_factory=env.qf)
+
+
+def physics_namelist(env_or_nl, n):
+    """The namelist entries the end-of-step operators read: {update_phys: {dt_atmos: 225, c2l_ord: 4}} in --namelist."""
+    import types
+
+    nl = env_or_nl if isinstance(env_or_nl, dict) else env_or_nl.namelist
+    o = {"dt_atmos": 225.0, "c2l_ord": 4, **nl.get("update_phys", {})}
+    return types.SimpleNamespace(npx=n + 1, npy=n + 1, layout=(1, 1), dt_atmos=float(o["dt_atmos"]), c2l_ord=int(o["c2l_ord"]))
+
+
+def spec_update_dwinds_phys(g):  # stencils/pace/stencils/testing/translate_update_dwind_phys.py:9-44 ("dwind": placed at 0, 0, 0)
+    at0 = {"istart": 0, "jstart": 0}
+    iv = {k: dict(at0) for k in ("u", "u_dt", "v", "v_dt")}
+    ov = {"u": g._with(g.y3d_domain_dict(), kend=g.npz - 1), "v": g._with(g.x3d_domain_dict(), kend=g.npz - 1)}
+
+    def run(env, f, p):
+        from pace_amd.stencils import AGrid2DGridPhysics
+        from pace_amd.util import TilePartitioner
+
+        op = AGrid2DGridPhysics(env.stencil_factory, env.qf, TilePartitioner((1, 1)), 0, physics_namelist(env, g.n), driver_grid_info(env))
+        op(f["u"], f["v"], f["u_dt"], f["v_dt"])
+        return f
+
+    return Spec(iv, [], ov, 1e-14, run)
+
+
+SAVEPOINTS = {"UpdateDWindsPhys": spec_update_dwinds_phys, "D_SW": spec_d_sw, "Riem_Solver3": spec_riem_solver3, "FvTp2d": spec_fvtp2d, "Riem_Solver_C": spec_riem_solver_c,
               "NH_P_Grad": spec_nh_p_grad, "FxAdv": spec_fxadv, "C_SW": spec_c_sw, "UpdateDzC": spec_updatedzc, "UpdateDzD": spec_updatedzd,
               "D2A2C_Vect": spec_d2a2c_vect, "DivergenceDamping": spec_divergence_damping, "DelnFlux": spec_delnflux,
               "XPPM": spec_xppm, "YPPM": spec_yppm, "SatAdjust3d": spec_sat_adjust3d, "FVSubgridZ": spec_fv_subgridz}
@@ -637,6 +676,106 @@ def run_dyncore(pair, args, lib):
     return all(e <= bound for e in worst.values()), bound, worst
 
 
+# ---- FillGFS (physics/tests/savepoint/translate/translate_fillgfs.py:9-47): physics-side serialisation -------------------------
+def run_fillgfs(pair, args, lib):
+    """Returns (ok, bound, worst) like run_one.  IPD_prsi (columns, npz + 1) and IPD_gq0 (columns, npz, tracers) are the
+    physics' arrays: cn * cn columns in C order, levels from the surface up (translate_physics.py:52-74); delp is the
+    difference of the interface pressures, zero in the halo; IPD_qvapor: the compute domain's columns, npz levels, reversed
+    again (:127-170).  No grid term is read."""
+    import ctypes
+
+    import torch
+
+    from pace_amd.tile import Env
+    from pace_amd.util.grid import geom_struct
+
+    ins, outs = pair
+    prsi, gq0, ref_q = np.asarray(ins["IPD_prsi"]), np.asarray(ins["IPD_gq0"]), np.asarray(outs["IPD_qvapor"])
+    worst = {}
+    for sp in range(prsi.shape[0]):
+        for rank in range(prsi.shape[1]):
+            cn = int(np.sqrt(prsi[sp, rank].shape[0]))
+            npz = prsi[sp, rank].shape[1] - 1
+            pe = np.reshape(prsi[sp, rank], (cn, cn, npz + 1))[:, :, ::-1]
+            q = np.reshape(gq0[sp, rank], (cn, cn, npz, -1))[:, :, ::-1, 0]
+            grid = SGrid(cn, npz)
+            z = np.zeros((cn + 7, cn + 7))
+            env = Env(lib, args.device, {"area": z, "da_min": 1.0, "da_min_c": 1.0, "del6_u": z, "del6_v": z, "divg_u": z, "divg_v": z}, cn, npz)
+            full_pe = place(pe, {}, grid)
+            delp = np.zeros_like(full_pe)
+            delp[:, :, :-1] = full_pe[:, :, 1:] - full_pe[:, :, :-1]
+            fq, fd = env.q3(place(q, {}, grid)), env.q3(delp)
+            stream = None if args.device == "cpu" else ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            lib.call("pace_fill_gfs_delp", ctypes.byref(geom_struct(env.qf)), fd.ptr, fq.ptr, 1.0e-9, stream)
+            if args.device != "cpu":
+                torch.cuda.synchronize()
+            got = np.reshape(fq.numpy()[grid.is_:grid.ie + 1, grid.js:grid.je + 1, :], (cn * cn, npz + 1))[:, ::-1][:, 1:]
+            worst["IPD_qvapor"] = max(worst.get("IPD_qvapor", 0.0), compare(np.squeeze(ref_q[sp, rank]), got))
+    bound = 1e-14
+    return all(e <= bound for e in worst.values()), bound, worst
+
+
+# ---- FVUpdatePhys (physics/tests/savepoint/translate/translate_fv_update_phys.py:52-236): six ranks, halo updates included -------
+def fv_update_phys_vars(g):
+    col = {"istart": g.is_, "jstart": g.js}
+    iv = {k: {} for k in ("u_dt", "v_dt", "t_dt", "ua", "va", "qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel", "delp", "pt", "ps")}
+    iv.update({"u": g.y3d_domain_dict(), "v": g.x3d_domain_dict(), "peln": dict(col, kaxis=1),
+               "pe": {"istart": g.is_ - 1, "jstart": g.js - 1, "kaxis": 1}, "pk": dict(col)})
+    last = {"kend": g.npz - 1}
+    ov = {k: dict(last) for k in ("qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel", "pt", "ua", "va")}
+    ov.update({"u": g._with(g.y3d_domain_dict(), **last), "v": g._with(g.x3d_domain_dict(), **last)})
+    return iv, ov
+
+
+def run_fv_update_phys(pair, args, lib):
+    """Returns (ok, bound, worst) like run_one.  Metrics: `--metrics` may hold `{rank}`; dt_atmos, c2l_ord: physics_namelist."""
+    import types
+
+    from pace_amd.stencils import ApplyPhysicsToDycore
+    from pace_amd.tile import Env
+    from pace_amd.util import CubedSphereCommunicator, run_tiles
+
+    ins, outs = pair
+    some = next(v for v in ins.values() if np.asarray(v).ndim >= 5)
+    n_sp, n_rank = some.shape[0], some.shape[1]
+    if n_rank != 6:
+        raise SystemExit(f"FVUpdatePhys: {n_rank} ranks in the data; this runner drives one tile per rank (6)")
+    shape = np.squeeze(np.asarray(ins["delp"])[0, 0]).shape
+    n, npz = shape[0] - 2 * HALO, shape[2]
+    grid = SGrid(n, npz)
+    iv, ov = fv_update_phys_vars(grid)
+    nml = physics_namelist(getattr(args, "namelist", None) or {}, n)
+    worst = {}
+    for sp in range(n_sp):
+        def program(comm, sp=sp):
+            rank = comm.Get_rank()
+            mpath = args.metrics.format(rank=rank) if args.metrics else None
+            terms = metrics_for(n, npz, rank, mpath)
+            env = Env(lib, args.device, terms, n, npz)
+            env.metric_terms = terms
+            cube = CubedSphereCommunicator(comm, device=args.device, lib=lib)
+            f = {}
+            for var, info in iv.items():
+                st = place(np.asarray(ins[var])[sp, rank], info, grid)
+                f[var] = env.q2(st) if st.ndim == 2 else env.q3(st)
+            state = types.SimpleNamespace(**{k: v for k, v in f.items() if k not in ("u_dt", "v_dt", "t_dt")})
+            op = ApplyPhysicsToDycore(env.stencil_factory, env.qf, env.grid_data, nml, cube, driver_grid_info(env), state, f["u_dt"], f["v_dt"])
+            op(state, f["u_dt"], f["v_dt"], f["t_dt"], dt=nml.dt_atmos)
+            if args.device != "cpu":
+                import torch
+
+                torch.cuda.synchronize()
+            return {k: f[k].numpy() for k in ov}
+
+        for rank, res in enumerate(run_tiles(6, program)):
+            for var, info in ov.items():
+                if var in outs:
+                    ref = np.squeeze(np.asarray(outs[var])[sp, rank])
+                    worst[var] = max(worst.get(var, 0.0), compare(ref, slice_out(res[var], info, grid)))
+    bound = 1e-14  # (the class sets none: the base class's default)
+    return all(e <= bound for e in worst.values()), bound, worst
+
+
 def metrics_for(n, npz, tile, path=None):
     if path:
         return dict(np.load(path))
@@ -664,7 +803,11 @@ def run_one(name, pair, args, lib):
             npz = min(s_[2] for s_ in wide if s_[0] >= n + 2 * HALO)
             grid = SGrid(n, npz)
             spec = SAVEPOINTS[name](grid)
-            env = Env(lib, args.device, metrics_for(n, npz, rank % 6 if args.rank_tile else 0, args.metrics), n, npz)
+            mpath = args.metrics.format(rank=rank) if args.metrics else None  # (`--metrics` may hold `{rank}`)
+            terms = metrics_for(n, npz, rank % 6 if args.rank_tile else 0, mpath)
+            env = Env(lib, args.device, terms, n, npz)
+            env.metric_terms = terms
+
             env.namelist = getattr(args, "namelist", None) or {}
             fields, params = {}, {}
             for pname in spec.parameters:
@@ -727,7 +870,7 @@ def main():
 
         args.namelist = yaml.safe_load(open(args.namelist))
     lib = _lib.Library(args.lib) if args.lib else _lib.load()
-    names = [s for s in args.only.split(",") if s] or sorted(SAVEPOINTS) + ["DynCore", "QSInit"]
+    names = [s for s in args.only.split(",") if s] or sorted(SAVEPOINTS) + ["DynCore", "QSInit", "FVUpdatePhys", "FillGFS"]
     found = {os.path.basename(p).rsplit("-In.", 1)[0] for p in glob.glob(os.path.join(args.directory, "*-In.*"))}
     failed = 0
     for name in names:
@@ -740,6 +883,13 @@ def main():
         if name == "DynCore" and name in found:
             ok, bound, worst = run_dyncore(read_pair(args.directory, name), args, lib)
             print(f"DynCore: {'PASS' if ok else 'FAIL'}  bound {bound:g} (six ranks, halo updates included)")
+            print("   the reference's windows: " + "  ".join(f"{k} {v:.2e}" for k, v in sorted(worst.items())))
+            failed += 0 if ok else 1
+            continue
+        if name in ("FVUpdatePhys", "FillGFS") and name in found:
+            run = run_fv_update_phys if name == "FVUpdatePhys" else run_fillgfs
+            ok, bound, worst = run(read_pair(args.directory, name), args, lib)
+            print(f"{name}: {'PASS' if ok else 'FAIL'}  bound {bound:g}" + (" (six ranks, halo updates included)" if name == "FVUpdatePhys" else ""))
             print("   the reference's windows: " + "  ".join(f"{k} {v:.2e}" for k, v in sorted(worst.items())))
             failed += 0 if ok else 1
             continue
