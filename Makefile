@@ -3,7 +3,7 @@
 # tests/emu/README.md).
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC := pace_amd/csrc
-SRCS := $(CSRC)/capi.hip $(CSRC)/k_fxadv.hip $(CSRC)/k_fvtp2d.hip $(CSRC)/k_fvt.hip $(CSRC)/k_fvt16.hip $(CSRC)/k_delnflux.hip $(CSRC)/k_dsw.hip $(CSRC)/k_riem3.hip $(CSRC)/k_riem3f.hip $(CSRC)/k_sim1.hip $(CSRC)/k_ppm.hip $(CSRC)/k_csw.hip $(CSRC)/k_acoustic.hip $(CSRC)/k_halo.hip $(CSRC)/k_tracer.hip $(CSRC)/k_remap.hip $(CSRC)/k_l2e.hip $(CSRC)/k_satadj.hip $(CSRC)/k_subgridz.hip $(CSRC)/k_updphys.hip $(CSRC)/k_dycore.hip $(CSRC)/k_stencils.hip
+SRCS := $(CSRC)/capi.hip $(CSRC)/k_fxadv.hip $(CSRC)/k_fvtp2d.hip $(CSRC)/k_fvt.hip $(CSRC)/k_fvt16.hip $(CSRC)/k_delnflux.hip $(CSRC)/k_dsw.hip $(CSRC)/k_riem3.hip $(CSRC)/k_riem3f.hip $(CSRC)/k_sim1.hip $(CSRC)/k_ppm.hip $(CSRC)/k_csw.hip $(CSRC)/k_acoustic.hip $(CSRC)/k_halo.hip $(CSRC)/k_tracer.hip $(CSRC)/k_remap.hip $(CSRC)/k_l2e.hip $(CSRC)/k_satadj.hip $(CSRC)/k_subgridz.hip $(CSRC)/k_updphys.hip $(CSRC)/k_microphys.hip $(CSRC)/k_dycore.hip $(CSRC)/k_stencils.hip
 HDRS := $(CSRC)/k_fvt.hip $(CSRC)/common.h $(CSRC)/kernels.h $(CSRC)/thermo.h $(CSRC)/delnflux_core.h $(CSRC)/fvt_core.h include/pace_hip.h
 # -ffp-contract=off: no FMA contraction, so horizontal stencils are bit-comparable with the numpy oracle.
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function
@@ -56,6 +56,15 @@ emu-f32: tests/emu/libpace_emu_f32.so
 tests/emu/libpace_emu_f32.so: $(EMUF32OBJS) build/emu/hip_emu.o
 	g++ -shared -fPIC $(EXPORTS) $(EMUF32OBJS) build/emu/hip_emu.o -o $@
 
+# the emulation with the microphysics' branch counters (tools/make_golden_microphysics.py counts the fixture's coverage with it)
+MPCOVOBJS := $(patsubst $(CSRC)/%.hip,build/emu_mpcov/%.o,$(SRCS))
+build/emu_mpcov/%.o: $(CSRC)/%.hip $(HDRS) tests/emu/hip_emu.h
+	@mkdir -p build/emu_mpcov
+	g++ $(EMUFLAGS) -DPACE_MP_COVERAGE -c $< -o $@
+emu-mpcov: tests/emu/libpace_emu_mpcov.so
+tests/emu/libpace_emu_mpcov.so: $(MPCOVOBJS) build/emu/hip_emu.o
+	g++ -shared -fPIC $(EXPORTS) $(MPCOVOBJS) build/emu/hip_emu.o -o $@
+
 # the same, with 4 x 4 transport / damping tiles and runs of 2 interfaces: at C12 this gives workgroups that touch no tile
 # edge, so the straight-line interior code paths and every tile seam are exercised by the CPU test-suite as well
 SMALLFLAGS := $(EMUFLAGS) -DFV_TI=4 -DFV_TJ=4 -DDN_TI=4 -DDN_TJ=4 -DFV_RF=2 -DDD_TI=5 -DDD_TJ=4 -DAB_TI=6 -DAB_TJ=3 -DCSW_TI=4 -DCSW_TJ=3
@@ -80,6 +89,6 @@ tests/emu/libpace_emu_canon.so: $(CANONOBJS) build/emu/hip_emu.o
 	g++ -shared -fPIC $(EXPORTS) $(CANONOBJS) build/emu/hip_emu.o -o $@
 
 clean:
-	rm -rf build pace_amd/libpace_hip.so pace_amd/libpace_hip_f32.so tests/emu/libpace_emu.so tests/emu/libpace_emu_small.so tests/emu/libpace_emu_f32.so tests/emu/libpace_emu_canon.so
+	rm -rf build pace_amd/libpace_hip.so pace_amd/libpace_hip_f32.so tests/emu/libpace_emu.so tests/emu/libpace_emu_small.so tests/emu/libpace_emu_f32.so tests/emu/libpace_emu_canon.so tests/emu/libpace_emu_mpcov.so
 
-.PHONY: all f32 emu emu-f32 emu-small emu-canon clean
+.PHONY: all f32 emu emu-f32 emu-small emu-canon emu-mpcov clean

@@ -495,6 +495,39 @@ int pace_update_dwinds_phys(const pace_geom_t* geom, pace_real_t* u, pace_real_t
                             const pace_real_t* const* ew2, const pace_real_t* edge_vect_w, const pace_real_t* edge_vect_e,
                             const pace_real_t* edge_vect_s, const pace_real_t* edge_vect_n, double dt5, void* stream);
 
+/* ---- Microphysics (physics/pace/physics/stencils/microphysics.py:1897-2533): the GFDL cloud microphysics, non-hydrostatic,
+ * NamelistDefaults switches.  One launch over origin (3, 3, 0), domain (n, n, nk), no host synchronisation: fields_init, ntimes x
+ * (warm_rain, sedimentation, warm_rain, icloud), fields_update.  float64 storage only (PACE_ERR_UNSUPPORTED otherwise).
+ *   workspace      pace_microphysics_workspace_bytes(geom) bytes of device memory: the work state of the columns
+ *   cfg            namelist values and the factors the reference's setupm / _set_timestep compute on the host, by value; a
+ *                  struct_bytes other than sizeof(pace_microphysics_config_t) is PACE_ERR_ARG
+ *   in             HOST array of PACE_MICROPHYSICS_INPUTS device pointers: pt, qvapor, qliquid, qrain, qice, qsnow, qgraupel, ua,
+ *                  va, delprsi, delz (3-D), land, area (2-D); read only
+ *   wmp            vertical velocity (inout: the sedimentation transports it)
+ *   tendencies     HOST array of PACE_MICROPHYSICS_TENDENCIES device pointers: qv_dt, ql_dt, qr_dt, qi_dt, qs_dt, qg_dt, qa_dt, udt,
+ *                  vdt, pt_dt; ACCUMULATED into (udt, vdt from level 1 on), except qa_dt, which is set to zero (do_qa)
+ *   precipitation  HOST array of four device pointers: rain, snow, ice, graupel (out, mm/day, the column's value on every level) */
+#define PACE_MICROPHYSICS_INPUTS 13
+#define PACE_MICROPHYSICS_TENDENCIES 10
+typedef struct {
+  int32_t struct_bytes; /* sizeof(pace_microphysics_config_t) */
+  int32_t ntimes;       /* sub-steps */
+  double timestep, rdt, dts, rdts, dt_rain;
+  double c_air, c_vap, d0_vap, lv00, cpaut, fac_rc, so3, zs, log_10, tice, tice0, t_wfr, t_sub;
+  double ccn_l, ccn_o, dw_land, dw_ocean, rh_inc, rh_inr;
+  double vr_fac, vr_max, vi_fac, vi_max, vs_fac, vs_max, vg_fac, vg_max;
+  double ql_mlt, qs_mlt, qi0_crt, qs0_crt, qi_gen, qi_lim;
+  double cracs, csacr, cgacr, cgacs;
+  double acco[3][4];
+  double csacw, csaci, cgacw, cgaci, cracw;
+  double cssub[5], crevp[5], cgfr[2], csmlt[5], cgmlt[5];
+  double ces0, fac_i2s, fac_g2v, fac_v2g, fac_imlt, fac_l2v;
+} pace_microphysics_config_t;
+int64_t pace_microphysics_workspace_bytes(const pace_geom_t* geom);
+int pace_microphysics(const pace_geom_t* geom, void* workspace, const pace_microphysics_config_t* cfg,
+                      const pace_real_t* const* in, pace_real_t* wmp, pace_real_t* const* tendencies,
+                      pace_real_t* const* precipitation, void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

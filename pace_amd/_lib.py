@@ -86,6 +86,26 @@ class SatAdjustParams(C.Structure):
     )
 
 
+MICROPHYSICS_INPUTS = ("pt", "qvapor", "qliquid", "qrain", "qice", "qsnow", "qgraupel", "ua", "va", "delprsi", "delz", "land", "area")
+MICROPHYSICS_TENDENCIES = ("qv_dt", "ql_dt", "qr_dt", "qi_dt", "qs_dt", "qg_dt", "qa_dt", "udt", "vdt", "pt_dt")
+MICROPHYSICS_SCALARS = (
+    "timestep rdt dts rdts dt_rain c_air c_vap d0_vap lv00 cpaut fac_rc so3 zs log_10 tice tice0 t_wfr t_sub ccn_l ccn_o dw_land "
+    "dw_ocean rh_inc rh_inr vr_fac vr_max vi_fac vi_max vs_fac vs_max vg_fac vg_max ql_mlt qs_mlt qi0_crt qs0_crt qi_gen qi_lim "
+    "cracs csacr cgacr cgacs").split()
+
+
+class MicrophysicsConfig(C.Structure):  # include/pace_hip.h pace_microphysics_config_t
+    _fields_ = (
+        [("struct_bytes", C.c_int32), ("ntimes", C.c_int32)]
+        + [(n, C.c_double) for n in MICROPHYSICS_SCALARS]
+        + [("acco", (C.c_double * 4) * 3)]
+        + [(n, C.c_double) for n in ("csacw", "csaci", "cgacw", "cgaci", "cracw")]
+        + [("cssub", C.c_double * 5), ("crevp", C.c_double * 5), ("cgfr", C.c_double * 2), ("csmlt", C.c_double * 5),
+           ("cgmlt", C.c_double * 5)]
+        + [(n, C.c_double) for n in ("ces0", "fac_i2s", "fac_g2v", "fac_v2g", "fac_imlt", "fac_l2v")]
+    )
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -171,6 +191,9 @@ _PROTOS = {
                                                                               C.c_void_p]),
     "pace_dry_convective_adjust": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [C.c_int, C.c_int, C.c_double, C.c_double,
                                                                                          C.c_void_p]),
+    "pace_microphysics_workspace_bytes": (C.c_int64, [_P(Geom)]),
+    "pace_microphysics": (C.c_int, [_P(Geom), c_dp, _P(MicrophysicsConfig), _P(C.c_void_p), c_dp, _P(C.c_void_p), _P(C.c_void_p),
+                                    C.c_void_p]),
     "pace_fill_gfs_delp": (C.c_int, [_P(Geom), c_dp, c_dp, C.c_double, C.c_void_p]),
     "pace_phys_thermo_pressure": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [C.c_double, C.c_void_p]),
     "pace_update_dwinds_phys": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [_P(C.c_void_p)] * 4 + [c_dp] * 4 + [C.c_double, C.c_void_p]),

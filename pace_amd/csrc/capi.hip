@@ -613,6 +613,25 @@ int pace_update_dwinds_phys(const pace_geom_t* geom, real* u, real* v, real* u_d
                                    edge_vect_s, edge_vect_n, dt5, S(stream));
 }
 
+int64_t pace_microphysics_workspace_bytes(const pace_geom_t* geom) {
+  return (geom && geom_check(geom) == PACE_OK) ? (int64_t)microphysics_workspace_bytes(make_geo(geom)) : 0;
+}
+
+int pace_microphysics(const pace_geom_t* geom, void* workspace, const pace_microphysics_config_t* cfg, const real* const* in,
+                      real* wmp, real* const* tendencies, real* const* precipitation, void* stream) {
+  NEED(geom && workspace && cfg && in && wmp && tendencies && precipitation);
+  if (cfg->struct_bytes != (int32_t)sizeof(pace_microphysics_config_t)) return PACE_ERR_ARG;  // built against another header
+  if (sizeof(real) != 8) return PACE_ERR_UNSUPPORTED;  // QCMIN, QVMIN are no float32 quantities
+  for (int n = 0; n < PACE_MICROPHYSICS_INPUTS; ++n)
+    if (!in[n]) return PACE_ERR_ARG;
+  for (int n = 0; n < PACE_MICROPHYSICS_TENDENCIES; ++n)
+    if (!tendencies[n]) return PACE_ERR_ARG;
+  for (int n = 0; n < 4; ++n)
+    if (!precipitation[n]) return PACE_ERR_ARG;
+  if (cfg->ntimes < 1 || !(cfg->timestep > 0.0) || !(cfg->dts > 0.0)) return PACE_ERR_ARG;
+  return launch_microphysics(make_geo(geom), workspace, in, wmp, tendencies, precipitation, *cfg, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

@@ -281,6 +281,10 @@ int launch_update_dwinds_phys(const Geo& g, real* u, real* v, real* u_dt, real* 
                               const real* const* vlat, const real* const* es1, const real* const* ew2, const real* edge_vect_w,
                               const real* edge_vect_e, const real* edge_vect_s, const real* edge_vect_n, double dt5,
                               hipStream_t st);
+// k_microphys.hip
+long microphysics_workspace_bytes(const Geo& g);
+int launch_microphysics(const Geo& g, void* workspace, const real* const* in, real* wmp, real* const* tend, real* const* precip,
+                        const pace_microphysics_config_t& cfg, hipStream_t st);
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);
 int launch_omega_from_w(const Geo& g, const real* delp, const real* delz, const real* w, real* omga, hipStream_t st);

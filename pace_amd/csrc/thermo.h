@@ -34,6 +34,7 @@ constexpr double LI2 = LV0 + LI00;
 constexpr double E00 = 611.21;
 constexpr double T_WFR = TICE - 40.0;
 constexpr double TICE0 = TICE - 0.01;
+constexpr double T_MIN = 178.0;
 constexpr double T_SAT_MIN = TICE - 160.0;
 constexpr double LAT2 = (HLV + HLF) * (HLV + HLF);
 }  // namespace phys

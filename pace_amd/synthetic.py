@@ -267,3 +267,76 @@ def convective_state(n, nk):
     s["u_dt"] = np.full(shape, 0.25)
     s["v_dt"] = np.full(shape, 0.25)
     return s
+
+
+def microphysics_columns(n, nk):
+    """Temperature, layer mass and (negative) layer depth on the compute domain of a tile of any size, (n, n, nk): a smooth
+    troposphere from 300 Pa to the surface with the freezing level inside it -- what microphysics_state() fills with water."""
+    i, j, k = np.meshgrid(np.arange(n), np.arange(n), np.arange(nk + 1), indexing="ij")
+    pe = 300.0 + (1.0e5 - 300.0) * (k / nk) ** 1.6 * (1.0 + 0.02 * np.sin(0.05 * i + 0.03 * j))
+    delp = pe[:, :, 1:] - pe[:, :, :-1]
+    pmid = pe[:, :, :-1] + 0.5 * delp
+    t = 205.0 + 90.0 * (pmid / 1.0e5) + 6.0 * np.sin(0.04 * i[:, :, :nk] + 0.06 * j[:, :, :nk])
+    delz = -(c.RDGAS * t * delp / (c.GRAV * pmid))
+    return t, delp, delz
+
+
+def microphysics_state(pt, delp, delz, dry=False):
+    """The fields of a MicrophysicsState on the compute domain (name -> (nx, ny, nk); land: (nx, ny)), every one a function of
+    the three given arrays and of position only: cloud water (supercooled down to below t_wfr) and rain below and a little above
+    the freezing level, cloud ice / snow / graupel above and across it, humidity between 0.25 and 1.25 of saturation, a few
+    negative values for fix_negative, columns without rain / ice / snow / graupel, a mixed land mask, non-zero omga.
+
+    The lowest six layers are cooled to just below freezing (a surface inversion under the warm layer, pt is returned changed),
+    kept near saturation and hold every species: what falls then reaches the ground in every column.  Without that the surface
+    precipitation of a species that stops falling above the ground is the rounding residue of the implicit scheme's column sum
+    (1e-17 mm/day of either sign), which no comparison can hold.
+    dry: no condensate anywhere."""
+    nx, ny, nk = pt.shape
+    i, j, k = np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nk), indexing="ij")
+    col = i * ny + j
+    depth = (nk - 1) - k  # layers above the lowest one
+    t_surf = 267.5 + 1.5 * np.sin(0.8 * i + 0.3 * j)
+    weight = np.clip((9.0 - depth) / 4.0, 0.0, 1.0)
+    pt = pt - weight * (pt[:, :, -1:] - t_surf)
+    low = depth <= 5
+    den = -delp / (c.GRAV * delz)
+    es = c.E00 * np.exp((c.DC_VAP * np.log(pt / c.TICE) + c.LV0 * (pt - c.TICE) / (pt * c.TICE)) / c.RVGAS)
+    qsat = es / (c.RVGAS * pt * den)
+    s = {"pt": pt, "delz": delz.copy(), "dz": delz.copy()}
+    rh = 0.75 + 0.5 * np.sin(0.9 * i + 0.5 * j + 0.21 * k)
+    rh = np.where(low, 1.06 + 0.04 * np.sin(0.9 * i + 0.5 * j + 0.21 * k), rh)
+    qv = np.minimum(rh * qsat, 0.025)
+    qv = np.where(((i + 2 * j + 3 * k) % 29 == 0) & ~low, -1.0e-6, qv)
+    s["qvapor"] = qv
+    wave = lambda m: 0.1 + 0.9 * (0.5 + 0.5 * np.sin(0.7 * i + 1.3 * j + 0.43 * k + 1.7 * m))  # noqa: E731
+    spec = (("qliquid", 2e-3, pt > 228.0, None), ("qrain", 3e-4, pt > 258.0, col % 5 == 0),
+            ("qice", 2e-4, (pt < 279.0) | low, col % 8 == 1), ("qsnow", 3e-4, (pt < 284.0) | low, col % 4 == 2),
+            ("qgraupel", 2e-4, (pt < 284.0) | low, col % 6 == 3))
+    for m, (name, scale, where, absent) in enumerate(spec):
+        f = scale * np.where(low, 0.6 + 0.4 * wave(m), wave(m)) * where
+        f = np.where((((3 * i + 5 * j + 7 * k + m) % 23) == 0) & ~low, -0.3 * f, f)
+        if absent is not None:
+            f = np.where(absent, 0.0, f)
+        if name == "qsnow":  # heavy snow near the ground where there is no graupel: its autoconversion makes some there
+            f = np.where(low & (col % 6 == 3), 4e-3 * (0.8 + 0.2 * wave(m)), f)
+        s[name] = np.zeros(pt.shape) if dry else f
+    s["qcld"] = 0.3 * wave(5) * (0.0 if dry else 1.0)
+    cond = s["qliquid"] + s["qrain"] + s["qice"] + s["qsnow"] + s["qgraupel"]
+    s["delp"] = delp.copy()
+    s["delprsi"] = delp * (1.0 - cond)
+    s["ua"] = 15.0 * np.sin(0.4 * i + 0.2 * j) + 0.25 * (nk - k) + 2.0 * np.sin(0.8 * k + 0.3 * i)
+    s["va"] = 5.0 * np.cos(0.3 * i - 0.5 * j) + 1.5 * np.cos(0.6 * k + 0.2 * j)
+    s["omga"] = 0.5 * np.sin(0.5 * i + 0.7 * j + 0.9 * k)
+    # prepare_microphysics (physics/pace/physics/stencils/physics.py:133-139)
+    s["wmp"] = -s["omga"] * (1.0 + c.ZVIR * qv) * pt / delp * (c.RDGAS * c.RGRAV)
+    land = np.where((i[:, :, 0] + 2 * j[:, :, 0]) % 3 == 0, 1.0, 0.0)
+    s["land"] = np.where((i[:, :, 0] + j[:, :, 0]) % 7 == 3, 0.4, land)
+    return s
+
+
+def microphysics_tendencies(shape, m):
+    """Non-zero tendencies on entry, exact in any arithmetic: multiples of 2 ** -40 that depend on position and on the field's
+    number m."""
+    i, j, k = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), np.arange(shape[2]), indexing="ij")
+    return (((3 * i + 5 * j + 7 * k + 11 * m) % 17) - 8.0) * 2.0 ** -40

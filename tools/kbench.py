@@ -1,6 +1,6 @@
 """Per-entry-point timing on the GPU box (HIP events on the launch stream), C192 x 79 by default.
 
-    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust,apply_physics]
+    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust,apply_physics,microphysics]
 """
 import argparse
 import os
@@ -166,10 +166,48 @@ def main():
 
     if not only or set(only) & set(apply_physics):  # (the driver grid terms take a grid generation: only when they are timed)
         build_apply_physics()
+
+    # Microphysics (k_microphys.hip) on pace_amd.synthetic's columns and fill, one sub-step (225 s) and two (450 s).  wmp is
+    # transported and the tendencies are accumulated: both are restored before every repetition.  Traffic: 12 fields read and 9
+    # tendencies read, 15 written (wmp, ten tendencies, the precipitation on every level) -- the algorithm's, not the workspace's.
+    mp_cases = {}
+
+    def build_microphysics():
+        from pace_amd.physics import Microphysics, MicrophysicsState, PhysicsConfig
+
+        if args.precision != 64:
+            raise SystemExit("microphysics needs the float64 library")
+        pt_h, delp_h, delz_h = synthetic.microphysics_columns(n, nz)
+        mp_h = synthetic.microphysics_state(pt_h, delp_h, delz_h)
+
+        def full(a):
+            out = np.zeros((n + 7, n + 7, nz + 1) if a.ndim == 3 else (n + 7, n + 7))
+            out[(slice(3, 3 + n), slice(3, 3 + n)) + ((slice(0, nz),) if a.ndim == 3 else ())] = a
+            return out
+
+        names = "pt qvapor qliquid qrain qice qsnow qgraupel qcld ua va delp delz omga delprsi wmp dz".split()
+        q = {k: env.q3(full(mp_h[k])) for k in names}
+        state = MicrophysicsState(*[q[k] for k in names[:13]], q["delprsi"], q["wmp"], q["dz"], env.q3(), env.q2(full(mp_h["land"])))
+        op = Microphysics(env.stencil_factory, env.qf, env.grid_data,
+                          PhysicsConfig(dt_atmos=225, hydrostatic=False, npx=n + 1, npy=n + 1, npz=nz, nwat=6, do_qa=True))
+        wmp0 = full(mp_h["wmp"])
+
+        def restore_microphysics():
+            q["wmp"].set(wmp0)
+            for k in _lib.MICROPHYSICS_TENDENCIES:
+                getattr(state, k).data.zero_()
+        mp_cases.update(microphysics=lambda: op(state, 225.0), microphysics_2=lambda: op(state, 450.0), restore=restore_microphysics)
+
+    if not only or "microphysics" in only:
+        build_microphysics()
+        if "microphysics" in only:
+            only.append("microphysics_2")
     cases = {
         "fill_gfs_delp": (ap_cases.get("fill_gfs_delp"), 3),
         "phys_thermo_pressure": (ap_cases.get("phys_thermo_pressure"), 14),
         "update_dwinds_phys": (ap_cases.get("update_dwinds_phys"), 8),
+        "microphysics": (mp_cases.get("microphysics"), 36),
+        "microphysics_2": (mp_cases.get("microphysics_2"), 36),
         "dry_convective_adjust": (lambda: dry_adj(cv_state, cv["u_dt"], cv["v_dt"], 225.0), 32.0 * ks / nz),
         "sat_adjust": (sat_adjust, 19),
         "fxadv": (lambda: prep(f["uc"], f["vc"], f["crx"], f["cry"], f["xfx"], f["yfx"], ut, vt, s["dt"]), 8),
@@ -202,6 +240,9 @@ def main():
                 torch.cuda.synchronize()
             if name == "dry_convective_adjust" or name in apply_physics:
                 restore_dry_adj()
+                torch.cuda.synchronize()
+            if name.startswith("microphysics"):
+                mp_cases["restore"]()
                 torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
