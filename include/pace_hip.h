@@ -528,6 +528,43 @@ int pace_microphysics(const pace_geom_t* geom, void* workspace, const pace_micro
                       const pace_real_t* const* in, pace_real_t* wmp, pace_real_t* const* tendencies,
                       pace_real_t* const* precipitation, void* stream);
 
+/* ---- The Physics shell and the physics-to-dycore coupling (physics/pace/physics/stencils/physics.py:33-201, get_prs_fv3.py,
+ * get_phi_fv3.py; stencils/pace/stencils/update_atmos_state.py:40-145).  One launch each, no host synchronisation, no
+ * allocation, no scratch field; fp64 arithmetic in the reference's order, no transcendental.  float64 storage only
+ * (PACE_ERR_UNSUPPORTED otherwise).  Every table is a HOST array of device pointers.
+ *   pace_copy_dycore_to_physics        copy_dycore_to_physics over origin (3, 3, 0), domain (n + 1, n + 1, nk): out[m] = in[m]
+ *                                      for PACE_PHYSICS_COPY_FIELDS fields (the reference's order: qvapor, qliquid, qrain, qsnow,
+ *                                      qice, qgraupel, qo3mr, qsgs_tke, qcld, pt, delp, delz, ua, va, w, omga)
+ *   pace_physics_prepare               what Physics.__call__ does before the microphysics, over origin (3, 3, 0), domain
+ *                                      (n, n, nk): atmos_phys_driver_statein (nwat 6), get_prs_fv3, get_phi_fv3 and, with
+ *                                      do_microphysics != 0, prepare_microphysics.  tracers: qvapor, qliquid, qrain, qice, qsnow,
+ *                                      qgraupel, qo3mr (times the moist delp, over the dry one), qsgs_tke (over the dry one).
+ *                                      delp (inout) becomes the clamped mid-layer pressure; prsi and phii (out) get nk + 1 levels,
+ *                                      phil and delprsi nk.  do_microphysics: dz, wmp (out) and the PACE_MICROPHYSICS_TENDENCIES
+ *                                      tendencies (set to zero); otherwise omga, dz, wmp and tendencies are not used and may be
+ *                                      NULL.  Nothing outside the compute domain is written (the reference runs get_prs_fv3 and
+ *                                      get_phi_fv3 over the halo too), level nk of the layer fields is neither read nor written,
+ *                                      and the reference's prsik is not computed.
+ *   pace_physics_update_state          update_physics_state_with_tendencies: out[m] = x[m] + x_dt[m] * dt for
+ *                                      PACE_PHYSICS_UPDATED_FIELDS fields over origin (3, 3, 0), domain (n, n, nk)
+ *   pace_physics_tendencies_to_dycore  prepare_tendencies_and_update_tracers over origin (3, 3, 0), domain (n, n, nk).
+ *                                      tendencies: u_dt, v_dt, pt_dt, ACCUMULATED into (+= (updated - before) * rdt); updated:
+ *                                      physics_updated_ua, _va, _pt, _specific_humidity, _qliquid, _qrain, _qsnow, _qice,
+ *                                      _qgraupel (nine); before: the physics state's ua, va, pt; tracers: the dycore's qvapor,
+ *                                      qliquid, qrain, qsnow, qice, qgraupel (inout); prsi: nk + 1 levels; delp (inout): the dycore's */
+#define PACE_PHYSICS_COPY_FIELDS 16
+#define PACE_PHYSICS_UPDATED_FIELDS 10
+int pace_copy_dycore_to_physics(const pace_geom_t* geom, const pace_real_t* const* in, pace_real_t* const* out, void* stream);
+int pace_physics_prepare(const pace_geom_t* geom, pace_real_t* const* tracers, const pace_real_t* pt, const pace_real_t* delz,
+                         pace_real_t* delp, const pace_real_t* omga, pace_real_t* prsi, pace_real_t* phii, pace_real_t* phil,
+                         pace_real_t* delprsi, pace_real_t* dz, pace_real_t* wmp, pace_real_t* const* tendencies, double ptop,
+                         int do_microphysics, void* stream);
+int pace_physics_update_state(const pace_geom_t* geom, const pace_real_t* const* x, const pace_real_t* const* x_dt,
+                              pace_real_t* const* out, double dt, void* stream);
+int pace_physics_tendencies_to_dycore(const pace_geom_t* geom, pace_real_t* const* tendencies, const pace_real_t* const* updated,
+                                      const pace_real_t* const* before, pace_real_t* const* tracers, const pace_real_t* prsi,
+                                      pace_real_t* delp, double rdt, void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

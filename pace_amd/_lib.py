@@ -88,6 +88,16 @@ class SatAdjustParams(C.Structure):
 
 MICROPHYSICS_INPUTS = ("pt", "qvapor", "qliquid", "qrain", "qice", "qsnow", "qgraupel", "ua", "va", "delprsi", "delz", "land", "area")
 MICROPHYSICS_TENDENCIES = ("qv_dt", "ql_dt", "qr_dt", "qi_dt", "qs_dt", "qg_dt", "qa_dt", "udt", "vdt", "pt_dt")
+# include/pace_hip.h PACE_PHYSICS_COPY_FIELDS / PACE_PHYSICS_UPDATED_FIELDS: the fields of pace_copy_dycore_to_physics, and the
+# state fields, their tendencies (MicrophysicsState) and the physics_updated_* fields of pace_physics_update_state
+PHYSICS_COPY_FIELDS = ("qvapor", "qliquid", "qrain", "qsnow", "qice", "qgraupel", "qo3mr", "qsgs_tke", "qcld", "pt", "delp", "delz",
+                       "ua", "va", "w", "omga")
+PHYSICS_PREPARE_TRACERS = ("qvapor", "qliquid", "qrain", "qice", "qsnow", "qgraupel", "qo3mr", "qsgs_tke")
+PHYSICS_UPDATED = (("qvapor", "qv_dt", "physics_updated_specific_humidity"), ("qliquid", "ql_dt", "physics_updated_qliquid"),
+                   ("qrain", "qr_dt", "physics_updated_qrain"), ("qice", "qi_dt", "physics_updated_qice"),
+                   ("qsnow", "qs_dt", "physics_updated_qsnow"), ("qgraupel", "qg_dt", "physics_updated_qgraupel"),
+                   ("qcld", "qa_dt", "physics_updated_cloud_fraction"), ("pt", "pt_dt", "physics_updated_pt"),
+                   ("ua", "udt", "physics_updated_ua"), ("va", "vdt", "physics_updated_va"))
 MICROPHYSICS_SCALARS = (
     "timestep rdt dts rdts dt_rain c_air c_vap d0_vap lv00 cpaut fac_rc so3 zs log_10 tice tice0 t_wfr t_sub ccn_l ccn_o dw_land "
     "dw_ocean rh_inc rh_inr vr_fac vr_max vi_fac vi_max vs_fac vs_max vg_fac vg_max ql_mlt qs_mlt qi0_crt qs0_crt qi_gen qi_lim "
@@ -194,6 +204,10 @@ _PROTOS = {
     "pace_microphysics_workspace_bytes": (C.c_int64, [_P(Geom)]),
     "pace_microphysics": (C.c_int, [_P(Geom), c_dp, _P(MicrophysicsConfig), _P(C.c_void_p), c_dp, _P(C.c_void_p), _P(C.c_void_p),
                                     C.c_void_p]),
+    "pace_copy_dycore_to_physics": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_void_p), C.c_void_p]),
+    "pace_physics_prepare": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 10 + [_P(C.c_void_p), C.c_double, C.c_int, C.c_void_p]),
+    "pace_physics_update_state": (C.c_int, [_P(Geom)] + [_P(C.c_void_p)] * 3 + [C.c_double, C.c_void_p]),
+    "pace_physics_tendencies_to_dycore": (C.c_int, [_P(Geom)] + [_P(C.c_void_p)] * 4 + [c_dp, c_dp, C.c_double, C.c_void_p]),
     "pace_fill_gfs_delp": (C.c_int, [_P(Geom), c_dp, c_dp, C.c_double, C.c_void_p]),
     "pace_phys_thermo_pressure": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [C.c_double, C.c_void_p]),
     "pace_update_dwinds_phys": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [_P(C.c_void_p)] * 4 + [c_dp] * 4 + [C.c_double, C.c_void_p]),

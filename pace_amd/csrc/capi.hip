@@ -632,6 +632,53 @@ int pace_microphysics(const pace_geom_t* geom, void* workspace, const pace_micro
   return launch_microphysics(make_geo(geom), workspace, in, wmp, tendencies, precipitation, *cfg, S(stream));
 }
 
+static bool all_set(const void* const* table, int count) {
+  for (int n = 0; n < count; ++n)
+    if (!table[n]) return false;
+  return true;
+}
+
+int pace_copy_dycore_to_physics(const pace_geom_t* geom, const real* const* in, real* const* out, void* stream) {
+  NEED(geom && in && out);
+  if (sizeof(real) != 8) return PACE_ERR_UNSUPPORTED;  // the physics is float64 only (pace_microphysics)
+  if (!all_set((const void* const*)in, PACE_PHYSICS_COPY_FIELDS) || !all_set((const void* const*)out, PACE_PHYSICS_COPY_FIELDS))
+    return PACE_ERR_ARG;
+  return launch_copy_dycore_to_physics(make_geo(geom), in, out, S(stream));
+}
+
+int pace_physics_prepare(const pace_geom_t* geom, real* const* tracers, const real* pt, const real* delz, real* delp,
+                         const real* omga, real* prsi, real* phii, real* phil, real* delprsi, real* dz, real* wmp,
+                         real* const* tendencies, double ptop, int do_microphysics, void* stream) {
+  NEED(geom && tracers && pt && delz && delp && prsi && phii && phil && delprsi);
+  if (sizeof(real) != 8) return PACE_ERR_UNSUPPORTED;
+  if (!all_set((const void* const*)tracers, 8)) return PACE_ERR_ARG;
+  if (do_microphysics && !(omga && dz && wmp && tendencies && all_set((const void* const*)tendencies, PACE_MICROPHYSICS_TENDENCIES)))
+    return PACE_ERR_ARG;
+  return launch_physics_prepare(make_geo(geom), tracers, pt, delz, delp, omga, prsi, phii, phil, delprsi, dz, wmp, tendencies,
+                                ptop, do_microphysics != 0, S(stream));
+}
+
+int pace_physics_update_state(const pace_geom_t* geom, const real* const* x, const real* const* x_dt, real* const* out, double dt,
+                              void* stream) {
+  NEED(geom && x && x_dt && out);
+  if (sizeof(real) != 8) return PACE_ERR_UNSUPPORTED;
+  if (!all_set((const void* const*)x, PACE_PHYSICS_UPDATED_FIELDS) || !all_set((const void* const*)x_dt, PACE_PHYSICS_UPDATED_FIELDS) ||
+      !all_set((const void* const*)out, PACE_PHYSICS_UPDATED_FIELDS))
+    return PACE_ERR_ARG;
+  return launch_physics_update_state(make_geo(geom), x, x_dt, out, dt, S(stream));
+}
+
+int pace_physics_tendencies_to_dycore(const pace_geom_t* geom, real* const* tendencies, const real* const* updated,
+                                      const real* const* before, real* const* tracers, const real* prsi, real* delp, double rdt,
+                                      void* stream) {
+  NEED(geom && tendencies && updated && before && tracers && prsi && delp);
+  if (sizeof(real) != 8) return PACE_ERR_UNSUPPORTED;
+  if (!all_set((const void* const*)tendencies, 3) || !all_set((const void* const*)updated, 9) ||
+      !all_set((const void* const*)before, 3) || !all_set((const void* const*)tracers, 6))
+    return PACE_ERR_ARG;
+  return launch_physics_tendencies_to_dycore(make_geo(geom), tendencies, updated, before, tracers, prsi, delp, rdt, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

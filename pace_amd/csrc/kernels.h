@@ -285,6 +285,16 @@ int launch_update_dwinds_phys(const Geo& g, real* u, real* v, real* u_dt, real* 
 long microphysics_workspace_bytes(const Geo& g);
 int launch_microphysics(const Geo& g, void* workspace, const real* const* in, real* wmp, real* const* tend, real* const* precip,
                         const pace_microphysics_config_t& cfg, hipStream_t st);
+// k_physics.hip
+int launch_copy_dycore_to_physics(const Geo& g, const real* const* in, real* const* out, hipStream_t st);
+int launch_physics_prepare(const Geo& g, real* const* tracers, const real* pt, const real* delz, real* delp, const real* omga,
+                           real* prsi, real* phii, real* phil, real* delprsi, real* dz, real* wmp, real* const* tendencies,
+                           double ptop, int do_microphysics, hipStream_t st);
+int launch_physics_update_state(const Geo& g, const real* const* x, const real* const* x_dt, real* const* out, double dt,
+                                hipStream_t st);
+int launch_physics_tendencies_to_dycore(const Geo& g, real* const* tendencies, const real* const* updated,
+                                        const real* const* before, real* const* tracers, const real* prsi, real* delp,
+                                        double rdt, hipStream_t st);
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);
 int launch_omega_from_w(const Geo& g, const real* delp, const real* delz, const real* w, real* omga, hipStream_t st);

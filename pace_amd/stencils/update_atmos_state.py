@@ -4,7 +4,8 @@
     DycoreToPhysics(...)(dycore_state, None, tendency_state, timestep)       the dry convective adjustment
     UpdateAtmosphereState(...)(dycore_state, None, u_dt, v_dt, pt_dt, dt)    fill_gfs_delp, then ApplyPhysicsToDycore
 
-Physics is out of scope: dycore_only=False raises NotImplementedError."""
+dycore_only=False raises NotImplementedError in both constructors: what the reference does there are operators of their own,
+pace_amd.stencils.CopyDycoreToPhysics and PhysicsToDycore (physics_coupling.py), run around pace_amd.physics.Physics."""
 from typing import Optional
 
 from ..fv3core.stencils.fv_subgridz import DryConvectiveAdjustment
@@ -15,7 +16,7 @@ from .fv_update_phys import ApplyPhysicsToDycore
 class DycoreToPhysics:
     def __init__(self, stencil_factory, quantity_factory, dycore_config, do_dry_convective_adjust: bool, dycore_only: bool):
         if not dycore_only:
-            raise NotImplementedError("DycoreToPhysics: only dycore_only=True -- there is no physics state to copy to")
+            raise NotImplementedError("DycoreToPhysics: only dycore_only=True -- the copy to a physics state is pace_amd.stencils.CopyDycoreToPhysics")
         refuse_other_layouts(dycore_config)
         self._do_dry_convective_adjustment = do_dry_convective_adjust
         self._dycore_only = dycore_only
@@ -37,7 +38,8 @@ class UpdateAtmosphereState(Operator):
     def __init__(self, stencil_factory, grid_data, namelist, comm, grid_info, state, quantity_factory, dycore_only: bool,
                  apply_tendencies: bool, tendency_state):
         if not dycore_only:
-            raise NotImplementedError("UpdateAtmosphereState: only dycore_only=True -- physics tendencies are not gathered here")
+            raise NotImplementedError("UpdateAtmosphereState: only dycore_only=True -- physics tendencies are gathered by "
+                                      "pace_amd.stencils.PhysicsToDycore")
         refuse_other_layouts(namelist)
         qf = quantity_factory if quantity_factory is not None else stencil_factory.quantity_factory
         if qf is None:

@@ -340,3 +340,15 @@ def microphysics_tendencies(shape, m):
     number m."""
     i, j, k = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), np.arange(shape[2]), indexing="ij")
     return (((3 * i + 5 * j + 7 * k + 11 * m) % 17) - 8.0) * 2.0 ** -40
+
+
+def physics_extras(shape):
+    """The three fields a physics state copies from the dycore besides those of microphysics_state(), name -> array of
+    `shape` = (nx, ny, nk), functions of position only: ozone (with a few negative values), turbulent kinetic energy and the
+    vertical wind."""
+    i, j, k = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), np.arange(shape[2]), indexing="ij")
+    qo3mr = 1.0e-6 * (0.2 + 0.8 * (0.5 + 0.5 * np.sin(0.31 * i + 0.17 * j + 0.23 * k)))
+    qo3mr = np.where((2 * i + 3 * j + 5 * k) % 31 == 0, -0.1 * qo3mr, qo3mr)
+    qsgs_tke = 1.0e-2 * (0.1 + 0.9 * (0.5 + 0.5 * np.cos(0.19 * i - 0.29 * j + 0.37 * k)))
+    w = 0.4 * np.sin(0.5 * i + 0.7 * j + 0.9 * k)
+    return {"qo3mr": qo3mr, "qsgs_tke": qsgs_tke, "w": w}

@@ -1,6 +1,6 @@
 """Per-entry-point timing on the GPU box (HIP events on the launch stream), C192 x 79 by default.
 
-    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust,apply_physics,microphysics]
+    python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust,apply_physics,microphysics,physics]
 """
 import argparse
 import os
@@ -202,7 +202,72 @@ def main():
         build_microphysics()
         if "microphysics" in only:
             only.append("microphysics_2")
+    # The Physics shell and the coupling (k_physics.hip), each kernel alone on pace_amd.synthetic's columns, fill and extras.  prepare
+    # and the coupling change their inputs: the state is restored from device copies before every repetition.  Field passes per
+    # cell: the copy 16 + 16; prepare 15 read (nine in the sweep down, six in the sweep up) and 26 written; update 20 + 10; the
+    # coupling 23 read and 10 written.  `--only physics` selects the four.
+    physics_kernels = ("physics_copy", "physics_prepare", "physics_update", "physics_coupling")
+    ph_cases = {}
+
+    def build_physics():
+        import types
+
+        from pace_amd.physics import Physics, PhysicsConfig, PhysicsState
+        from pace_amd.stencils import CopyDycoreToPhysics, PhysicsToDycore
+
+        if args.precision != 64:
+            raise SystemExit("the physics needs the float64 library")
+        host = synthetic.microphysics_state(*synthetic.microphysics_columns(n, nz))
+        host.update(synthetic.physics_extras(host["pt"].shape))
+
+        def full(a):
+            out = np.ones((n + 7, n + 7, nz + 1) if a.ndim == 3 else (n + 7, n + 7))
+            out[(slice(3, 3 + n), slice(3, 3 + n)) + ((slice(0, nz),) if a.ndim == 3 else ())] = a
+            return out
+
+        nml = PhysicsConfig(dt_atmos=225, hydrostatic=False, npx=n + 1, npy=n + 1, npz=nz, nwat=6, do_qa=True)
+        dycore = types.SimpleNamespace(**{k: env.q3(full(host[k])) for k in _lib.PHYSICS_COPY_FIELDS})
+        state = PhysicsState.init_zeros(env.qf, ["microphysics"])
+        state.land.copy_(env.q2(full(host["land"])).data)
+        copy = CopyDycoreToPhysics(env.stencil_factory, env.qf)
+        physics = Physics(env.stencil_factory, env.qf, env.grid_data, nml, ["microphysics"])
+        couple = PhysicsToDycore(env.stencil_factory, env.qf, nml)
+        tend = [env.q3(), env.q3(), env.q3()]
+        copy(dycore, state)
+        entry = {k: getattr(state, k).clone() for k in _lib.PHYSICS_COPY_FIELDS}  # the physics state before prepare
+        physics(state, 225.0)
+        dycore_entry = {k: getattr(dycore, k).data.clone() for k in ("delp",) + _lib.PHYSICS_COPY_FIELDS[:6]}
+        humidity = state.physics_updated_specific_humidity.clone()
+
+        def restore_physics(name):
+            if name == "physics_prepare":
+                for k, v in entry.items():
+                    getattr(state, k).copy_(v)
+            if name == "physics_coupling":
+                for k, v in dycore_entry.items():
+                    getattr(dycore, k).data.copy_(v)
+                state.physics_updated_specific_humidity.copy_(humidity)
+        ph_cases.update(physics_copy=lambda: copy(dycore, state), physics_prepare=lambda: physics.prepare(state),
+                        physics_update=lambda: physics.update(state, 225.0),
+                        physics_coupling=lambda: couple.call(
+                            "pace_physics_tendencies_to_dycore", *coupling_args(couple, dycore, state, tend)),
+                        restore=restore_physics)
+
+    def coupling_args(couple, dycore, state, tend):
+        from pace_amd.stencils.physics_coupling import _SUM_ORDER, _UPDATED, _pointers
+
+        return (_pointers(tend), _pointers([getattr(state, k) for k in _UPDATED]), _pointers([state.ua, state.va, state.pt]),
+                _pointers([getattr(dycore, k) for k in _SUM_ORDER]), dptr(state.prsi), dptr(dycore.delp), 1.0 / 225.0, couple.stream())
+
+    if "physics" in only:
+        only += list(physics_kernels)
+    if not only or set(only) & set(physics_kernels):
+        build_physics()
     cases = {
+        "physics_copy": (ph_cases.get("physics_copy"), 32),
+        "physics_prepare": (ph_cases.get("physics_prepare"), 41),
+        "physics_update": (ph_cases.get("physics_update"), 30),
+        "physics_coupling": (ph_cases.get("physics_coupling"), 33),
         "fill_gfs_delp": (ap_cases.get("fill_gfs_delp"), 3),
         "phys_thermo_pressure": (ap_cases.get("phys_thermo_pressure"), 14),
         "update_dwinds_phys": (ap_cases.get("update_dwinds_phys"), 8),
@@ -243,6 +308,9 @@ def main():
                 torch.cuda.synchronize()
             if name.startswith("microphysics"):
                 mp_cases["restore"]()
+                torch.cuda.synchronize()
+            if name in physics_kernels:
+                ph_cases["restore"](name)
                 torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
