@@ -54,6 +54,8 @@ void emu_shuffle_exchange(const void* mine, void* out, int src_lane_in_wave, int
 
 namespace {
 const char* volatile g_kernel_name = "(no kernel)";
+volatile bool g_in_launch = false;
+struct sigaction g_prev_segv, g_prev_bus;  // what was installed before this library's reporter
 char g_altstack[64 * 1024];
 
 // async-signal-safe enough for a test tool: format by hand, write(2), _exit
@@ -68,7 +70,27 @@ void put_num(unsigned long v, int base) {
   } while (v);
   while (n) (void)!write(2, &buf[--n], 1);
 }
-void on_segv(int, siginfo_t* si, void*) {
+void on_segv(int sig, siginfo_t* si, void* uc) {
+  if (!g_in_launch) {
+    // A process may hold several emulation libraries (float64 and float32 storage, other tile sizes), each with a reporter and
+    // a kernel name of its own, and the one loaded last owns the signal.  If this one is not running a kernel, the fault belongs to
+    // whoever came before it: another library's reporter (which reports and exits, or passes it on in the same way), or the
+    // interpreter's fault handler for a fault of the host code.  That one writes its traceback, puts the default disposition
+    // back and raises the signal again; the signal stays pending, because it is blocked while this handler runs (no
+    // SA_NODEFER here), so control comes back and the lines below still end the process with the reporter's exit status.
+    // g_in_launch is one flag per library, not per thread: emu_launch holds its mutex from before the flag is set until after
+    // it is cleared, so at most one thread of the process is inside a launch of this library.
+    const struct sigaction& prev = sig == SIGBUS ? g_prev_bus : g_prev_segv;
+    if (prev.sa_flags & SA_SIGINFO) {
+      if (prev.sa_sigaction) prev.sa_sigaction(sig, si, uc);
+    } else if (prev.sa_handler != SIG_DFL && prev.sa_handler != SIG_IGN) {
+      prev.sa_handler(sig);
+    }
+    put("[emu] invalid access at 0x");
+    put_num((unsigned long)si->si_addr, 16);
+    put(" outside a kernel launch\n");
+    _exit(99);
+  }
   put("[emu] invalid access at 0x");
   put_num((unsigned long)si->si_addr, 16);
   put(" in kernel ");
@@ -90,8 +112,8 @@ struct GuardInit {
     struct sigaction sa {};
     sa.sa_sigaction = on_segv;
     sa.sa_flags = SA_SIGINFO | SA_ONSTACK;
-    sigaction(SIGSEGV, &sa, nullptr);
-    sigaction(SIGBUS, &sa, nullptr);
+    sigaction(SIGSEGV, &sa, &g_prev_segv);
+    sigaction(SIGBUS, &sa, &g_prev_bus);
   }
 } g_guard_init;
 }  // namespace
@@ -101,6 +123,10 @@ void emu_launch(dim3 grid, dim3 block, const std::function<void()>& body, int* m
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
   g_kernel_name = name;
+  struct InLaunch {
+    InLaunch() { g_in_launch = true; }
+    ~InLaunch() { g_in_launch = false; }
+  } in_launch;
   gridDim = grid;
   blockDim = block;
   g_body = &body;

@@ -3,7 +3,7 @@
 GPU sanitizers are not available, and an out-of-bounds READ of a kernel is silent on the CPU as long as it lands in mapped
 memory -- on the GPU it is a memory access fault whenever the array happens to end at the end of an allocator segment.
 `guarded()` makes every CPU tensor the host layer allocates (QuantityFactory fields, metric terms, workspaces, per-level
-tables) end exactly at an inaccessible page (mode "over") or start right after one (mode "under"), so such an access faults
+and saturation tables) end exactly at an inaccessible page (mode "over") or start right after one (mode "under"), so such an access faults
 under emulation too; with PACE_EMU_GUARD=1 the emulator reports the kernel, block and thread (tests/emu/hip_emu.cpp).
 """
 import contextlib
@@ -34,10 +34,10 @@ def guarded_array(shape, dtype, mode):
 
 @contextlib.contextmanager
 def guarded(mode="over"):
-    """Within the block torch.full / torch.zeros / torch.as_tensor make guarded CPU tensors."""
+    """Within the block torch.full / torch.zeros / torch.empty / torch.as_tensor make guarded CPU tensors."""
     import torch
 
-    real_full, real_zeros, real_as_tensor = torch.full, torch.zeros, torch.as_tensor
+    real_full, real_zeros, real_empty, real_as_tensor = torch.full, torch.zeros, torch.empty, torch.as_tensor
     np_dtype = {torch.float64: np.float64, torch.int64: np.int64, torch.bool: np.bool_, torch.float32: np.float32,
                 torch.int32: np.int32}
 
@@ -58,6 +58,15 @@ def guarded(mode="over"):
             size = tuple(size[0])
         return full(size, 0, dtype=dtype, device=device)
 
+    def empty(*size, dtype=None, device=None, **kw):
+        """(the saturation tables of SatAdjust3d; what a kernel does not write stays NaN, not zero)"""
+        if not on_cpu(device) or kw or (dtype or torch.float64) not in np_dtype:
+            return real_empty(*size, dtype=dtype, device=device, **kw)
+        if len(size) == 1 and not isinstance(size[0], int):
+            size = tuple(size[0])
+        dtype = dtype or torch.float64
+        return full(size, float("nan") if dtype.is_floating_point else 0, dtype=dtype, device=device)
+
     def as_tensor(data, dtype=None, device=None):
         t = real_as_tensor(data, dtype=dtype, device=device)
         if t.device.type != "cpu" or t.dtype not in np_dtype or t.dim() == 0:
@@ -66,8 +75,8 @@ def guarded(mode="over"):
         a[...] = t.numpy()
         return torch.from_numpy(a)
 
-    torch.full, torch.zeros, torch.as_tensor = full, zeros, as_tensor
+    torch.full, torch.zeros, torch.empty, torch.as_tensor = full, zeros, empty, as_tensor
     try:
         yield
     finally:
-        torch.full, torch.zeros, torch.as_tensor = real_full, real_zeros, real_as_tensor
+        torch.full, torch.zeros, torch.empty, torch.as_tensor = real_full, real_zeros, real_empty, real_as_tensor

@@ -30,6 +30,15 @@ def oracle_grid(metrics, n, nk):
     return Grid(n, nk, dict(metrics))
 
 
+def minimal_metrics(n, area=1.0):
+    """The metric terms an Env needs at any size, for operators that read none of them but (at most) the cell area.
+    (tools/make_golden_physics.py make_env holds the same dictionary plus ptop -- tools/ imports nothing from tests/: keep the
+    two alike.)"""
+    full = area if isinstance(area, np.ndarray) else np.full((n + 7, n + 7), float(area))
+    return {"area": full, "da_min": 1.0, "da_min_c": 1.0,
+            **{k: np.zeros((n + 7, n + 7)) for k in ("del6_u", "del6_v", "divg_u", "divg_v")}}
+
+
 def _make(target):
     """`make <target>` under an exclusive file lock: several test processes (pytest -n) may ask for the same library at once."""
     import fcntl
@@ -47,6 +56,13 @@ def build_emu():
     """Build tests/emu/libpace_emu.so (the kernel sources compiled for the CPU).  Test infrastructure."""
     _make("emu")
     return os.path.join(ROOT, "tests", "emu", "libpace_emu.so")
+
+
+def build_emu_f32():
+    """tests/emu/libpace_emu_f32.so: the emulation build with float32 storage (Makefile emu-f32).  Every test that wants it asks
+    here: a bare `make emu-f32` next to a locked one links the library from objects another process is still writing."""
+    _make("emu-f32")
+    return os.path.join(ROOT, "tests", "emu", "libpace_emu_f32.so")
 
 
 def build_emu_canon():

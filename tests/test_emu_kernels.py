@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (DSW_ARGS, Env, build_emu_small, oracle_grid, acoustic_errors, check_tracer_outputs, run_acoustic_six_tiles, run_tracer_six_tiles, build_emu, column_for_levels, compare, dsw_window, expand_riem_fixture, golden, run_d_sw,
+from helpers import (DSW_ARGS, Env, build_emu_small, oracle_grid, acoustic_errors, check_tracer_outputs, run_acoustic_six_tiles, run_tracer_six_tiles, build_emu, build_emu_f32, column_for_levels, compare, dsw_window, expand_riem_fixture, golden, run_d_sw,
                      run_riem3, window)
 
 
@@ -167,7 +167,7 @@ def _legacy_solver_child(precision):
     from pace_amd import _lib, synthetic
     from oracle import vertical
 
-    lib = _lib.Library(build_emu() if precision == 64 else __import__("test_f32").build_emu_f32())
+    lib = _lib.Library(build_emu() if precision == 64 else build_emu_f32())
     out = {}
     # riem_solver3 on the reference-run fixture
     fix = golden("riem_solver3_c12_tile0_call3.npz")

@@ -9,24 +9,14 @@ to 6e-8 of its value each time it is stored.  Bounds (max |got - ref| / max |ref
     field's range); 2e-3 for the horizontal winds and 2e-2 for w / omga -- the algorithm amplifies 1e-13 of wind noise to
     2e-4 in one step of this zonal-flow case (tools/wind_noise_sensitivity.py), float32 rounding is a million times more.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from helpers import (DSW_ARGS, ROOT, Env, column_for_levels, dsw_window, dycore_scaled_errors, golden, run_d_sw,
+from helpers import (DSW_ARGS, Env, build_emu_f32, column_for_levels, dsw_window, dycore_scaled_errors, golden, run_d_sw,
                      run_dycore_six_tiles)
 
 STEP_TOL = {"u": 2e-3, "v": 2e-3, "va": 2e-3, "ua": 2e-3, "w": 2e-2, "omga": 2e-2, "qliquid": 1e-4, "qrain": 1e-4, "qice": 1e-4,
             "qsnow": 1e-4, "qgraupel": 1e-4, "q_con": 1e-4}
-
-
-def build_emu_f32():
-    from helpers import _make
-
-    _make("emu-f32")
-    return os.path.join(ROOT, "tests", "emu", "libpace_emu_f32.so")
 
 
 def check_d_sw(lib, device):

@@ -10,7 +10,7 @@ import types
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, Env, build_emu, compare, golden
+from helpers import GOLDEN, Env, build_emu, build_emu_f32, compare, golden, minimal_metrics
 
 N, NZ = 12, 79
 TRACERS = ["qvapor", "qliquid", "qrain", "qice", "qsnow", "qgraupel", "qo3mr", "qsgs_tke", "qcld"]
@@ -30,13 +30,9 @@ def emu_lib():
 
 @pytest.fixture(scope="module")
 def emu_f32_lib():
-    import subprocess
-
     from pace_amd import _lib
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.run(["make", "-s", "-j8", "emu-f32"], cwd=root, check=True)
-    return _lib.Library(os.path.join(root, "tests", "emu", "libpace_emu_f32.so"))
+    return _lib.Library(build_emu_f32())
 
 
 @pytest.fixture(scope="module")
@@ -75,24 +71,25 @@ def expected(d, name, inp):
     return out
 
 
-def embed(inp, pe00):
+def embed(inp, pe00, n=N):
     """The inputs in NaN-filled storage; of pe only the element the operator reads is set."""
     full = {}
     for name in IN3 + ["pe", "u_dt", "v_dt"]:
-        a = np.full((N + 7, N + 7, NZ + 1), np.nan)
+        a = np.full((n + 7, n + 7, NZ + 1), np.nan)
         if name in inp:
-            a[C, C, :inp[name].shape[2]] = inp[name]
+            a[3:3 + n, 3:3 + n, :inp[name].shape[2]] = inp[name]
         full[name] = a
     full["pe"][3, 3, 0] = pe00
     return full
 
 
-def run_case(lib, device, d, inp, tensors=False, n_sponge="fixture"):
-    """DryConvectiveAdjustment with the case's arguments on `inp`; returns (outputs, storage before the call) as full arrays."""
+def run_case(lib, device, d, inp, tensors=False, n_sponge="fixture", n=N):
+    """DryConvectiveAdjustment with the case's arguments on `inp` (n x n columns; the operator reads no metric term, so any size
+    other than the fixture's gets minimal ones); returns (outputs, storage before the call) as full arrays."""
     from pace_amd.fv3core import DryConvectiveAdjustment
 
-    env = Env(lib, device, golden("grid_c12_tile0.npz"), N, NZ)
-    full = embed(inp, float(d["pe00"]))
+    env = Env(lib, device, golden("grid_c12_tile0.npz") if n == N else minimal_metrics(n), n, NZ)
+    full = embed(inp, float(d["pe00"]), n)
     q = {k: env.q3(v) for k, v in full.items()}
     if n_sponge == "fixture":
         n_sponge = None if int(d["n_sponge"]) < 0 else int(d["n_sponge"])
@@ -111,19 +108,23 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
-def check_bitwise(d, out, full, inp, tag):
+def check_bitwise(d, out, full, inp, tag, n=N, gather=None):
+    """`inp`: the fixture's C12 inputs (the expectation is stored against them); gather: what takes a C12 window to the n x n
+    one the operator ran on (tests/columns.py), none at C12."""
     ks = int(d["k_sponge"])
     for name in OUT:
-        ref, got = expected(d, name, inp), out[name][C, C, :ks]
+        ref, got = expected(d, name, inp), out[name][3:3 + n, 3:3 + n, :ks]
+        if gather is not None:
+            ref = gather(ref)
         same = bits(ref) == bits(got)
         assert same.all(), (tag, name, int((~same).sum()), "points differ; worst", compare(ref, got))
-    check_outside(out, full, ks, tag)
+    check_outside(out, full, ks, tag, n=n)
 
 
-def check_outside(out, full, ks, tag, f32=False):
+def check_outside(out, full, ks, tag, f32=False, n=N):
     """Halo, the extra level and levels >= k_sponge keep their bits, in every field the operator is given."""
-    outside = np.ones((N + 7, N + 7, NZ + 1), dtype=bool)
-    outside[C, C, :ks] = False
+    outside = np.ones((n + 7, n + 7, NZ + 1), dtype=bool)
+    outside[3:3 + n, 3:3 + n, :ks] = False
     for name in full:
         before = full[name].astype(np.float32).astype(np.float64) if f32 else full[name]
         where = outside if name in OUT else np.ones_like(outside)

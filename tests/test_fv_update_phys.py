@@ -21,7 +21,7 @@ import types
 import numpy as np
 import pytest
 
-from helpers import ROOT, build_emu, golden
+from helpers import ROOT, build_emu, build_emu_f32, golden
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fv_update_phys_np as npr  # noqa: E402
@@ -48,8 +48,7 @@ def emu_lib():
 def emu_f32_lib():
     from pace_amd import _lib
 
-    subprocess.run(["make", "-s", "-j8", "emu-f32"], cwd=ROOT, check=True)
-    return _lib.Library(os.path.join(ROOT, "tests", "emu", "libpace_emu_f32.so"))
+    return _lib.Library(build_emu_f32())
 
 
 # ---- fixtures, inputs, expectations ----------------------------------------------------------------------------------------

@@ -1,9 +1,11 @@
 """Out-of-bounds accesses of the kernels, caught on the CPU: the emulated kernels run in a child process in which every array
 the host layer allocates ends at (mode "over") or starts right after (mode "under") an inaccessible page (tests/guard.py).
 A kernel that reads or writes outside an array it was handed dies there, and the emulator names it (PACE_EMU_GUARD=1).
+Covered: the 15 operators of the acoustic loop, one DynamicalCore step, and the emulated tests of the moist side (both modes).
 GPU sanitizers are not available on the pool; on the device such an access is a memory fault only when the array happens to
 end at the end of an allocator segment (found that way in round 2: a metric row of a tile that sticks out of the storage)."""
 import os
+import re
 import subprocess
 import sys
 
@@ -18,6 +20,10 @@ import guard, helpers
 from pace_amd import _lib
 lib = _lib.Library(helpers.build_emu())
 """
+
+
+PHYSICS_SIDE = ["test_microphysics.py", "test_physics.py", "test_physics_coupling.py", "test_fv_subgridz.py",
+                "test_fv_update_phys.py", "test_sat_adjust.py", "test_column_tiling.py"]
 
 
 def _run(body, mode):
@@ -50,3 +56,57 @@ def test_dynamical_core_step_with_guard_pages():
 fixes, outs = helpers.run_dycore_six_tiles(lib, "cpu", generated="metrics")
 helpers.check_dycore(fixes, outs)
 """, "over")
+
+
+def test_allocations_are_guarded_when_asked():
+    """PACE_GUARD_MODE set (the child runs below): the session fixture of tests/conftest.py has put tests/guard.py's wrappers in
+    place of torch's four allocators, and a tensor from them lies against an inaccessible page.  Not set: torch's own."""
+    import torch
+
+    mode = os.environ.get("PACE_GUARD_MODE")
+    wrapped = [f.__module__ == "guard" for f in (torch.full, torch.zeros, torch.empty, torch.as_tensor)]
+    if not mode:
+        assert not any(wrapped)
+        return
+    assert all(wrapped), wrapped
+    import mmap
+
+    for t in (torch.empty(5, dtype=torch.float64), torch.zeros(3, 2), torch.as_tensor([1.0, 2.0])):
+        edge = t.data_ptr() + t.numel() * t.element_size() if mode == "over" else t.data_ptr()
+        assert edge % mmap.PAGESIZE == 0, (mode, hex(edge))
+    assert torch.isnan(torch.empty(5, dtype=torch.float64)).all()
+
+
+@pytest.mark.parametrize("mode", ["over", "under"])
+def test_physics_side_with_guard_pages(mode):
+    """The moist side -- k_satadj.hip, k_subgridz.hip, k_updphys.hip, k_microphys.hip, k_physics.hip -- under guard pages: every
+    emulated test of PHYSICS_SIDE (results as well as bounds; the C68 column-tiled cases, the saturation tables and
+    LagrangianToEulerian(do_sat_adj=True) among them) in one child pytest without workers, whose session fixture
+    (tests/conftest.py, PACE_GUARD_MODE) guards every allocation.  These kernels sweep to level nk of nk + 1-level storage, read
+    delp[a - sk] from level 1 on, clamp their chunked loads and index 1-D edge vectors by the storage's i: an access one
+    element outside ends the child, and the emulator names the kernel.  (Not seen: an overrun of exactly the one spare double
+    every workspace has, and the padding of Quantity rows.)"""
+    env = dict(os.environ, PACE_GUARD_MODE=mode, PACE_EMU_GUARD="1")
+    env.pop("PYTEST_XDIST_WORKER", None)  # (the child is a pytest of its own, not a worker of this one)
+    env.pop("PYTEST_XDIST_WORKER_COUNT", None)
+    env.pop("PYTEST_CURRENT_TEST", None)
+    # (--capture=sys: what the emulator and the fault handler write to the process's own stderr when a kernel dies is not lost)
+    here = os.path.join(ROOT, "tests")
+    command = [sys.executable, "-X", "faulthandler", "-m", "pytest", "-n0", "-m", "not gpu", "-p", "no:cacheprovider", "-q", "-rp",
+               "--capture=sys", "test_guard_pages.py::test_allocations_are_guarded_when_asked", *PHYSICS_SIDE]
+    p = subprocess.run(command, cwd=here, capture_output=True, text=True, timeout=1200, env=env)
+    tail = p.stdout[-3000:] + "\n" + p.stderr[-3000:]
+    assert p.returncode == 0, f"the guarded run ({mode}) ended with {p.returncode}:\n{tail}"
+    assert " passed" in p.stdout and "failed" not in p.stdout.splitlines()[-1] and "skipped" not in p.stdout.splitlines()[-1], tail
+    # ... and it was a guarded run of what it is meant to be: the sentinel above passed in the child (the wrappers were in place),
+    # every file contributed, the C68 cases of all five operators among them
+    passed = set(re.findall(r"^PASSED (\S+)", p.stdout, flags=re.M))
+    assert "test_guard_pages.py::test_allocations_are_guarded_when_asked" in passed, tail
+    for name in PHYSICS_SIDE:
+        assert any(t.startswith(name + "::") for t in passed), (name, tail)
+    for case in ("test_microphysics_c68[emulated-base]", "test_microphysics_c68[emulated-sub2]", "test_microphysics_c68[emulated-mptime]",
+                 "test_microphysics_c68[emulated-dry]", "test_microphysics_c68[emulated-accum]", "test_physics_c68[emulated]",
+                 "test_physics_to_dycore_c68[emulated]", "test_dry_convective_adjust_c68[emulated-base]",
+                 "test_sat_adjust_c68[emulated-mid]", "test_l2e_sat_adj_emulated[True]"):
+        assert any(t.endswith("::" + case) for t in passed), (case, tail)
+    assert len(passed) >= 100, len(passed)  # (81 before the C68 cases and the workspace tests, 109 with them)

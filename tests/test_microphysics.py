@@ -10,7 +10,8 @@ State fields the reference leaves alone have to keep their bits.
 Measured (worst over the five cases; every test prints its own): the emulated library udt 1.8e-11, vdt 5.2e-11, the species'
 tendencies <= 5e-13, pt_dt 1.3e-12, wmp 1.9e-15, precipitation 7.8e-15; the MI355X udt 1.2e-10, vdt 5.2e-11, qg_dt 2.3e-11,
 qi_dt 4.6e-12, the other species <= 5.8e-13, pt_dt 1.8e-12, wmp 2.3e-15, precipitation 7.3e-14; the device against the emulated
-library at C20 x 79 udt 1.4e-11.  The bound stays the reference's."""
+library at C20 x 79 udt 1.4e-11.  The bound stays the reference's.  The workspace tests (NaN on entry, reuse across cases) are bit
+identity against a fresh operator and hold on the emulated library and on the MI355X for every case."""
 import ctypes as C
 import dataclasses
 import os
@@ -21,7 +22,7 @@ import types
 import numpy as np
 import pytest
 
-from helpers import ROOT, Env, build_emu, compare
+from helpers import ROOT, Env, build_emu, build_emu_f32, compare, minimal_metrics
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from make_golden_microphysics import CASES, COVERAGE, MAX_ERROR, NEAR_ZERO, OUT, PRECIP, STATE3, TEND, load_split  # noqa: E402
@@ -87,9 +88,7 @@ def embed(a, n, fill=np.nan):
 
 
 def make_env(lib, device, area, n, nk):
-    metrics = {"area": embed(area, n, 1.0), "da_min": 1.0, "da_min_c": 1.0,
-               **{k: np.zeros((n + 7, n + 7)) for k in ("del6_u", "del6_v", "divg_u", "divg_v")}}
-    return Env(lib, device, metrics, n, nk)
+    return Env(lib, device, minimal_metrics(n, embed(area, n, 1.0)), n, nk)
 
 
 def namelist(mp_time=225.0, **kw):
@@ -153,15 +152,17 @@ def window(out, name, n=N, nk=NZ):
     return out[name][3:3 + n, 3:3 + n, :nk]
 
 
-def check_against_reference(tag, out, inp, what):
+def check_against_reference(tag, out, inp, what, n=N, gather=None):
+    """gather: what takes the fixture's C12 window to the n x n one the operator ran on (tests/columns.py), none at C12."""
     d = case(tag)
     worst = {}
     for name in OUT:
-        worst[name] = compare(d["out_" + name], window(out, name), near_zero=NEAR_ZERO.get(name, 1e-18))
+        ref = d["out_" + name] if gather is None else gather(d["out_" + name])
+        worst[name] = compare(ref, window(out, name, n), near_zero=NEAR_ZERO.get(name, 1e-18))
     print(what, tag, " ".join(f"{k} {v:.1e}" for k, v in worst.items()))
     for name, e in worst.items():
         assert e <= MAX_ERROR, (tag, name, e)
-    check_untouched(out, inp)
+    check_untouched(out, inp, n)
 
 
 def check_untouched(out, inp, n=N, nk=NZ):
@@ -275,6 +276,63 @@ def test_state_copies_the_tendency(emu_lib):
     assert len(ptrs) == len(TEND)
 
 
+# ---- the workspace between calls -----------------------------------------------------------------------------------------------
+# The sixteen work arrays live in one workspace the operator allocates once (zeros) and hands to every call.  A work array the
+# kernel read before its first write of that call would see zeros in a fresh operator and the previous step's values in a model
+# run.  So: the workspace poisoned with NaN, and the workspace as another case left it, both against a fresh operator, bit for bit
+# on the whole storage of every field.
+
+def run_copied(lib, device, inp, tag, op=None, poison=False):
+    """run() on case `tag`'s timestep, the arrays copied (on the CPU they are views, the precipitation's of the operator's own
+    storage, which the next call writes); poison: the operator's workspace filled with NaN before the call."""
+    from pace_amd.physics import Microphysics
+
+    if poison:
+        env = make_env(lib, device, inp["area"], N, NZ)
+        op = Microphysics(env.stencil_factory, env.qf, env.grid_data, namelist(CASES[tag]["mp_time"]))
+        op._workspace.fill_(float("nan"))
+    out, op = run(lib, device, inp, [CASES[tag]["timestep"]], CASES[tag]["mp_time"], op=op)
+    return {name: np.array(a) for name, a in out.items()}, op
+
+
+def assert_same_storage(got, want, what):
+    assert sorted(got) == sorted(want)
+    for name in got:
+        differ = bits(got[name]) != bits(want[name])
+        assert not differ.any(), (what, name, int(differ.sum()), "values differ; first at", tuple(np.argwhere(differ)[0]))
+
+
+def check_poisoned_workspace(lib, device, tag):
+    inp = case_inputs(tag)
+    fresh, _ = run_copied(lib, device, inp, tag)
+    poisoned, op = run_copied(lib, device, inp, tag, poison=True)
+    assert_same_storage(poisoned, fresh, f"{tag}, workspace NaN on entry")
+    for name in OUT:
+        assert np.isfinite(window(poisoned, name)).all(), (tag, name)
+    return op
+
+
+def check_reuse_across_cases(lib, device, first, second):
+    """`first` then `second` on one operator: the second call gives what a fresh operator gives on the same inputs."""
+    _, op = run_copied(lib, device, case_inputs(first), first)
+    assert float(op._workspace.abs().max()) > 0  # (the first call left something behind)
+    inp = case_inputs(second)
+    reused, _ = run_copied(lib, device, inp, second, op=op)
+    fresh, _ = run_copied(lib, device, inp, second)
+    assert_same_storage(reused, fresh, f"{second} after {first} on one operator")
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_nan_in_the_workspace_changes_nothing_emulated(emu_lib, tag):
+    check_poisoned_workspace(emu_lib, "cpu", tag)
+
+
+@pytest.mark.parametrize("first,second", [("base", "dry"), ("dry", "base")])
+def test_workspace_reused_across_cases_emulated(emu_lib, first, second):
+    """dry skips every fall path: what base left in the work arrays of the falls is still there to be read."""
+    check_reuse_across_cases(emu_lib, "cpu", first, second)
+
+
 # ---- the host layer ----------------------------------------------------------------------------------------------------------
 
 def test_exported_names_and_config():
@@ -336,13 +394,10 @@ def test_other_switch_values_are_refused(emu_lib):
 def test_float32_library_is_refused():
     """QCMIN = 1e-12 and QVMIN = 1e-20 are no float32 quantities: the constructor refuses the float32 build, and so does the
     entry point (the library still builds and links with the kernel in it)."""
-    import subprocess
-
     from pace_amd import _lib
     from pace_amd.physics import Microphysics
 
-    subprocess.run(["make", "-s", "-j8", "emu-f32"], cwd=ROOT, check=True)
-    f32 = _lib.Library(os.path.join(ROOT, "tests", "emu", "libpace_emu_f32.so"))
+    f32 = _lib.Library(build_emu_f32())
     env = make_env(f32, "cpu", fixture_inputs()["area"], N, NZ)
     with pytest.raises(NotImplementedError, match="float64"):
         Microphysics(env.stencil_factory, env.qf, env.grid_data, namelist())
@@ -399,6 +454,18 @@ def test_microphysics_gpu(lib, tag):
     out, op = run(lib, "cuda:0", inp, [CASES[tag]["timestep"]], CASES[tag]["mp_time"])
     assert op._ntimes == (2 if tag in ("sub2", "mptime") else 1)
     check_against_reference(tag, out, inp, "device")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", TAGS)
+def test_nan_in_the_workspace_changes_nothing_gpu(lib, tag):
+    check_poisoned_workspace(lib, "cuda:0", tag)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first,second", [("base", "dry"), ("dry", "base")])
+def test_workspace_reused_across_cases_gpu(lib, first, second):
+    check_reuse_across_cases(lib, "cuda:0", first, second)
 
 
 @pytest.mark.gpu

@@ -20,7 +20,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import ROOT, build_emu
+from helpers import ROOT, build_emu, build_emu_f32
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import make_golden_physics as mgp  # noqa: E402
@@ -261,8 +261,6 @@ def test_physics_state_init_zeros(emu_lib):
 
 
 def test_refusals(emu_lib):
-    import subprocess
-
     from pace_amd import _lib
     from pace_amd.physics import Physics
     from pace_amd.util.grid import geom_struct
@@ -280,8 +278,7 @@ def test_refusals(emu_lib):
         make(mgp.namelist(), ("microphysics", "pbl"))
     op = make(mgp.namelist())
     assert (op._nwat, op._p00, op._ptop, op._do_microphysics) == (6, 1.0e5, 300.0, True)
-    subprocess.run(["make", "-s", "-j8", "emu-f32"], cwd=ROOT, check=True)
-    f32 = _lib.Library(os.path.join(ROOT, "tests", "emu", "libpace_emu_f32.so"))
+    f32 = _lib.Library(build_emu_f32())
     env32 = mgp.make_env(f32, "cpu", inputs()["area"], N, NZ, 300.0)
     with pytest.raises(NotImplementedError, match="float64"):
         make(mgp.namelist(), (), env32)

@@ -13,7 +13,7 @@ import types
 import numpy as np
 import pytest
 
-from helpers import ROOT, build_emu
+from helpers import ROOT, build_emu, build_emu_f32
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import make_golden_physics as mgp  # noqa: E402
@@ -155,8 +155,6 @@ def test_copy_covers_its_domain_and_nothing_else(emu_lib):
 
 
 def test_refusals_and_checks(emu_lib):
-    import subprocess
-
     import torch
 
     from pace_amd import _lib, stencils
@@ -167,8 +165,7 @@ def test_refusals_and_checks(emu_lib):
     env = mgp.make_env(emu_lib, "cpu", inputs()["area"], N, NZ, 300.0)
     with pytest.raises(NotImplementedError, match="layout"):
         stencils.PhysicsToDycore(env.stencil_factory, env.qf, mgp.namelist(layout=(2, 2)))
-    subprocess.run(["make", "-s", "-j8", "emu-f32"], cwd=ROOT, check=True)
-    f32 = _lib.Library(os.path.join(ROOT, "tests", "emu", "libpace_emu_f32.so"))
+    f32 = _lib.Library(build_emu_f32())
     env32 = mgp.make_env(f32, "cpu", inputs()["area"], N, NZ, 300.0)
     with pytest.raises(NotImplementedError, match="float64"):
         stencils.PhysicsToDycore(env32.stencil_factory, env32.qf, mgp.namelist())

@@ -3,7 +3,7 @@ against runs of the reference (tools/make_golden_satadj.py): the emulated librar
 import numpy as np
 import pytest
 
-from helpers import Env, build_emu, compare, golden
+from helpers import Env, build_emu, build_emu_f32, compare, golden, minimal_metrics
 
 CASES = ["mid", "last", "consv", "rad", "icloud2"]
 SPECIES = ["qvapor", "qliquid", "qrain", "qsnow", "qice", "qgraupel"]
@@ -21,14 +21,9 @@ def emu_lib():
 
 @pytest.fixture(scope="module")
 def emu_f32_lib():
-    import os
-    import subprocess
-
     from pace_amd import _lib
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.run(["make", "-s", "-j8", "emu-f32"], cwd=root, check=True)
-    return _lib.Library(os.path.join(root, "tests", "emu", "libpace_emu_f32.so"))
+    return _lib.Library(build_emu_f32())
 
 
 @pytest.fixture(scope="module")
@@ -48,25 +43,26 @@ def case_config(tag):
     return SatAdjustConfig()
 
 
-def run_sat_adjust(lib, device, d, tag):
-    """SatAdjust3d on satadj_c12.npz's inputs embedded in NaN-filled storage; returns (outputs, inputs) as full arrays."""
+def run_sat_adjust(lib, device, d, tag, n=N):
+    """SatAdjust3d on satadj_c12.npz's inputs (or those gathered to n x n columns, tests/columns.py; the operator is handed its
+    area, so any other size gets minimal metrics) embedded in NaN-filled storage; returns (outputs, inputs) as full arrays."""
     import torch
 
     from pace_amd.fv3core.stencils.saturation_adjustment import SatAdjust3d
     from pace_amd.util import constants as c
 
     nk = len(d["k_sel"])
-    env = Env(lib, device, golden("grid_c12_tile0.npz"), N, nk)
+    env = Env(lib, device, golden("grid_c12_tile0.npz") if n == N else minimal_metrics(n), n, nk)
     full = {}
     for name in SA_OUT + ["delp", "delz"]:
-        a = np.full((N + 7, N + 7, nk + 1), np.nan)
-        a[3:15, 3:15, :nk] = d["in_" + name] if "in_" + name in d else 0.0
+        a = np.full((n + 7, n + 7, nk + 1), np.nan)
+        a[3:3 + n, 3:3 + n, :nk] = d["in_" + name] if "in_" + name in d else 0.0
         full[name] = a
     f = {k: env.q3(v) for k, v in full.items()}
-    area = np.full((N + 7, N + 7), np.nan)
-    area[3:15, 3:15] = d["area"]
-    hs = np.full((N + 7, N + 7), np.nan)
-    hs[3:15, 3:15] = d["hs"]
+    area = np.full((n + 7, n + 7), np.nan)
+    area[3:3 + n, 3:3 + n] = d["area"]
+    hs = np.full((n + 7, n + 7), np.nan)
+    hs[3:3 + n, 3:3 + n] = d["hs"]
     op = SatAdjust3d(env.stencil_factory, case_config(tag), env.q2(area), int(d["kmp"]))
     last = tag != "mid"
     op(f["te"], f["qvapor"], f["qliquid"], f["qice"], f["qrain"], f["qsnow"], f["qgraupel"], f["qcld"], env.q2(hs), None, f["delp"],
@@ -76,18 +72,18 @@ def run_sat_adjust(lib, device, d, tag):
     return {k: v.numpy() for k, v in f.items()}, full
 
 
-def check_sat_adjust(d, out, full, tag, tol, f32=False):
+def check_sat_adjust(d, out, full, tag, tol, f32=False, n=N):
     """Worst error per output on the window; everything outside the window (halo, k < kmp) holds what it held before."""
     kmp, nk = int(d["kmp"]), len(d["k_sel"])
     worst = {}
     for name in SA_OUT:
-        ref, got = d[f"out_{tag}_{name}"], out[name][3:15, 3:15, :nk]
+        ref, got = d[f"out_{tag}_{name}"], out[name][3:3 + n, 3:3 + n, :nk]
         e = compare(ref[:, :, kmp:], got[:, :, kmp:], near_zero=1e-9 if f32 else 1e-18)
         bound = tol(name) if callable(tol) else tol
         assert e < bound, (tag, name, e)
         worst[name] = e
         outside = np.ones(out[name].shape, dtype=bool)
-        outside[3:15, 3:15, kmp:nk] = False
+        outside[3:3 + n, 3:3 + n, kmp:nk] = False
         if not f32:
             assert np.array_equal(out[name][outside], full[name][outside], equal_nan=True), (tag, name, "outside the window")
         else:

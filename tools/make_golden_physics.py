@@ -91,6 +91,7 @@ def window(full, name, n, nk):
 def make_env(lib, device, area, n, nk, ptop):
     from pace_amd.tile import Env
 
+    # (the dictionary of tests/helpers.py minimal_metrics plus ptop; tools/ imports nothing from tests/: keep the two alike)
     metrics = {"area": embed(area, n, 1.0), "da_min": 1.0, "da_min_c": 1.0, "ptop": ptop,
                **{k: np.zeros((n + 7, n + 7)) for k in ("del6_u", "del6_v", "divg_u", "divg_v")}}
     return Env(lib, device, metrics, n, nk)
