@@ -155,11 +155,7 @@ int pace_d_sw_wind_outputs_supported(const pace_geom_t* geom, const pace_dsw_con
 int pace_d_sw_outputs_supported(const pace_geom_t* geom, const pace_column_t* col, const pace_dsw_config_t* cfg) {
   // the ONE predicate of what launch_d_sw accepts: the two queries above plus the condition on the column namelist they cannot see
   if (!geom || !col || !cfg || !col->nord_v || !col->nord_w || !col->nord_t) return 0;
-  const Geo g = make_geo(geom);
-  for (int k = 0; k < g.nk; ++k)
-    if (col->nord_v[k] > 2 || col->nord_w[k] > 2 || col->nord_t[k] > 2) return 0;
-  if (!dsw_pingpong_supported(g, cfg)) return 0;
-  return dsw_winds_in_scalars(g, cfg) ? 3 : 1;
+  return dsw_outputs_supported(make_geo(geom), col, cfg);
 }
 
 int pace_d_sw_prepare(const pace_geom_t* geom, const pace_column_t* col, void* workspace, void* stream) {
@@ -168,47 +164,42 @@ int pace_d_sw_prepare(const pace_geom_t* geom, const pace_column_t* col, void* w
 }
 
 static int d_sw_entry(int phases, const pace_geom_t* geom, const pace_metrics_t* met, const pace_column_t* col,
-                      const pace_dsw_config_t* cfg, void* workspace, real* delpc, real* delp, real* pt, real* u,
-                      real* v, real* w, real* uc, real* vc, const real* ua, const real* va, real* divgd,
-                      real* mfx, real* mfy, real* cx, real* cy, real* crx, real* cry, real* xfx, real* yfx,
-                      real* q_con, const real* zh, real* heat_source, real* diss_est, double dt, void* stream) {
+                      const pace_dsw_config_t* cfg, void* workspace, const DswFields& f, void* stream) {
   NEED(geom && met && col && cfg && workspace);
-  NEED(delpc && delp && pt && u && v && w && uc && vc && ua && va && divgd && mfx && mfy && cx && cy);
-  NEED(crx && cry && xfx && yfx && q_con && heat_source && diss_est);
+  NEED(f.delpc && f.delp && f.pt && f.u && f.v && f.w && f.uc && f.vc && f.ua && f.va && f.divgd && f.mfx && f.mfy && f.cx && f.cy);
+  NEED(f.crx && f.cry && f.xfx && f.yfx && f.q_con && f.heat_source && f.diss_est);
   if (cfg->struct_bytes != (int32_t)sizeof(pace_dsw_config_t)) return PACE_ERR_ARG;  // built against another header
-  {  // separate outputs: all four or none, none of them an input
-    const int given = (cfg->delp_out != nullptr) + (cfg->pt_out != nullptr) + (cfg->w_out != nullptr) + (cfg->q_con_out != nullptr);
-    if (given != 0 && given != 4) return PACE_ERR_ARG;
-    if (given && (cfg->delp_out == delp || cfg->pt_out == pt || cfg->w_out == w || cfg->q_con_out == q_con)) return PACE_ERR_ARG;
-    if (given && ((((uintptr_t)cfg->delp_out | (uintptr_t)cfg->pt_out | (uintptr_t)cfg->w_out | (uintptr_t)cfg->q_con_out) & 15) != 0))
-      return PACE_ERR_ARG;  // (16-byte rows, as the header says)
-    // ... of the winds: both or none, only with the four, only in a call that runs scalars and winds together
-    const int winds = (cfg->u_out != nullptr) + (cfg->v_out != nullptr);
-    if (winds == 1 || (winds && !given) || (winds && (cfg->u_out == u || cfg->v_out == v || cfg->u_out == cfg->v_out))) return PACE_ERR_ARG;
-    // (they are written by the kernel of phases 2 + 4 + 8 / 256; a call without 2 and 8 does not touch the winds' outputs)
-    if (winds && ((phases & 2) || (phases & 8)) && !((phases & 2) && (phases & 4) && (phases & 8))) return PACE_ERR_ARG;
-  }
-  return launch_d_sw(make_geo(geom), *met, col, cfg, workspace, delpc, delp, pt, u, v, w, uc, vc, ua, va, divgd, mfx, mfy,
-                     cx, cy, crx, cry, xfx, yfx, q_con, zh, heat_source, diss_est, dt, phases, S(stream));
+  // separate outputs: all four or none, none of them an input
+  const int given = (cfg->delp_out != nullptr) + (cfg->pt_out != nullptr) + (cfg->w_out != nullptr) + (cfg->q_con_out != nullptr);
+  if (given != 0 && given != 4) return PACE_ERR_ARG;
+  if (given && (cfg->delp_out == f.delp || cfg->pt_out == f.pt || cfg->w_out == f.w || cfg->q_con_out == f.q_con)) return PACE_ERR_ARG;
+  if (given && ((((uintptr_t)cfg->delp_out | (uintptr_t)cfg->pt_out | (uintptr_t)cfg->w_out | (uintptr_t)cfg->q_con_out) & 15) != 0))
+    return PACE_ERR_ARG;  // (16-byte rows, as the header says)
+  // ... of the winds: both or none, only with the four, only in a call that runs scalars and winds together
+  const int winds = (cfg->u_out != nullptr) + (cfg->v_out != nullptr);
+  if (winds == 1 || (winds && !given) || (winds && (cfg->u_out == f.u || cfg->v_out == f.v || cfg->u_out == cfg->v_out))) return PACE_ERR_ARG;
+  // (they are written by the kernel of phases 2 + 4 + 8 / 256; a call without 2 and 8 does not touch the winds' outputs)
+  if (winds && ((phases & 2) || (phases & 8)) && !((phases & 2) && (phases & 4) && (phases & 8))) return PACE_ERR_ARG;
+  return launch_d_sw(make_geo(geom), *met, col, cfg, workspace, phases, f, S(stream));
 }
 
+// the ABI signature of the d_sw entry points (include/pace_hip.h), and its field arguments as the bundle the launcher takes
 #define DSW_PARAMS                                                                                                        \
   const pace_geom_t *geom, const pace_metrics_t *met, const pace_column_t *col, const pace_dsw_config_t *cfg,            \
       void *workspace, real *delpc, real *delp, real *pt, real *u, real *v, real *w, real *uc, real *vc,  \
       const real *ua, const real *va, real *divgd, real *mfx, real *mfy, real *cx, real *cy, real *crx,   \
       real *cry, real *xfx, real *yfx, real *q_con, const real *zh, real *heat_source, real *diss_est,       \
       double dt, void *stream
-#define DSW_ARGS_                                                                                                          \
-  geom, met, col, cfg, workspace, delpc, delp, pt, u, v, w, uc, vc, ua, va, divgd, mfx, mfy, cx, cy, crx, cry, xfx, yfx,  \
-      q_con, zh, heat_source, diss_est, dt, stream
+#define DSW_FIELDS \
+  DswFields { delpc, delp, pt, u, v, w, uc, vc, ua, va, divgd, mfx, mfy, cx, cy, crx, cry, xfx, yfx, q_con, heat_source, diss_est, dt }
 
-int pace_d_sw(DSW_PARAMS) { return d_sw_entry(15, DSW_ARGS_); }
-int pace_d_sw_transport(DSW_PARAMS) { return d_sw_entry(3, DSW_ARGS_); }
-int pace_d_sw_winds(DSW_PARAMS) { return d_sw_entry(12, DSW_ARGS_); }
+int pace_d_sw(DSW_PARAMS) { return d_sw_entry(15, geom, met, col, cfg, workspace, DSW_FIELDS, stream); }
+int pace_d_sw_transport(DSW_PARAMS) { return d_sw_entry(3, geom, met, col, cfg, workspace, DSW_FIELDS, stream); }
+int pace_d_sw_winds(DSW_PARAMS) { return d_sw_entry(12, geom, met, col, cfg, workspace, DSW_FIELDS, stream); }
 int pace_d_sw_phases(int phases, DSW_PARAMS) {
   if (phases < 1 || phases > 256 || ((phases & 1) && (phases & 48)) || ((phases & 4) && (phases & 192)) || ((phases & 256) && phases != 256))
     return PACE_ERR_ARG;  // (1 and 16 / 32, 4 and 64 / 128 are alternatives; 256 stands alone)
-  return d_sw_entry(phases, DSW_ARGS_);
+  return d_sw_entry(phases, geom, met, col, cfg, workspace, DSW_FIELDS, stream);
 }
 
 // d_sw with its wind half on a second stream, in ONE call (the host layer used to make four calls and three event operations
@@ -216,10 +207,12 @@ int pace_d_sw_phases(int phases, DSW_PARAMS) {
 // started with phases 16).  Events: the caller's (e.g. torch.cuda.Event.cuda_event), recorded here; afterwards the caller makes
 // its stream wait for ev_done before it touches u, v, uc, vc, heat_source, diss_est, delpc or divgd (pace_amd ... d_sw.py join()).
 int pace_d_sw_overlapped(int prep, DSW_PARAMS, void* side_stream, void* ev_prep, void* ev_scalars, void* ev_done) {
+  const DswFields f = DSW_FIELDS;
+  const auto run = [&](int phases, void* on) { return d_sw_entry(phases, geom, met, col, cfg, workspace, f, on); };
 #ifdef PACE_EMU
   (void)side_stream; (void)ev_prep; (void)ev_scalars; (void)ev_done;
   if (prep != 1 && prep != 32) return PACE_ERR_ARG;
-  return d_sw_entry(prep | 14, DSW_ARGS_);
+  return run(prep | 14, stream);
 #else
   NEED(side_stream && ev_prep && ev_scalars && ev_done);
   if (prep != 1 && prep != 32) return PACE_ERR_ARG;
@@ -229,24 +222,16 @@ int pace_d_sw_overlapped(int prep, DSW_PARAMS, void* side_stream, void* ev_prep,
   if (geom && cfg && dsw_winds_in_scalars(make_geo(geom), cfg)) {
     // the winds are the last pass of the kernel that transports the scalars: one stream, nothing left for the side stream (the
     // kinetic energy there next to vorticity + divergence damping measured slower: profiles/r05_experiments x05)
-    if ((rc = d_sw_entry(prep | 14, DSW_ARGS_))) return rc;
-    if (hipEventRecord(e_done, main_s) != hipSuccess) return PACE_ERR_LAUNCH;
-    return PACE_OK;
+    if ((rc = run(prep | 14, stream))) return rc;
+    return hipEventRecord(e_done, main_s) != hipSuccess ? PACE_ERR_LAUNCH : PACE_OK;
   }
-  if ((rc = d_sw_entry(prep, DSW_ARGS_))) return rc;  // flux preparation on the caller's stream
+  if ((rc = run(prep, stream))) return rc;  // flux preparation on the caller's stream
   if (hipEventRecord(e_prep, main_s) != hipSuccess || hipStreamWaitEvent(side_s, e_prep, 0) != hipSuccess) return PACE_ERR_LAUNCH;
-  {
-    void* stream = side_stream;  // winds A next to the scalar transports
-    if ((rc = d_sw_entry(4, DSW_ARGS_))) return rc;
-  }
-  if ((rc = d_sw_entry(2, DSW_ARGS_))) return rc;  // the scalars on the caller's stream
+  if ((rc = run(4, side_stream))) return rc;  // winds A next to the scalar transports
+  if ((rc = run(2, stream))) return rc;       // the scalars on the caller's stream
   if (hipEventRecord(e_scal, main_s) != hipSuccess || hipStreamWaitEvent(side_s, e_scal, 0) != hipSuccess) return PACE_ERR_LAUNCH;
-  {
-    void* stream = side_stream;  // winds B (they need the new delp) next to whatever the caller launches next
-    if ((rc = d_sw_entry(8, DSW_ARGS_))) return rc;
-  }
-  if (hipEventRecord(e_done, side_s) != hipSuccess) return PACE_ERR_LAUNCH;
-  return PACE_OK;
+  if ((rc = run(8, side_stream))) return rc;  // winds B (they need the new delp) next to whatever the caller launches next
+  return hipEventRecord(e_done, side_s) != hipSuccess ? PACE_ERR_LAUNCH : PACE_OK;
 #endif
 }
 

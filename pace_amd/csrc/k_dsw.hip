@@ -59,15 +59,6 @@ k_corner_blocks_x(Geo g, real* __restrict__ f0, real* __restrict__ f1, real* __r
   p[IDX2(g, i, j)] = p[IDX2(g, si, sj_)];
 }
 
-bool dsw_pingpong_supported(const Geo& g, const pace_dsw_config_t* cfg) {
-  return cfg->hord_dp == cfg->hord_vt && cfg->hord_dp == cfg->hord_tm && transport_lean_covers(g, cfg->hord_dp);
-}
-// whether a whole-d_sw call runs the winds as the fifth pass of the scalar-phase kernel (then nothing of d_sw is left to overlap
-// with what follows it, and the winds can have outputs of their own)
-bool dsw_winds_in_scalars(const Geo& g, const pace_dsw_config_t* cfg) {
-  return dsw_pingpong_supported(g, cfg) && dsw_scalars_take_winds();
-}
-
 // apply_pt_delp_fluxes (d_sw.py:148-201) + adjust_w_and_qcon (:331-350), given the flux-form updates
 // pt*delp + F(pt), w*delp + F(w), q_con*delp + F(q_con) that the transport kernels' epilogues produced
 __global__ void __launch_bounds__(256)
@@ -1495,15 +1486,18 @@ int launch_divergence_damping(const Geo& g, const Met& m, const real* u, const r
 }
 
 struct DswWork {
-  real *ut, *vt, *fx, *fy, *gx, *gy, *fx2, *fy2, *dw, *heat_s, *ke, *wk, *abs_vort, *vort_b, *ut2, *vt2, *da, *db, *fyv, *umid, *vmid, *wtmp;
-  real* kcol;  // device copy of the column namelist: 12 arrays of (nk+1)
+  // (`unused`: nothing reads it; it keeps its slot, the byte position of every field is part of the workspace's layout)
+  real *ut, *vt, *fx, *fy, *gx, *gy, *fx2, *fy2, *dw, *heat_s, *ke, *wk, *unused, *vort_b, *ut2, *vt2, *da, *db, *fyv, *umid, *vmid, *wtmp;
+  real* kcol;  // device copy of the column namelist: DSWC_COUNT arrays of (nk + 1) (kernels.h DswColumn); room for DSW_COL_RESERVED
   int* ddh;    // the halo-state kernel's tables of this geometry (k_ddh_tables), or null where its LDS form does not apply
 };
 #define DSW_NFIELDS 22
+#define DSW_COL_RESERVED 16
+static_assert(DSWC_COUNT <= DSW_COL_RESERVED, "the column block outgrew its room in the workspace");
 
 int64_t dsw_workspace_bytes(const Geo& g) {
   const int64_t field = (int64_t)g.sk * (g.nk + 1) * (int64_t)sizeof(real);
-  return field * DSW_NFIELDS + 16 * (int64_t)(g.nk + 1) * (int64_t)sizeof(real) + 256 + (int64_t)sizeof(int) * DDH_TAB * DDH_SLOTS;
+  return field * DSW_NFIELDS + DSW_COL_RESERVED * (int64_t)(g.nk + 1) * (int64_t)sizeof(real) + 256 + (int64_t)sizeof(int) * DDH_TAB * DDH_SLOTS;
 }
 
 static DswWork carve(const Geo& g, void* ws) {
@@ -1513,37 +1507,74 @@ static DswWork carve(const Geo& g, void* ws) {
   real** f = &w.ut;
   for (int n = 0; n < DSW_NFIELDS; ++n) f[n] = p + (long)n * field;
   w.kcol = p + (long)DSW_NFIELDS * field;
-  // (behind the column block: 16 (nk + 1) elements + padding to 256 bytes)
-  char* after = (char*)(w.kcol + 16 * (long)(g.nk + 1));
+  // (behind the column block + padding to 256 bytes)
+  char* after = (char*)(w.kcol + DSW_COL_RESERVED * (long)(g.nk + 1));
   after += (256 - ((uintptr_t)after & 255)) & 255;
   w.ddh = (DdhBand(g, DDH_M).total <= DDH_SLOTS) ? (int*)after : nullptr;
   return w;
 }
 
-#ifdef PACE_EMU
-#include <cstring>
-static void upload(real* dst, const real* src, size_t n, hipStream_t) { memcpy(dst, src, n * sizeof(real)); }
-#else
-static void upload(real* dst, const real* src, size_t n, hipStream_t st) {
-  (void)hipMemcpyAsync(dst, src, n * sizeof(real), hipMemcpyHostToDevice, st);
-  (void)hipStreamSynchronize(st);
-}
-#endif
-
-#define NCOL 13
 // Upload the column namelist once per object (the reference derives these in __init__, d_sw.py:785,924-933).
 int dsw_prepare(const Geo& g, const pace_column_t* col, void* ws, hipStream_t st) {
   DswWork W = carve(g, ws);
   const int K = g.nk + 1;
-  std::vector<real> h((size_t)NCOL * K, (real)0.0);
-  const double* src[NCOL] = {col->nord_v, col->nord_w, col->nord_t, col->damp_vt, col->damp_w, col->damp_t, col->d2_divg,
-                             col->d_con,  col->ke_bg,  col->fac_vt, col->fac_t,   col->fac_vt_c, col->fac_w_c};
-  for (int a = 0; a < NCOL; ++a)
+  std::vector<real> h((size_t)DSWC_COUNT * K, (real)0.0);
+  // (DswColumn's order)
+  const double* src[DSWC_COUNT] = {col->nord_v, col->nord_w, col->nord_t, col->damp_vt, col->damp_w, col->damp_t, col->d2_divg,
+                                   col->d_con,  col->ke_bg,  col->fac_vt, col->fac_t,   col->fac_vt_c, col->fac_w_c};
+  for (int a = 0; a < DSWC_COUNT; ++a)
     for (int k = 0; k < g.nk; ++k) h[(size_t)a * K + k] = (real)src[a][k];
-  upload(W.kcol, h.data(), h.size(), st);
+#ifdef PACE_EMU
+  memcpy(W.kcol, h.data(), h.size() * sizeof(real));
+#else
+  (void)hipMemcpyAsync(W.kcol, h.data(), h.size() * sizeof(real), hipMemcpyHostToDevice, st);
+  (void)hipStreamSynchronize(st);
+#endif
   if (W.ddh != nullptr) hipLaunchKernelGGL(k_ddh_tables, dim3(1), dim3(DDH_NT), 0, st, g, W.ddh);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
+}
+
+// ---- the plan of one launch_d_sw call: every decision between its kernels, made once ----
+// Who gives separate wind outputs the halo of the inputs.  NOBODY: there are none, or this call does not write them.  FLUX_PREP: the
+// frame workgroups of the flux preparation take the copy along (kernels.h FxWindHalo).  OWN_LAUNCH: k_copy_wind_halo, behind the kinetic
+// energy -- this call runs the winds but not the flux preparation's frame.  EDGE_TILES: the fused kernel's, when it is launched alone
+// (phases 256).
+enum DswWindHalo { WIND_HALO_NOBODY, WIND_HALO_FLUX_PREP, WIND_HALO_OWN_LAUNCH, WIND_HALO_EDGE_TILES };
+// nmax_*: the column's highest damping orders.  kstart, nonzero_nord: the divergence damping's column is split at the first level with
+// nord > 0 (divergence_damping.py:307-331).  pingpong: the caller gave the four transported scalars outputs of their own
+// (pace_dsw_config_t).  lean_scalars: the fused scalar kernel (k_fvt.hip launch_dsw_scalars_lean) covers this tiling and these orders;
+// winds_in_scalars: ... and this call runs the winds as its fifth pass, the FUSED order of launch_d_sw.  skip_dead:
+// PACE_DSW_SKIP_DEAD_OUTPUTS.  ke_by_consumer: `ke += damped vorticity` is left to the fused kernel.
+struct DswPlan {
+  int nmax_v, nmax_w, nmax_t, kstart, nonzero_nord;
+  bool pingpong, lean_scalars, winds_in_scalars, skip_dead, ke_by_consumer;
+  DswWindHalo wind_halo;
+};
+
+// The scalars can have outputs of their own where ONE kernel transports them: the production tilings, one order for all transports.
+bool dsw_pingpong_supported(const Geo& g, const pace_dsw_config_t* cfg) {
+  return cfg->hord_dp == cfg->hord_vt && cfg->hord_dp == cfg->hord_tm && transport_lean_covers(g, cfg->hord_dp);
+}
+// whether a whole-d_sw call runs the winds as the fifth pass of the scalar-phase kernel (then nothing of d_sw is left to overlap
+// with what follows it, and the winds can have outputs of their own)
+bool dsw_winds_in_scalars(const Geo& g, const pace_dsw_config_t* cfg) {
+  return dsw_pingpong_supported(g, cfg) && dsw_scalars_take_winds();
+}
+static void dsw_max_orders(const Geo& g, const pace_column_t* col, DswPlan& p) {
+  p.nmax_v = p.nmax_w = p.nmax_t = 0;
+  for (int k = 0; k < g.nk; ++k) {
+    p.nmax_v = std::max(p.nmax_v, (int)col->nord_v[k]);
+    p.nmax_w = std::max(p.nmax_w, (int)col->nord_w[k]);
+    p.nmax_t = std::max(p.nmax_t, (int)col->nord_t[k]);
+  }
+}
+// the two queries above plus the condition on the column namelist they cannot see
+int dsw_outputs_supported(const Geo& g, const pace_column_t* col, const pace_dsw_config_t* cfg) {
+  DswPlan p;
+  dsw_max_orders(g, col, p);
+  if (!dsw_fused_takes_orders(p.nmax_v, p.nmax_w, p.nmax_t) || !dsw_pingpong_supported(g, cfg)) return 0;
+  return dsw_winds_in_scalars(g, cfg) ? 3 : 1;
 }
 
 // phases (bit mask): 1 = flux preparation (fxadv), 2 = transport of delp, w, q_con, pt (everything riem_solver3 /
@@ -1551,181 +1582,193 @@ int dsw_prepare(const Geo& g, const pace_column_t* col, void* ws, hipStream_t st
 // vorticity damping fluxes), 8 = winds B (dissipative heating, final u/v update).  15 = the whole of d_sw.
 // Dependencies: 2 and 4 need only 1 (and use disjoint workspace fields); 8 needs 2 and 4.  A caller may therefore run
 // 4 (then 8) on a second stream concurrently with 2 and with whatever follows d_sw on the first stream -- the vertical
-// solver -- see pace_amd/fv3core/stencils/d_sw.py.
-int launch_d_sw(const Geo& g, const Met& m, const pace_column_t* col, const pace_dsw_config_t* cfg, void* ws,
-                real* delpc, real* delp, real* pt, real* u, real* v, real* w, real* uc, real* vc,
-                const real* ua, const real* va, real* divgd, real* mfx, real* mfy, real* cx, real* cy,
-                real* crx, real* cry, real* xfx, real* yfx, real* q_con, const real* zh,
-                real* heat_source, real* diss_est, double dt, int phases, hipStream_t st) {
-  (void)zh;
-  // optional separate outputs of the four transported scalars (pace_dsw_config_t): delp, pt, w, q_con
-  real* scalar_outs[4] = {cfg->delp_out, cfg->pt_out, cfg->w_out, cfg->q_con_out};
-  const bool pingpong = scalar_outs[0] != nullptr;
-  if (pingpong && !dsw_pingpong_supported(g, cfg)) return PACE_ERR_UNSUPPORTED;
-  const int nk = g.nk;
-  DswWork W = carve(g, ws);
-  const int K = nk + 1;
-  real* kc = W.kcol;  // filled by dsw_prepare
-  real *d_nord_v = kc, *d_nord_w = kc + K, *d_nord_t = kc + 2 * K, *d_damp_vt_c = kc + 3 * K, *d_damp_w_c = kc + 4 * K,
-         *d_d2 = kc + 6 * K, *d_dcon = kc + 7 * K, *d_kebg = kc + 8 * K, *d_dampfac_vt = kc + 9 * K,
-         *d_dampfac_t = kc + 10 * K, *d_dampfac_vt_c = kc + 11 * K, *d_dampfac_w_c = kc + 12 * K;
-  int nmax_v = 0, nmax_w = 0, nmax_t = 0, kstart = 0, nonzero_nord = cfg->nord;
-  bool found = false;
-  for (int k = 0; k < nk; ++k) {
-    nmax_v = std::max(nmax_v, (int)col->nord_v[k]);
-    nmax_w = std::max(nmax_w, (int)col->nord_w[k]);
-    nmax_t = std::max(nmax_t, (int)col->nord_t[k]);
-    if (!found && col->nord[k] > 0) {
-      found = true;
-      kstart = k;
-      nonzero_nord = (int)col->nord[k];
-    }
-  }
-  int rc;
+// solver -- see pace_amd/fv3core/stencils/d_sw.py.  1 in two parts around a halo exchange: 16 = interior box, 32 = the rest; 4 in
+// two parts: 64 = kinetic energy + vorticity, 128 = the rest; 256, a measurement aid: the fused scalar + wind kernel ALONE, on
+// the kinetic energy / vorticity / damped vorticity a previous call left in the workspace.
+static int dsw_plan(const Geo& g, const pace_column_t* col, const pace_dsw_config_t* cfg, const DswWork& W, int phases, DswPlan& p) {
+  p.pingpong = cfg->delp_out != nullptr;
+  p.lean_scalars = dsw_pingpong_supported(g, cfg);
+  if (p.pingpong && !p.lean_scalars) return PACE_ERR_UNSUPPORTED;
+  dsw_max_orders(g, col, p);
+  p.kstart = 0, p.nonzero_nord = cfg->nord;
+  for (int k = g.nk - 1; k >= 0; --k)  // (downwards: what stays is the FIRST level with nord > 0)
+    if (col->nord[k] > 0) p.kstart = k, p.nonzero_nord = (int)col->nord[k];
   // Where the scalar-phase kernel can take the winds (the production tilings, one order for all transports, the 512-thread form)
   // and the call asks for scalars and winds together, the vorticity transport, the wind update and the dissipative heating are
   // the FIFTH PASS of that kernel (fvt_core.h): k_fvt<.., 0, 0> and k_heat_source, and the fields between them, disappear.
-  // The kinetic energy, the vorticity and the divergence damping then have to run BEFORE the scalars.
-  const bool lean_scalars = cfg->hord_dp == cfg->hord_vt && cfg->hord_dp == cfg->hord_tm && transport_lean_covers(g, cfg->hord_dp);
-  // (phases 256, a measurement aid: that kernel ALONE, on the kinetic energy / vorticity / damped vorticity a previous call left in
-  // the workspace)
-  const bool winds_in_scalars = lean_scalars && (((phases & 2) && (phases & 4) && (phases & 8)) || (phases & 256)) && dsw_scalars_take_winds() &&
-                                nmax_v <= 2 && nmax_w <= 2 && nmax_t <= 2 && ((uintptr_t)W.wk & 15) == 0;
+  // (16-byte rows of the relative vorticity: a condition on the workspace the caller handed over, known only here)
+  const bool whole = ((phases & 2) && (phases & 4) && (phases & 8)) || (phases & 256);
+  p.winds_in_scalars = whole && dsw_winds_in_scalars(g, cfg) && dsw_fused_takes_orders(p.nmax_v, p.nmax_w, p.nmax_t) && ((uintptr_t)W.wk & 15) == 0;
+  if ((phases & 256) && !p.winds_in_scalars) return PACE_ERR_UNSUPPORTED;
   // (separate wind outputs exist in that form only; a call that runs neither the scalars nor the heating does not touch them)
-  if ((cfg->u_out != nullptr) && !winds_in_scalars && (phases & (2 | 8))) return PACE_ERR_UNSUPPORTED;
-  const bool skip_dead = (cfg->flags & PACE_DSW_SKIP_DEAD_OUTPUTS) != 0;
+  if (cfg->u_out != nullptr && !p.winds_in_scalars && (phases & (2 | 8))) return PACE_ERR_UNSUPPORTED;
+  p.skip_dead = (cfg->flags & PACE_DSW_SKIP_DEAD_OUTPUTS) != 0;
   // ... and where the work fields are not asked for either, the divergence damping leaves `ke += damped vorticity` to that kernel
   // (it holds both at the tile's B-grid points): the damping then does not touch ke, 47 MB less, and it no longer depends on the
   // kinetic-energy kernel
-  const bool ke_by_consumer = winds_in_scalars && skip_dead && nk - kstart > 0;
-  // (separate wind outputs: the halo of the output buffers is a copy of the inputs' -- taken along by the flux preparation's frame
-  // workgroups when this call also runs the wind phase, else by a launch of its own below)
-  FxWindHalo wind_halo{u, v, cfg->u_out, cfg->v_out, false};
-  FxWindHalo* const wh = (winds_in_scalars && cfg->u_out != nullptr && (phases & (4 | 64))) ? &wind_halo : nullptr;
-  if (phases & 1) {
-  if ((rc = launch_fxadv(g, m, uc, vc, crx, cry, xfx, yfx, W.ut, W.vt, dt, cx, cy, st, 0, 0, wh))) return rc;
-  } else {  // the same in two parts around a halo exchange: 16 = interior box, 32 = the rest
-    if ((phases & 16) && (rc = launch_fxadv(g, m, uc, vc, crx, cry, xfx, yfx, W.ut, W.vt, dt, cx, cy, st, 1))) return rc;
-    if ((phases & 32) && (rc = launch_fxadv(g, m, uc, vc, crx, cry, xfx, yfx, W.ut, W.vt, dt, cx, cy, st, 2, 0, wh))) return rc;
+  p.ke_by_consumer = p.winds_in_scalars && p.skip_dead && g.nk - p.kstart > 0;
+  if (!p.winds_in_scalars || cfg->u_out == nullptr) p.wind_halo = WIND_HALO_NOBODY;
+  else if (!(phases & (4 | 64))) p.wind_halo = WIND_HALO_EDGE_TILES;
+  else p.wind_halo = (phases & (1 | 32)) ? WIND_HALO_FLUX_PREP : WIND_HALO_OWN_LAUNCH;
+  return PACE_OK;
+}
+
+// ---- one launch_d_sw call: its arguments, the carved workspace, the plan, and one member function per stage ----
+struct DswCall {
+  const Geo& g; const Met& m; const pace_dsw_config_t* cfg; const DswFields& f; hipStream_t st; DswWork W; DswPlan p;
+  const real* column(DswColumn slot) const { return dsw_column(W.kcol, g, slot); }
+
+  // flux preparation: part 0 = the whole, 1 = the interior box, 2 = the frame
+  int flux_preparation(int part) const {
+    FxWindHalo wh{f.u, f.v, cfg->u_out, cfg->v_out, false};
+    return launch_fxadv(g, m, f.uc, f.vc, f.crx, f.cry, f.xfx, f.yfx, W.ut, W.vt, f.dt, f.cx, f.cy, st, part, 0,
+                        (part != 1 && p.wind_halo == WIND_HALO_FLUX_PREP) ? &wh : nullptr);
   }
-  auto scalar_phase = [&]() -> int {
-    // The production tilings with one order for all four: ONE kernel (k_fvt.hip launch_dsw_scalars_lean) takes a tile through
-    // delp, w, q_con, pt and the division by the new delp; its results go to the caller's separate outputs, or to workspace
-    // fields that are copied back (the in-place contract of pace_d_sw).
-    bool fused = false;
-    if (lean_scalars) {
-      real* ws_outs[4] = {W.gx, W.fx2, W.wtmp, W.gy};
-      DswWinds wd{};
-      if (winds_in_scalars) {
-        wd.rel_vort = W.wk, wd.u = u, wd.v = v, wd.ke = W.ke, wd.vort_b = W.vort_b, wd.heat_source = heat_source;
-        wd.u_out = cfg->u_out ? cfg->u_out : W.umid, wd.v_out = cfg->v_out ? cfg->v_out : W.vmid;
-        // (the halo of separate wind outputs: copied by k_copy_wind_halo when this call runs the wind phase, by the kernel's edge tiles when the
-        // kernel is launched alone -- phases 256, a measurement aid)
-        wd.copy_halo = cfg->u_out != nullptr && !(phases & (4 | 64)), wd.do_skeb = cfg->do_skeb, wd.d_con = cfg->d_con;
-        wd.ke_plus_vort = ke_by_consumer;
-      }
-      rc = launch_dsw_scalars_lean(g, m, delp, pt, w, q_con, pingpong ? scalar_outs : ws_outs, crx, cry, xfx, yfx, mfx, mfy, W.dw,
-                                   W.heat_s, diss_est, kc, cfg->hord_dp, nmax_v, nmax_w, nmax_t, dt, st, winds_in_scalars ? &wd : nullptr);
-      if (rc == PACE_OK) {
-        fused = true;
-        if (!pingpong) hipLaunchKernelGGL(k_copy_scalars, patch_grid(g, nk), PATCH_BLOCK, 0, st, g, delp, pt, w, q_con, W.gx, W.fx2, W.wtmp, W.gy);
-        if (winds_in_scalars && !cfg->u_out) hipLaunchKernelGGL(k_copy_winds, patch_grid(g, nk), PATCH_BLOCK, 0, st, g, u, v, W.umid, W.vmid);
-      } else if (rc != PACE_ERR_UNSUPPORTED || winds_in_scalars) {
-        return rc;
-      }
-    }
-    if (!fused) {
-    if (pingpong) return PACE_ERR_UNSUPPORTED;
-    const int nl = nk;
+
+  // the full contract: the corner blocks of the four scalars as the transport's in-place corner copies leave them
+  // (separate outputs: the scalar-phase kernel's corner tiles have written them with the halo, fvt_core.h place_footprint)
+  void corner_blocks() const {
+    if (!p.skip_dead && !p.pingpong) hipLaunchKernelGGL(k_corner_blocks_x, dim3((unsigned)g.nk), dim3(256), 0, st, g, f.delp, f.pt, f.w, f.q_con);
+  }
+
+  // The production tilings with one order for all four: ONE kernel (k_fvt.hip launch_dsw_scalars_lean) takes a tile through
+  // delp, w, q_con, pt and the division by the new delp -- and, in the fused order, through the winds; its results go to the
+  // caller's separate outputs, or to workspace fields that are copied back (the in-place contract of pace_d_sw).
+  // PACE_ERR_UNSUPPORTED (nothing launched): the kernel does not take these pointers.
+  int fused_scalars() const {
+    real* ws_outs[4] = {W.gx, W.fx2, W.wtmp, W.gy};
+    real* scalar_outs[4] = {cfg->delp_out, cfg->pt_out, cfg->w_out, cfg->q_con_out};
+    DswWinds wd{};  // (handed over in the fused order only)
+    wd.rel_vort = W.wk, wd.u = f.u, wd.v = f.v, wd.ke = W.ke, wd.vort_b = W.vort_b, wd.heat_source = f.heat_source;
+    wd.u_out = cfg->u_out ? cfg->u_out : W.umid, wd.v_out = cfg->v_out ? cfg->v_out : W.vmid;
+    wd.copy_halo = p.wind_halo == WIND_HALO_EDGE_TILES, wd.do_skeb = cfg->do_skeb, wd.d_con = cfg->d_con;
+    wd.ke_plus_vort = p.ke_by_consumer;
+    const int rc = launch_dsw_scalars_lean(g, m, f, p.pingpong ? scalar_outs : ws_outs, W.dw, W.heat_s, W.kcol, cfg->hord_dp, p.nmax_v, p.nmax_w,
+                                           p.nmax_t, st, p.winds_in_scalars ? &wd : nullptr);
+    if (rc) return rc;
+    if (!p.pingpong) hipLaunchKernelGGL(k_copy_scalars, patch_grid(g, g.nk), PATCH_BLOCK, 0, st, g, f.delp, f.pt, f.w, f.q_con, W.gx, W.fx2, W.wtmp, W.gy);
+    if (p.winds_in_scalars && !cfg->u_out) hipLaunchKernelGGL(k_copy_winds, patch_grid(g, g.nk), PATCH_BLOCK, 0, st, g, f.u, f.v, W.umid, W.vmid);
+    corner_blocks();
+    return PACE_OK;
+  }
+
+  // The scalars one by one (the general tilings, mixed orders): the transport kernels' epilogues leave the flux-form updates in
+  // workspace fields, k_finish_scalars divides by the new delp.
+  int general_scalars() const {
+    if (p.pingpong) return PACE_ERR_UNSUPPORTED;
+    int rc;
     FvDamp dp{};
     // delp: transport + del-n damping of the mass fluxes -> fx, fy
-    dp.damp_k = d_dampfac_vt; dp.nord_k = d_nord_v; dp.nmax = nmax_v; dp.mass_given = 0;
-    dp.accx = mfx; dp.accy = mfy;  // flux_capacitor (d_sw.py:33-60); its Courant-number half sits in fxadv
-    if ((rc = launch_transport(g, m, delp, crx, cry, xfx, yfx, W.fx, W.fy, nullptr, nullptr, cfg->hord_dp, nl, 1, 0, dp, st))) return rc;
+    dp.damp_k = column(DSWC_FAC_VT); dp.nord_k = column(DSWC_NORD_V); dp.nmax = p.nmax_v; dp.mass_given = 0;
+    dp.accx = f.mfx; dp.accy = f.mfy;  // flux_capacitor (d_sw.py:33-60); its Courant-number half sits in fxadv
+    if ((rc = launch_transport(g, m, f.delp, f.crx, f.cry, f.xfx, f.yfx, W.fx, W.fy, nullptr, nullptr, cfg->hord_dp, g.nk, 1, 0, dp, st))) return rc;
     // w: transport with the mass fluxes, del-n damping fluxes -> heat_diss, flux-form update -> W.gx (= w*delp + F(w))
     dp = FvDamp{};
-    dp.damp_k = d_dampfac_w_c; dp.nord_k = d_nord_w; dp.nmax = nmax_w; dp.mass_given = 0;
-    dp.qout = W.gx; dp.amass = delp; dp.dw = W.dw; dp.heat_s = W.heat_s; dp.diss_est = diss_est;
-    dp.damp_w_k = d_damp_w_c; dp.ke_bg_k = d_kebg; dp.dt = dt;
+    dp.damp_k = column(DSWC_FAC_W_C); dp.nord_k = column(DSWC_NORD_W); dp.nmax = p.nmax_w; dp.mass_given = 0;
+    dp.qout = W.gx; dp.amass = f.delp; dp.dw = W.dw; dp.heat_s = W.heat_s; dp.diss_est = f.diss_est;
+    dp.damp_w_k = column(DSWC_DAMP_W); dp.ke_bg_k = column(DSWC_KE_BG); dp.dt = f.dt;
     const FvDamp dpw = dp;
     // q_con -> W.gy
     dp = FvDamp{};
-    dp.damp_k = d_dampfac_t; dp.nord_k = d_nord_t; dp.nmax = nmax_t; dp.mass_given = 1; dp.mass = delp;
-    dp.qout = W.gy; dp.amass = delp;
+    dp.damp_k = column(DSWC_FAC_T); dp.nord_k = column(DSWC_NORD_T); dp.nmax = p.nmax_t; dp.mass_given = 1; dp.mass = f.delp;
+    dp.qout = W.gy; dp.amass = f.delp;
     // pt -> W.fx2
     FvDamp dp2 = dp;
-    dp2.damp_k = d_dampfac_vt; dp2.nord_k = d_nord_v; dp2.nmax = nmax_v; dp2.qout = W.fx2;
+    dp2.damp_k = column(DSWC_FAC_VT); dp2.nord_k = column(DSWC_NORD_V); dp2.nmax = p.nmax_v; dp2.qout = W.fx2;
     // General tilings with ord 6 for all three: ONE launch (k_fvtp2d_scalars3: a grid three tile planes high)
-    bool done3 = false;
-    if (!transport_lean_covers(g, 6) && cfg->hord_vt == 6 && cfg->hord_dp == 6 && cfg->hord_tm == 6) {
-      rc = launch_transport_scalars3(g, m, w, q_con, pt, crx, cry, xfx, yfx, W.fx, W.fy, nl, dpw, dp, dp2, st);
-      if (rc == PACE_OK) done3 = true;
-      else if (rc != PACE_ERR_UNSUPPORTED) return rc;
+    rc = PACE_ERR_UNSUPPORTED;
+    if (!p.lean_scalars && cfg->hord_vt == 6 && cfg->hord_dp == 6 && cfg->hord_tm == 6) {
+      rc = launch_transport_scalars3(g, m, f.w, f.q_con, f.pt, f.crx, f.cry, f.xfx, f.yfx, W.fx, W.fy, g.nk, dpw, dp, dp2, st);
+      if (rc != PACE_OK && rc != PACE_ERR_UNSUPPORTED) return rc;
     }
-    if (!done3) {
-      if ((rc = launch_transport(g, m, w, crx, cry, xfx, yfx, nullptr, nullptr, W.fx, W.fy, cfg->hord_vt, nl, 0, 2, dpw, st))) return rc;
-      if ((rc = launch_transport(g, m, q_con, crx, cry, xfx, yfx, nullptr, nullptr, W.fx, W.fy, cfg->hord_dp, nl, 2, 1, dp, st))) return rc;
-      if ((rc = launch_transport(g, m, pt, crx, cry, xfx, yfx, nullptr, nullptr, W.fx, W.fy, cfg->hord_tm, nl, 2, 1, dp2, st))) return rc;
+    if (rc != PACE_OK) {
+      if ((rc = launch_transport(g, m, f.w, f.crx, f.cry, f.xfx, f.yfx, nullptr, nullptr, W.fx, W.fy, cfg->hord_vt, g.nk, 0, 2, dpw, st))) return rc;
+      if ((rc = launch_transport(g, m, f.q_con, f.crx, f.cry, f.xfx, f.yfx, nullptr, nullptr, W.fx, W.fy, cfg->hord_dp, g.nk, 2, 1, dp, st))) return rc;
+      if ((rc = launch_transport(g, m, f.pt, f.crx, f.cry, f.xfx, f.yfx, nullptr, nullptr, W.fx, W.fy, cfg->hord_tm, g.nk, 2, 1, dp2, st))) return rc;
     }
-    hipLaunchKernelGGL(k_finish_scalars, patch_grid(g, nk), PATCH_BLOCK, 0, st, g, m, pt, delp, w, q_con, W.fx2, W.gx, W.gy, W.fx, W.fy, W.dw, d_damp_w_c);
-    }
-    // the full contract: the corner blocks of the four scalars as the transport's in-place corner copies leave them
-    // (separate outputs: the scalar-phase kernel's corner tiles have written them with the halo, fvt_core.h place_footprint)
-    if (!skip_dead && !pingpong) hipLaunchKernelGGL(k_corner_blocks_x, dim3((unsigned)nk), dim3(256), 0, st, g, delp, pt, w, q_con);
+    hipLaunchKernelGGL(k_finish_scalars, patch_grid(g, g.nk), PATCH_BLOCK, 0, st, g, m, f.pt, f.delp, f.w, f.q_con, W.fx2, W.gx, W.gy, W.fx, W.fy,
+                       W.dw, column(DSWC_DAMP_W));
+    corner_blocks();
     return PACE_OK;
-  };
-  if ((phases & 2) && !winds_in_scalars && (rc = scalar_phase())) return rc;
-  if (phases & (4 | 64)) {
+  }
+
   // winds A1: kinetic energy and relative vorticity (need only the flux preparation), two kinds of workgroups of one launch
   // (the vorticity inside the kinetic-energy point function: no faster, x02; both from LDS tiles of u and v: twice as slow, x06 --
   // profiles/r05_experiments)
-  const Regions rke = (g.n >= 8) ? bgrid_regions(g, 3) : a2b_regions(g);
-  if (cfg->hord_mt != 5 && cfg->hord_mt != 6) return PACE_ERR_UNSUPPORTED;
-  const int nbr = rke.first[rke.n];
-  const dim3 pg = patch_grid(g, 1);
-  const unsigned nbl = (unsigned)nbr + pg.x * pg.y;
-  const char* ke_ch_env = getenv("PACE_KE_LEVELS");  // (read per call; a test lever: 1 or 2 levels per thread)
-  const int ke_ch = ke_ch_env ? (ke_ch_env[0] == '2' ? 2 : 1) : (nbl * (unsigned)nk >= KE_CH2_MIN_WGS ? 2 : 1);
-#define KE_GO(MORD, CH)                                                                                                                   \
-  hipLaunchKernelGGL((k_ke_vorticity<MORD, CH>), dim3(nbl, 1, (unsigned)((nk + CH - 1) / CH)), dim3(64, 4), 0, st, g, m, uc, vc, u, v, W.ut, W.vt, \
-                     W.ke, dt, rke, W.wk, nbr)
-  if (cfg->hord_mt == 5) {
-    if (ke_ch == 2) KE_GO(5, 2); else KE_GO(5, 1);
-  } else {
-    if (ke_ch == 2) KE_GO(6, 2); else KE_GO(6, 1);
-  }
+  int ke_vorticity() const {
+    const int nk = g.nk;
+    const Regions rke = (g.n >= 8) ? bgrid_regions(g, 3) : a2b_regions(g);
+    if (cfg->hord_mt != 5 && cfg->hord_mt != 6) return PACE_ERR_UNSUPPORTED;
+    const int nbr = rke.first[rke.n];
+    const dim3 pg = patch_grid(g, 1);
+    const unsigned nbl = (unsigned)nbr + pg.x * pg.y;
+    const char* ke_ch_env = getenv("PACE_KE_LEVELS");  // (read per call; a test lever: 1 or 2 levels per thread)
+    const int ke_ch = ke_ch_env ? (ke_ch_env[0] == '2' ? 2 : 1) : (nbl * (unsigned)nk >= KE_CH2_MIN_WGS ? 2 : 1);
+#define KE_GO(MORD, CH)                                                                                                                     \
+  hipLaunchKernelGGL((k_ke_vorticity<MORD, CH>), dim3(nbl, 1, (unsigned)((nk + CH - 1) / CH)), dim3(64, 4), 0, st, g, m, f.uc, f.vc, f.u, f.v, \
+                     W.ut, W.vt, W.ke, f.dt, rke, W.wk, nbr)
+    if (cfg->hord_mt == 5) {
+      if (ke_ch == 2) KE_GO(5, 2); else KE_GO(5, 1);
+    } else {
+      if (ke_ch == 2) KE_GO(6, 2); else KE_GO(6, 1);
+    }
 #undef KE_GO
-  // (with separate wind outputs the halo of the output buffers is copied here, by a launch of its own over the frame of the plane)
-  if (winds_in_scalars && cfg->u_out != nullptr && !wind_halo.done) {
-    const int frame = wind_halo_points(g);
-    hipLaunchKernelGGL(k_copy_wind_halo, dim3((unsigned)((frame + 255) / 256), (unsigned)nk), dim3(256), 0, st, g, u, v, cfg->u_out, cfg->v_out);
+    if (p.wind_halo == WIND_HALO_OWN_LAUNCH)  // over the frame of the plane
+      hipLaunchKernelGGL(k_copy_wind_halo, dim3((unsigned)((wind_halo_points(g) + 255) / 256), (unsigned)nk), dim3(256), 0, st, g, f.u, f.v,
+                         cfg->u_out, cfg->v_out);
+    return PACE_OK;
   }
-  }
-  if (phases & (4 | 128)) {
-  // winds A2: divergence damping
-  if (nonzero_nord < 0 || nonzero_nord > 3) return PACE_ERR_UNSUPPORTED;  // (as pace_divergence_damping: halo 3)
-  if ((rc = launch_divergence_damping(g, m, u, v, va, W.vort_b, ua, divgd, vc, uc, delpc, W.ke, W.wk, dt, d_d2, kstart, nonzero_nord,
-                                      cfg->dddmp, cfg->d4_bg, W.da, W.db, st, skip_dead, ke_by_consumer, W.ddh)))
-    return rc;
-  // vorticity transport
-  // vorticity: transport of the absolute vorticity (wk + fC_agrid) -> W.fy2, W.fyv (own flux buffers: the mass fluxes
-  // in W.fx / W.fy may still be in use by phase 2 on another stream) and the del-n damping fluxes of the relative
-  // vorticity -> ut2, vt2 (DelnFluxNoSG, d_sw.py:1187-1195), one kernel
-  if (!winds_in_scalars) {
+
+  // winds A2: divergence damping, then (the split order) the vorticity transport
+  int damping_and_vorticity_transport() const {
+    if (p.nonzero_nord < 0 || p.nonzero_nord > 3) return PACE_ERR_UNSUPPORTED;  // (as pace_divergence_damping: halo 3)
+    const int rc = launch_divergence_damping(g, m, f.u, f.v, f.va, W.vort_b, f.ua, f.divgd, f.vc, f.uc, f.delpc, W.ke, W.wk, f.dt,
+                                             column(DSWC_D2_DIVG), p.kstart, p.nonzero_nord, cfg->dddmp, cfg->d4_bg, W.da, W.db, st, p.skip_dead,
+                                             p.ke_by_consumer, W.ddh);
+    if (rc || p.winds_in_scalars) return rc;
+    // vorticity: transport of the absolute vorticity (wk + fC_agrid) -> W.fy2, W.fyv (own flux buffers: the mass fluxes
+    // in W.fx / W.fy may still be in use by phase 2 on another stream) and the del-n damping fluxes of the relative
+    // vorticity -> ut2, vt2 (DelnFluxNoSG, d_sw.py:1187-1195), one kernel
     FvDamp dp{};
-    dp.damp_k = d_dampfac_vt_c; dp.nord_k = d_nord_v; dp.nmax = nmax_v; dp.mass_given = 0;
+    dp.damp_k = column(DSWC_FAC_VT_C); dp.nord_k = column(DSWC_NORD_V); dp.nmax = p.nmax_v; dp.mass_given = 0;
     dp.fx2o = W.ut2; dp.fy2o = W.vt2; dp.add2d = m.fC_agrid;
     // ... and u_and_v_from_ke finished in the kernel's store phase: the vorticity fluxes never reach memory
-    dp.u_upd = u; dp.v_upd = v; dp.ke = W.ke;
+    dp.u_upd = f.u; dp.v_upd = f.v; dp.ke = W.ke;
     dp.u_out = W.umid; dp.v_out = W.vmid;  // (read by k_heat_source, which writes the final winds to u, v)
-    if ((rc = launch_transport(g, m, W.wk, crx, cry, xfx, yfx, W.fy2, W.fyv, nullptr, nullptr, cfg->hord_vt, nk, 0, 0, dp, st))) return rc;
+    return launch_transport(g, m, W.wk, f.crx, f.cry, f.xfx, f.yfx, W.fy2, W.fyv, nullptr, nullptr, cfg->hord_vt, g.nk, 0, 0, dp, st);
   }
+
+  // winds B: dissipative heating and the final winds, from the intermediate winds the vorticity transport left in the workspace
+  void heating() const {
+    hipLaunchKernelGGL(k_heat_source, patch_grid(g, g.nk), PATCH_BLOCK, 0, st, g, m, W.umid, W.vmid, W.vort_b, W.ut2, W.vt2,
+                       p.pingpong ? cfg->delp_out : f.delp, W.heat_s, f.heat_source, f.diss_est, column(DSWC_D_CON), cfg->d_con, cfg->do_skeb, f.u,
+                       f.v, column(DSWC_DAMP_VT));
   }
-  if ((phases & 256) && !winds_in_scalars) return PACE_ERR_UNSUPPORTED;
-  if (winds_in_scalars && (rc = scalar_phase())) return rc;  // scalars + winds, after the kinetic energy and the divergence damping
-  if ((phases & 8) && !winds_in_scalars) {
-  hipLaunchKernelGGL(k_heat_source, patch_grid(g, nk), PATCH_BLOCK, 0, st, g, m, W.umid, W.vmid, W.vort_b, W.ut2, W.vt2, pingpong ? scalar_outs[0] : delp, W.heat_s, heat_source,
-                     diss_est, d_dcon, cfg->d_con, cfg->do_skeb, u, v, d_damp_vt_c);
+};
+
+int launch_d_sw(const Geo& g, const Met& m, const pace_column_t* col, const pace_dsw_config_t* cfg, void* ws, int phases, const DswFields& f,
+                hipStream_t st) {
+  DswCall c{g, m, cfg, f, st, carve(g, ws), DswPlan{}};
+  int rc;
+  if ((rc = dsw_plan(g, col, cfg, c.W, phases, c.p))) return rc;
+  if ((phases & 1) && (rc = c.flux_preparation(0))) return rc;
+  if ((phases & 16) && (rc = c.flux_preparation(1))) return rc;  // (the same in two parts around a halo exchange)
+  if ((phases & 32) && (rc = c.flux_preparation(2))) return rc;
+  if (c.p.winds_in_scalars) {
+    // the fused order: the kinetic energy, the vorticity and the divergence damping have to run BEFORE the kernel that takes the
+    // scalars and the winds (phases 256: that kernel alone)
+    if ((phases & 4) && ((rc = c.ke_vorticity()) || (rc = c.damping_and_vorticity_transport()))) return rc;
+    if ((rc = c.fused_scalars())) return rc;
+  } else {
+    // the split order: scalars, winds A, winds B, each where the mask asks for it
+    if (phases & 2) {
+      rc = c.p.lean_scalars ? c.fused_scalars() : PACE_ERR_UNSUPPORTED;
+      if (rc == PACE_ERR_UNSUPPORTED) rc = c.general_scalars();
+      if (rc) return rc;
+    }
+    if ((phases & (4 | 64)) && (rc = c.ke_vorticity())) return rc;
+    if ((phases & (4 | 128)) && (rc = c.damping_and_vorticity_transport())) return rc;
+    if (phases & 8) c.heating();
   }
   PACE_CHECK_LAUNCH();
   return PACE_OK;

@@ -134,7 +134,7 @@ int FVT_FN(launch_transport)(const Geo& g, const Met& m, const real* q, const re
 }
 
 // The scalar phase of d_sw (delp, w, q_con, pt) in one launch; see fvt_core.h.  kc: the device column block of dsw_prepare
-// (NCOL arrays of nk + 1).  outs[4] = delp, pt, w, q_con outputs, distinct from the inputs.  PACE_ERR_UNSUPPORTED if the geometry /
+// (kernels.h DswColumn).  outs[4] = delp, pt, w, q_con outputs, distinct from the inputs.  PACE_ERR_UNSUPPORTED if the geometry /
 // orders are not covered (the caller then runs the scalars one by one).
 // whether the scalar-phase kernel can take the winds as its fifth pass (the 512-thread form)
 bool FVT_FN(take_winds)() {
@@ -145,39 +145,35 @@ bool FVT_FN(take_winds)() {
 #endif
 }
 
-int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const real* delp, const real* pt, const real* w, const real* q_con,
-                           real* const* outs, const real* crx, const real* cry, const real* xfx, const real* yfx, real* mfx,
-                           real* mfy, real* dw, real* heat_s, real* diss_est, const real* kc, int hord, int nmax_v, int nmax_w,
-                           int nmax_t, double dt, hipStream_t st, const DswWinds* winds) {
+int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const DswFields& f, real* const* outs, real* dw, real* heat_s, const real* kc, int hord,
+                           int nmax_v, int nmax_w, int nmax_t, hipStream_t st, const DswWinds* winds) {
 #if FVT_AVAILABLE
-  if (!FVT_FN(covers)(g, hord) || nmax_v > 2 || nmax_w > 2 || nmax_t > 2) return PACE_ERR_UNSUPPORTED;
+  if (!FVT_FN(covers)(g, hord) || !dsw_fused_takes_orders(nmax_v, nmax_w, nmax_t)) return PACE_ERR_UNSUPPORTED;
   if (winds && !FVT_FN(take_winds)()) return PACE_ERR_UNSUPPORTED;
-  const real* ins[4] = {delp, pt, w, q_con};
+  const real* ins[4] = {f.delp, f.pt, f.w, f.q_con};
   for (int n = 0; n < 4; ++n)
     if (((uintptr_t)ins[n] & 15) != 0 || outs[n] == nullptr || outs[n] == ins[n]) return PACE_ERR_UNSUPPORTED;
-  const int K = g.nk + 1;
   FvtScalars S{};
-  // (the order of dsw_prepare: nord_v, nord_w, nord_t, damp_vt, damp_w, damp_t, d2_divg, d_con, ke_bg, fac_vt, fac_t, fac_vt_c, fac_w_c)
-  const real *nord_v = kc, *nord_w = kc + K, *nord_t = kc + 2 * K, *fac_vt = kc + 9 * K, *fac_t = kc + 10 * K, *fac_w = kc + 12 * K;
+  const auto column = [&](DswColumn slot) { return dsw_column(kc, g, slot); };
   // delp, w, q_con, pt
-  S.q[0] = delp, S.q[1] = w, S.q[2] = q_con, S.q[3] = pt;
+  S.q[0] = f.delp, S.q[1] = f.w, S.q[2] = f.q_con, S.q[3] = f.pt;
   S.qout[0] = outs[0], S.qout[1] = outs[2], S.qout[2] = outs[3], S.qout[3] = outs[1];
-  S.fac[0] = fac_vt, S.fac[1] = fac_w, S.fac[2] = fac_t, S.fac[3] = fac_vt;
-  S.nord[0] = nord_v, S.nord[1] = nord_w, S.nord[2] = nord_t, S.nord[3] = nord_v;
+  S.fac[0] = column(DSWC_FAC_VT), S.fac[1] = column(DSWC_FAC_W_C), S.fac[2] = column(DSWC_FAC_T), S.fac[3] = S.fac[0];
+  S.nord[0] = column(DSWC_NORD_V), S.nord[1] = column(DSWC_NORD_W), S.nord[2] = column(DSWC_NORD_T), S.nord[3] = S.nord[0];
   S.nmax[0] = nmax_v, S.nmax[1] = nmax_w, S.nmax[2] = nmax_t, S.nmax[3] = nmax_v;
-  S.crx = crx, S.cry = cry, S.xfx = xfx, S.yfx = yfx, S.mfx = mfx, S.mfy = mfy, S.dw = dw, S.heat_s = heat_s,
-  S.diss_est = diss_est;
-  S.damp_w = kc + 4 * K, S.ke_bg = kc + 8 * K;
-  S.dt = dt;
+  S.crx = f.crx, S.cry = f.cry, S.xfx = f.xfx, S.yfx = f.yfx, S.mfx = f.mfx, S.mfy = f.mfy, S.dw = dw, S.heat_s = heat_s,
+  S.diss_est = f.diss_est;
+  S.damp_w = column(DSWC_DAMP_W), S.ke_bg = column(DSWC_KE_BG);
+  S.dt = f.dt;
   if (winds) {
     // the relative vorticity: DelnFluxNoSG with nord_v and (damp_vt * da_min_c) ^ (nord_v + 1) (d_sw.py:1187-1195)
     if (((uintptr_t)winds->rel_vort & 15) != 0 || winds->u_out == winds->u || winds->v_out == winds->v) return PACE_ERR_UNSUPPORTED;
     S.winds = 1;
-    S.q[4] = winds->rel_vort, S.fac[4] = kc + 11 * K, S.nord[4] = nord_v, S.nmax[4] = nmax_v;
+    S.q[4] = winds->rel_vort, S.fac[4] = column(DSWC_FAC_VT_C), S.nord[4] = S.nord[0], S.nmax[4] = nmax_v;
     S.u = winds->u, S.v = winds->v, S.u_out = winds->u_out, S.v_out = winds->v_out, S.ke = winds->ke, S.vort_b = winds->vort_b;
     S.heat_source = winds->heat_source, S.do_skeb = winds->do_skeb, S.d_con = winds->d_con, S.copy_wind_halo = winds->copy_halo;
     S.ke_plus_vort = winds->ke_plus_vort;
-    S.damp_vt = kc + 3 * K, S.d_con_k = kc + 7 * K;
+    S.damp_vt = column(DSWC_DAMP_VT), S.d_con_k = column(DSWC_D_CON);
     S.fC = m.fC_agrid, S.rdx = m.rdx, S.rdy = m.rdy, S.rsin2 = m.rsin2, S.cosa_s = m.cosa_s;
   }
   const dim3 grid(g.n / TI, g.n / TJ, g.nk);
@@ -197,10 +193,8 @@ bool fvt16_take_winds();
 int fvt16_launch_transport(const Geo& g, const Met& m, const real* q, const real* crx, const real* cry, const real* xfx, const real* yfx,
                            real* fx, real* fy, const real* xu, const real* yu, int hord, int nlev, int dmode, int epi, const FvDamp& dp,
                            hipStream_t st);
-int fvt16_launch_scalars(const Geo& g, const Met& m, const real* delp, const real* pt, const real* w, const real* q_con, real* const* outs,
-                         const real* crx, const real* cry, const real* xfx, const real* yfx, real* mfx, real* mfy, real* dw, real* heat_s,
-                         real* diss_est, const real* kc, int hord, int nmax_v, int nmax_w, int nmax_t, double dt, hipStream_t st,
-                         const DswWinds* winds);
+int fvt16_launch_scalars(const Geo& g, const Met& m, const DswFields& f, real* const* outs, real* dw, real* heat_s, const real* kc, int hord,
+                         int nmax_v, int nmax_w, int nmax_t, hipStream_t st, const DswWinds* winds);
 
 bool transport_lean_covers(const Geo& g, int hord) { return fvt32_covers(g, hord) || fvt16_covers(g, hord); }
 bool dsw_scalars_take_winds() { return fvt32_take_winds(); }  // (both shapes are compiled from the same source with the same form)
@@ -210,14 +204,9 @@ int launch_transport_lean(const Geo& g, const Met& m, const real* q, const real*
   if (fvt32_covers(g, hord)) return fvt32_launch_transport(g, m, q, crx, cry, xfx, yfx, fx, fy, xu, yu, hord, nlev, dmode, epi, dp, st);
   return fvt16_launch_transport(g, m, q, crx, cry, xfx, yfx, fx, fy, xu, yu, hord, nlev, dmode, epi, dp, st);
 }
-int launch_dsw_scalars_lean(const Geo& g, const Met& m, const real* delp, const real* pt, const real* w, const real* q_con,
-                            real* const* outs, const real* crx, const real* cry, const real* xfx, const real* yfx, real* mfx,
-                            real* mfy, real* dw, real* heat_s, real* diss_est, const real* kc, int hord, int nmax_v, int nmax_w,
-                            int nmax_t, double dt, hipStream_t st, const DswWinds* winds) {
-  if (fvt32_covers(g, hord))
-    return fvt32_launch_scalars(g, m, delp, pt, w, q_con, outs, crx, cry, xfx, yfx, mfx, mfy, dw, heat_s, diss_est, kc, hord, nmax_v, nmax_w,
-                                nmax_t, dt, st, winds);
-  return fvt16_launch_scalars(g, m, delp, pt, w, q_con, outs, crx, cry, xfx, yfx, mfx, mfy, dw, heat_s, diss_est, kc, hord, nmax_v, nmax_w,
-                              nmax_t, dt, st, winds);
+int launch_dsw_scalars_lean(const Geo& g, const Met& m, const DswFields& f, real* const* outs, real* dw, real* heat_s, const real* kc, int hord,
+                            int nmax_v, int nmax_w, int nmax_t, hipStream_t st, const DswWinds* winds) {
+  if (fvt32_covers(g, hord)) return fvt32_launch_scalars(g, m, f, outs, dw, heat_s, kc, hord, nmax_v, nmax_w, nmax_t, st, winds);
+  return fvt16_launch_scalars(g, m, f, outs, dw, heat_s, kc, hord, nmax_v, nmax_w, nmax_t, st, winds);
 }
 #endif

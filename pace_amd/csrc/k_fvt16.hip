@@ -16,8 +16,7 @@ int fvt16_launch_transport(const Geo&, const Met&, const real*, const real*, con
                            const real*, int, int, int, int, const FvDamp&, hipStream_t) {
   return PACE_ERR_UNSUPPORTED;
 }
-int fvt16_launch_scalars(const Geo&, const Met&, const real*, const real*, const real*, const real*, real* const*, const real*, const real*,
-                         const real*, const real*, real*, real*, real*, real*, real*, const real*, int, int, int, int, double, hipStream_t,
+int fvt16_launch_scalars(const Geo&, const Met&, const DswFields&, real* const*, real*, real*, const real*, int, int, int, int, hipStream_t,
                          const DswWinds*) {
   return PACE_ERR_UNSUPPORTED;
 }

@@ -99,10 +99,24 @@ struct DswWinds {
   double d_con;
 };
 bool dsw_scalars_take_winds();
-int launch_dsw_scalars_lean(const Geo& g, const Met& m, const real* delp, const real* pt, const real* w, const real* q_con,
-                            real* const* outs, const real* crx, const real* cry, const real* xfx, const real* yfx, real* mfx,
-                            real* mfy, real* dw, real* heat_s, real* diss_est, const real* kc, int hord, int nmax_v, int nmax_w,
-                            int nmax_t, double dt, hipStream_t st, const DswWinds* winds = nullptr);
+// The device column block of d_sw: one array of nk + 1 per slot, uploaded by dsw_prepare, read by the launchers of k_dsw.hip and k_fvt.hip
+enum DswColumn {
+  DSWC_NORD_V, DSWC_NORD_W, DSWC_NORD_T, DSWC_DAMP_VT, DSWC_DAMP_W, DSWC_DAMP_T, DSWC_D2_DIVG, DSWC_D_CON, DSWC_KE_BG, DSWC_FAC_VT, DSWC_FAC_T,
+  DSWC_FAC_VT_C, DSWC_FAC_W_C, DSWC_COUNT
+};
+static inline const real* dsw_column(const real* kc, const Geo& g, DswColumn slot) { return kc + (long)slot * (g.nk + 1); }
+// the damping orders the fused scalar kernel takes (fvt_core.h): nmax_* = the column's highest nord_v / nord_w / nord_t
+static inline bool dsw_fused_takes_orders(int nmax_v, int nmax_w, int nmax_t) { return nmax_v <= 2 && nmax_w <= 2 && nmax_t <= 2; }
+// the field arguments of the d_sw entry points (include/pace_hip.h pace_d_sw; its unused zh is not among them)
+struct DswFields {
+  real *delpc, *delp, *pt, *u, *v, *w, *uc, *vc;
+  const real *ua, *va;
+  real *divgd, *mfx, *mfy, *cx, *cy, *crx, *cry, *xfx, *yfx, *q_con, *heat_source, *diss_est;
+  double dt;
+};
+// (f: delp, pt, w, q_con, the Courant numbers and area fluxes, mfx, mfy, diss_est and dt are read from it)
+int launch_dsw_scalars_lean(const Geo& g, const Met& m, const DswFields& f, real* const* outs, real* dw, real* heat_s, const real* kc, int hord,
+                            int nmax_v, int nmax_w, int nmax_t, hipStream_t st, const DswWinds* winds = nullptr);
 // whether launch_transport_lean takes this geometry with this order (fp64 build, tiling, row alignment)
 bool transport_lean_covers(const Geo& g, int hord);
 
@@ -166,12 +180,11 @@ int64_t dsw_workspace_bytes(const Geo& g);
 // whether launch_d_sw can write the four transported scalars to separate buffers (pace_dsw_config_t::delp_out ...)
 bool dsw_pingpong_supported(const Geo& g, const pace_dsw_config_t* cfg);
 bool dsw_winds_in_scalars(const Geo& g, const pace_dsw_config_t* cfg);
+// what launch_d_sw accepts with this column namelist (pace_d_sw_outputs_supported): 0, 1 = the scalars' outputs, 3 = the winds' too
+int dsw_outputs_supported(const Geo& g, const pace_column_t* col, const pace_dsw_config_t* cfg);
 int dsw_prepare(const Geo& g, const pace_column_t* col, void* ws, hipStream_t st);
-int launch_d_sw(const Geo& g, const Met& m, const pace_column_t* col, const pace_dsw_config_t* cfg, void* ws,
-                real* delpc, real* delp, real* pt, real* u, real* v, real* w, real* uc, real* vc,
-                const real* ua, const real* va, real* divgd, real* mfx, real* mfy, real* cx, real* cy,
-                real* crx, real* cry, real* xfx, real* yfx, real* q_con, const real* zh,
-                real* heat_source, real* diss_est, double dt, int phases, hipStream_t st);
+int launch_d_sw(const Geo& g, const Met& m, const pace_column_t* col, const pace_dsw_config_t* cfg, void* ws, int phases,
+                const DswFields& f, hipStream_t st);
 int64_t riem3_workspace_bytes(const Geo& g);
 int launch_riem_solver3(const Geo& g, void* ws, int last_call, double dt, const real* cappa, double ptop,
                         const real* zs, const real* wsd, real* delz, const real* q_con, const real* delp,

@@ -69,8 +69,9 @@ def get_column_namelist(config: DGridShallowWaterLagrangianDynamicsConfig, quant
 
 
 class DGridShallowWaterLagrangianDynamics(Operator):
-    """Fortran d_sw.  One call = the 29-launch HIP sequence in csrc/k_dsw.hip::launch_d_sw instead of
-    the reference's 177 stencil launches."""
+    """Fortran d_sw.  One call = the HIP launches of csrc/k_dsw.hip::launch_d_sw instead of the reference's 177 stencil
+    launches: 9 on the production tilings (6 with `swap_scalar_storage`, 4 when the dead outputs are skipped as well), 11 on the
+    general tilings with order 6 for every transport, 13 otherwise (tests/golden/dsw_launch_sequences.json)."""
 
     def __init__(self, stencil_factory, quantity_factory, grid_data, damping_coefficients, column_namelist, nested: bool,
                  stretched_grid: bool, config: DGridShallowWaterLagrangianDynamicsConfig, *, swap_scalar_storage: bool = False):

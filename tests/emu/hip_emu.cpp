@@ -123,6 +123,9 @@ void emu_launch(dim3 grid, dim3 block, const std::function<void()>& body, int* m
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
   g_kernel_name = name;
+  // PACE_EMU_LAUNCH_LOG: one line per launch (tests compare d_sw's launch sequence with a recorded one; read at every launch)
+  if (getenv("PACE_EMU_LAUNCH_LOG"))
+    fprintf(stderr, "[emu launch] %s grid %u %u %u block %u %u %u\n", name, grid.x, grid.y, grid.z, block.x, block.y, block.z);
   struct InLaunch {
     InLaunch() { g_in_launch = true; }
     ~InLaunch() { g_in_launch = false; }

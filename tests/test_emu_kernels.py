@@ -343,6 +343,209 @@ def test_d_sw_launch_structure_switches_are_bit_identical_emulated():
     dsw_launch_structure_switches()
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# d_sw's phase masks (pace_d_sw_phases; csrc/k_dsw.hip launch_d_sw): 1 flux preparation (16 interior + 32 frame), 2 scalars,
+# 4 winds A (64 kinetic energy + vorticity, 128 divergence damping + vorticity transport), 8 winds B, 256 the fused kernel alone
+# ------------------------------------------------------------------------------------------------------------------
+DSW_PHASE_SEQUENCES = [(15,), (1, 2, 4, 8), (3, 12), (1, 4, 2, 8), (16, 46), (1, 64, 128, 2, 8), (16, 32, 2, 192, 8)]
+DSW_OUT6 = ("delp", "pt", "w", "q_con", "u", "v")
+PACE_ERR_ARG = -1  # include/pace_hip.h
+
+
+class DswPhases:
+    """ONE d_sw operator (the in-place contract) on a synthetic tile, driven mask by mask through pace_d_sw_phases."""
+
+    def __init__(self, lib, device, n, nz, **orders):
+        from pace_amd import synthetic
+        from pace_amd.fv3core import DGridShallowWaterLagrangianDynamicsConfig
+        from pace_amd.fv3core.stencils.d_sw import DGridShallowWaterLagrangianDynamics, get_column_namelist
+
+        m = synthetic.tile_metrics(n, nz)
+        self.state = synthetic.acoustic_state(m, n, nz)
+        self.env = Env(lib, device, m, n, nz)
+        cfg = DGridShallowWaterLagrangianDynamicsConfig(**orders)
+        self.op = DGridShallowWaterLagrangianDynamics(self.env.stencil_factory, self.env.qf, self.env.grid_data, self.env.damping,
+                                                     get_column_namelist(cfg, self.env.qf), False, False, cfg)
+
+    def fresh(self, names=DSW_ARGS):
+        """New buffers holding the state (for separate outputs too: the storage no kernel writes then equals the inputs')."""
+        return {k: self.env.q3(self.state[k]) for k in names}
+
+    def call(self, mask, f, outs=None, flags=0):
+        """pace_d_sw_phases on the fields f; returns the entry point's return code."""
+        import ctypes as C
+
+        from pace_amd.fv3core.stencils._common import dptr
+
+        op = self.op
+        for k in DSW_OUT6:
+            setattr(op._cfg, k + "_out", dptr(outs[k]) if outs else None)
+        op._cfg.flags = flags
+        return op.lib.cdll.pace_d_sw_phases(mask, C.byref(op._geom), *op._args([f[k] for k in DSW_ARGS], float(self.state["dt"])), op.stream())
+
+    def arrays(self, f):
+        if self.env.qf.device.type == "cuda":
+            import torch
+
+            torch.cuda.synchronize()
+        return {k: v.numpy().copy() for k, v in f.items()}
+
+    def run(self, masks):
+        f = self.fresh()
+        for mask in masks:
+            assert self.call(mask, f) == 0, (masks, mask)
+        return self.arrays(f)
+
+
+def check_dsw_phase_sequence(case, ref, masks):
+    got = case.run(masks)
+    for k in DSW_ARGS:  # every argument, whole storage
+        assert np.array_equal(ref[k], got[k], equal_nan=True), (masks, k)
+
+
+def check_dsw_fused_kernel_alone(case, flags):
+    """Mask 256 -- the fused scalar + wind kernel alone, on what a whole call left in the workspace -- writes the six separate
+    outputs and diss_est that the whole call (15) wrote, and leaves the six inputs alone.  (heat_source and the accumulators mfx, mfy,
+    cx, cy are added to by every call.)"""
+    f, outs, outs2 = case.fresh(), case.fresh(DSW_OUT6), case.fresh(DSW_OUT6)
+    assert case.call(15, f, outs, flags) == 0
+    first = case.arrays({**outs, "diss_est": f["diss_est"]})
+    assert not np.array_equal(first["delp"], case.state["delp"]) and not np.array_equal(first["u"], case.state["u"])
+    assert case.call(256, f, outs2, flags) == 0
+    second = case.arrays({**outs2, "diss_est": f["diss_est"]})
+    for k in first:
+        assert np.array_equal(first[k], second[k], equal_nan=True), (flags, k)
+    inputs = case.arrays({k: f[k] for k in DSW_OUT6})
+    for k in DSW_OUT6:
+        assert np.array_equal(inputs[k], case.fresh([k])[k].numpy(), equal_nan=True), (flags, k)
+
+
+_dsw_phase_cases = {}
+
+
+def dsw_phase_case_emulated(build):
+    """(case, what mask 15 leaves in every argument), made once per emulation build: `canon` = C24 x 5 on emu-canon, the lean
+    tilings, where 15 takes the fused scalar + wind kernel and no split sequence does; `default` = C12 x 5, the general tilings."""
+    if build not in _dsw_phase_cases:
+        from helpers import build_emu_canon
+        from pace_amd import _lib
+
+        lib, n = (_lib.Library(build_emu_canon()), 24) if build == "canon" else (_lib.Library(build_emu()), 12)
+        case = DswPhases(lib, "cpu", n, 5)
+        _dsw_phase_cases[build] = (case, case.run((15,)))
+    return _dsw_phase_cases[build]
+
+
+@pytest.mark.parametrize("masks", DSW_PHASE_SEQUENCES, ids=lambda m: "-".join(map(str, m)))
+@pytest.mark.parametrize("build", ["canon", "default"])
+def test_d_sw_phase_masks_compose_emulated(build, masks):
+    """Whatever way a caller splits d_sw into phases (AcousticDynamics: 16 then 46; bench.py and the tools: the single stages),
+    every argument ends with the bits the whole call (15) leaves, over its whole storage."""
+    case, ref = dsw_phase_case_emulated(build)
+    check_dsw_phase_sequence(case, ref, masks)
+
+
+@pytest.mark.parametrize("flags", [0, 1], ids=["full", "skip_dead"])
+def test_d_sw_fused_kernel_alone_emulated(flags):
+    from pace_amd import _lib
+
+    assert _lib.DSW_SKIP_DEAD_OUTPUTS == 1
+    check_dsw_fused_kernel_alone(dsw_phase_case_emulated("canon")[0], flags)
+
+
+def test_d_sw_rejected_phase_masks_emulated():
+    """Alternatives in one mask (1 and 16 / 32, 4 and 64 / 128), 256 with company and masks out of range are argument errors; so is
+    a call that has the winds' separate outputs but runs the scalars and the heating without the winds between them."""
+    case, _ = dsw_phase_case_emulated("canon")
+    f = case.fresh()
+    for mask in (0, 1 | 16, 4 | 64, 256 | 1, 512):
+        assert case.call(mask, f) == PACE_ERR_ARG, mask
+    assert case.call(2 | 8, f, case.fresh(DSW_OUT6)) == PACE_ERR_ARG
+    got = case.arrays(f)
+    for k in DSW_ARGS:  # (and nothing ran)
+        assert np.array_equal(got[k], case.fresh([k])[k].numpy(), equal_nan=True), k
+
+
+# name -> (emulation build, hord_* of the config or None, separate outputs, flags, masks run before the log starts, masks logged)
+_H5656 = dict(hord_dp=5, hord_tm=6, hord_vt=5, hord_mt=6)
+_H5 = dict(hord_dp=5, hord_tm=5, hord_vt=5, hord_mt=5)
+DSW_LAUNCH_CASES = {
+    "canon_15_in_place": ("canon", None, False, 0, (), (15,)),
+    "canon_15_outputs": ("canon", None, True, 0, (), (15,)),
+    "canon_15_outputs_skip_dead": ("canon", None, True, 1, (), (15,)),
+    "canon_16_46": ("canon", None, False, 0, (), (16, 46)),
+    "canon_1_4_2_8": ("canon", None, False, 0, (), (1, 4, 2, 8)),
+    "canon_256": ("canon", None, True, 0, (15,), (256,)),
+    "canon_15_hord_5656": ("canon", _H5656, False, 0, (), (15,)),
+    "default_15": ("default", None, False, 0, (), (15,)),
+    "default_1_4_2_8": ("default", None, False, 0, (), (1, 4, 2, 8)),
+    "default_15_hord_5": ("default", _H5, False, 0, (), (15,)),
+}
+
+
+def _dsw_launch_log_child(name):
+    """(child process) Run the case; the emulation writes one line per kernel launch to stderr while PACE_EMU_LAUNCH_LOG is set
+    (tests/emu/hip_emu.cpp emu_launch reads it at every launch: the operator's set-up is not logged)."""
+    from helpers import build_emu_canon
+    from pace_amd import _lib
+
+    build, orders, separate, flags, before, masks = DSW_LAUNCH_CASES[name]
+    lib, n = (_lib.Library(build_emu_canon()), 24) if build == "canon" else (_lib.Library(build_emu()), 12)
+    case = DswPhases(lib, "cpu", n, 5, **(orders or {}))
+    f, outs = case.fresh(), (case.fresh(DSW_OUT6) if separate else None)
+    for mask in before:
+        assert case.call(mask, f, outs, flags) == 0
+    if before and separate:  # (mask 256: into a second set of outputs)
+        outs = case.fresh(DSW_OUT6)
+    os.environ["PACE_EMU_LAUNCH_LOG"] = "1"
+    for mask in masks:
+        assert case.call(mask, f, outs, flags) == 0
+
+
+def dsw_launch_sequence(name):
+    """[[kernel name (up to its template arguments), grid x, y, z, block x, y, z], ...] of the case, from a child process."""
+    import subprocess
+    import sys
+
+    from helpers import ROOT
+
+    code = (f"import sys; sys.path.insert(0, {ROOT!r}); sys.path.insert(0, {os.path.join(ROOT, 'tests')!r}); "
+            f"import test_emu_kernels as t; t._dsw_launch_log_child({name!r})")
+    env = {k: v for k, v in os.environ.items() if k != "PACE_EMU_LAUNCH_LOG"}
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
+    assert p.returncode == 0, p.stderr[-3000:]
+    seq = []
+    for line in p.stderr.splitlines():
+        if line.startswith("[emu launch] "):
+            kernel, dims = line[len("[emu launch] "):].split(" grid ")
+            seq.append([kernel.split("<")[0].strip("() ")] + [int(x) for x in dims.replace("block ", "").split()])
+    return seq
+
+
+def record_dsw_launch_sequences():
+    """How tests/golden/dsw_launch_sequences.json was made (on the commit BEFORE launch_d_sw became a plan and named stages)."""
+    import json
+
+    from helpers import GOLDEN
+
+    with open(os.path.join(GOLDEN, "dsw_launch_sequences.json"), "w") as f:
+        f.write("{\n" + ",\n".join(f"{json.dumps(name)}: {json.dumps(dsw_launch_sequence(name))}" for name in DSW_LAUNCH_CASES) + "\n}\n")
+
+
+@pytest.mark.parametrize("name", list(DSW_LAUNCH_CASES))
+def test_d_sw_launch_sequence_is_the_recorded_one(name):
+    """Equal outputs cannot see an extra copy kernel or another grid: the kernels d_sw launches, in order, with their grid and
+    block dimensions, are those recorded in tests/golden/dsw_launch_sequences.json."""
+    import json
+
+    from helpers import GOLDEN
+
+    with open(os.path.join(GOLDEN, "dsw_launch_sequences.json")) as f:
+        recorded = json.load(f)
+    seq = dsw_launch_sequence(name)
+    assert len(seq) > 0 and seq == recorded[name], (name, seq)
+
+
 def test_swapped_storage_is_detectable():
     """What holds something derived from a Quantity's storage across a d_sw call with `swap_scalar_storage` can tell that it went
     stale: `Quantity.generation` counts the swaps, a tensor taken from `.data` before the call no longer aliases the Quantity,

@@ -707,6 +707,52 @@ def test_d_sw_launch_structure_switches_are_bit_identical(lib):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [24, 48, 96])
+def test_d_sw_phase_masks_compose(lib, n):
+    """The GPU twin of ..._emulated: every way of splitting d_sw into phases leaves the bits of the whole call in every argument,
+    whole storage -- C24 x 5 (the general tilings), C48 x 5 (the 16 x 24 tile), C96 x 5 (the 32 x 24 tile, 3 x 4 of them: corner,
+    edge and interior tiles)."""
+    from test_emu_kernels import DSW_PHASE_SEQUENCES, DswPhases, check_dsw_phase_sequence
+
+    case = DswPhases(lib, "cuda", n, 5)
+    ref = case.run((15,))
+    for masks in DSW_PHASE_SEQUENCES:
+        check_dsw_phase_sequence(case, ref, masks)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [0, 1], ids=["full", "skip_dead"])
+def test_d_sw_fused_kernel_alone(lib, flags):
+    from test_emu_kernels import DswPhases, check_dsw_fused_kernel_alone
+
+    check_dsw_fused_kernel_alone(DswPhases(lib, "cuda", 48, 5), flags)
+
+
+@pytest.mark.gpu
+def test_d_sw_overlapped_on_two_streams_equals_one_stream(lib):
+    """C24 x 5, the general tilings: pace_d_sw_overlapped has work for the side stream (flux preparation, winds A next to the
+    scalars, winds B after them: three events).  After join() every argument holds the bits of the one-stream call."""
+    import torch
+
+    from test_emu_kernels import DswPhases
+
+    import ctypes as C
+
+    case = DswPhases(lib, "cuda", 24, 5)
+    assert lib.cdll.pace_d_sw_wind_outputs_supported(C.byref(case.op._geom), C.byref(case.op._cfg)) == 0  # (else: one stream)
+    res = []
+    for overlap in (False, True):
+        f = case.fresh()
+        case.op(*[f[k] for k in DSW_ARGS], float(case.state["dt"]), overlap_winds=overlap)
+        assert case.op._pending == overlap
+        case.op.join()
+        torch.cuda.synchronize()
+        res.append(case.arrays(f))
+    for k in DSW_ARGS:
+        assert np.array_equal(res[0][k], res[1][k], equal_nan=True), k
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n,nz", [(192, 8), (96, 79)])
 def test_c_sw_interior_tiles_equal_the_four_passes_on_the_device(n, nz):
     """c_sw on the device: k_csw_tile on the interior tiles (6 x 12 of them at C192) + the four passes on the band, beside each other
