@@ -4,7 +4,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC := pace_amd/csrc
 SRCS := $(CSRC)/capi.hip $(CSRC)/k_fxadv.hip $(CSRC)/k_fvtp2d.hip $(CSRC)/k_fvt.hip $(CSRC)/k_fvt16.hip $(CSRC)/k_delnflux.hip $(CSRC)/k_dsw.hip $(CSRC)/k_riem3.hip $(CSRC)/k_riem3f.hip $(CSRC)/k_sim1.hip $(CSRC)/k_ppm.hip $(CSRC)/k_csw.hip $(CSRC)/k_acoustic.hip $(CSRC)/k_halo.hip $(CSRC)/k_tracer.hip $(CSRC)/k_remap.hip $(CSRC)/k_l2e.hip $(CSRC)/k_satadj.hip $(CSRC)/k_subgridz.hip $(CSRC)/k_updphys.hip $(CSRC)/k_microphys.hip $(CSRC)/k_physics.hip $(CSRC)/k_dycore.hip $(CSRC)/k_stencils.hip
-HDRS := $(CSRC)/k_fvt.hip $(CSRC)/common.h $(CSRC)/kernels.h $(CSRC)/thermo.h $(CSRC)/delnflux_core.h $(CSRC)/fvt_core.h include/pace_hip.h
+HDRS := $(CSRC)/k_fvt.hip $(CSRC)/common.h $(CSRC)/kernels.h $(CSRC)/wgmap.h $(CSRC)/thermo.h $(CSRC)/delnflux_core.h $(CSRC)/fvt_core.h include/pace_hip.h
 # -ffp-contract=off: no FMA contraction, so horizontal stencils are bit-comparable with the numpy oracle.
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function
 OBJS := $(patsubst $(CSRC)/%.hip,build/hip/%.o,$(SRCS))
@@ -88,7 +88,18 @@ emu-canon: tests/emu/libpace_emu_canon.so
 tests/emu/libpace_emu_canon.so: $(CANONOBJS) build/emu/hip_emu.o
 	g++ -shared -fPIC $(EXPORTS) $(CANONOBJS) build/emu/hip_emu.o -o $@
 
+# the stand-alone exhaustive check of the workgroup maps (csrc/wgmap.h), plain and under AddressSanitizer + UBSan (their runtimes
+# linked statically: a stand-alone program that runs in any environment)
+WGMAP_SRC := tests/emu/wgmap_check.cpp $(CSRC)/wgmap.h
+wgmap-check: build/wgmap_check build/wgmap_check_asan
+build/wgmap_check: $(WGMAP_SRC)
+	@mkdir -p build
+	g++ -O2 -g -std=c++17 -Wall -Wextra tests/emu/wgmap_check.cpp -o $@
+build/wgmap_check_asan: $(WGMAP_SRC)
+	@mkdir -p build
+	g++ -O2 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -static-libasan -static-libubsan -fno-sanitize-recover=all -fno-omit-frame-pointer tests/emu/wgmap_check.cpp -o $@
+
 clean:
 	rm -rf build pace_amd/libpace_hip.so pace_amd/libpace_hip_f32.so tests/emu/libpace_emu.so tests/emu/libpace_emu_small.so tests/emu/libpace_emu_f32.so tests/emu/libpace_emu_canon.so tests/emu/libpace_emu_mpcov.so
 
-.PHONY: all f32 emu emu-f32 emu-small emu-canon emu-mpcov clean
+.PHONY: all f32 emu emu-f32 emu-small emu-canon emu-mpcov wgmap-check clean

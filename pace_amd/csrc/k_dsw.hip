@@ -184,26 +184,9 @@ __global__ void __launch_bounds__(256)
 k_ke_vorticity(Geo g, Met m, const real* __restrict__ uc, const real* __restrict__ vc, const real* __restrict__ u,
                const real* __restrict__ v, const real* __restrict__ ut, const real* __restrict__ vt, real* __restrict__ ke, double dt,
                Regions R, real* __restrict__ vort, int nbr) {
-  int bx__, bz__;
-#ifdef PACE_EMU
-  bx__ = (int)blockIdx.x, bz__ = (int)blockIdx.z;
-#else
-  {  // (workgroups are dealt to the eight XCDs round-robin in launch order, each XCD has its own L2, and a point re-reads rows of its
-     // j-neighbours: the workgroups of a level run on ONE XCD -- XCD x works through levels x, x + 8, ...; affinity only, the map is a
-     // bijection of the launch's workgroups)
-    const int nbx__ = (int)gridDim.x, nlev__ = (int)gridDim.z;
-    const int lin__ = (int)blockIdx.x + nbx__ * (int)blockIdx.z;
-    const int full__ = (nlev__ / 8) * 8;
-    if (lin__ < full__ * nbx__) {
-      const int slot__ = lin__ >> 3;
-      bz__ = (slot__ / nbx__) * 8 + (lin__ & 7);
-      bx__ = slot__ - (slot__ / nbx__) * nbx__;
-    } else {
-      bz__ = lin__ / nbx__;
-      bx__ = lin__ - bz__ * nbx__;
-    }
-  }
-#endif
+  // (a point re-reads rows of its j-neighbours: the workgroups of a level run on ONE XCD -- wgmap.h ke_block_of_linear; affinity only)
+  const KeBlock wg__ = ke_block_of_linear((int)blockIdx.x + (int)gridDim.x * (int)blockIdx.z, (int)gridDim.x, (int)gridDim.z);
+  const int bx__ = wg__.bx, bz__ = wg__.bz;
   const int k0 = bz__ * KE_CH;
   if (bx__ >= nbr) {
     // a 64 x 4 patch of the vorticity (patch_grid's enumeration)

@@ -298,14 +298,13 @@ __global__ void __launch_bounds__(FX_NT) FX_ATTR k_fxadv_fused(Geo g, Met m, con
   b -= nframe;
   // ---- the interior box: FXC levels of a point per thread (the metric values of the point loaded once) ----
 #ifdef PACE_EMU
+  // (the emulated launch is not padded -- tests/golden/dsw_launch_sequences.json records its grids -- and the map needs the padding)
   const int chunk = b / nbx, bxp = b - chunk * nbx;
 #else
-  // Workgroups are dealt to the eight XCDs round-robin in launch order, and a point reads the rows above and below its own: XCD x takes
-  // the x-th eighth of the plane's blocks (contiguous rows) of every chunk of levels, so that only the seams between the eighths are
-  // fetched by two L2s (with the plain order: 324 MB for 233 algorithmic)
-  const int seg = nbx / 8;
-  const int chunk = b / nbx, r = b - chunk * nbx;
-  const int bxp = (r & 7) * seg + (r >> 3);
+  // XCD x takes the x-th eighth of the plane's blocks (contiguous rows) of every chunk of levels (wgmap.h fxadv_block_of_workgroup);
+  // the blocks the launch is padded with lie past the plane's last row: the box test below returns them
+  const FxBlock wg = fxadv_block_of_workgroup(b, nbx);
+  const int chunk = wg.chunk, bxp = wg.block;
 #endif
   const long p = (long)bxp * FX_NT + tid;
   const int j = (int)(p / g.sj);
@@ -389,7 +388,7 @@ int launch_fxadv(const Geo& g, const Met& m, const real* uc, const real* vc, rea
   // the interior's blocks: the whole plane's flattened rows (a block whose points all lie outside the box returns at once)
   unsigned nbx = (unsigned)(((long)g.sj * g.nj + FX_NT - 1) / FX_NT);
 #ifndef PACE_EMU
-  nbx = (nbx + 7) / 8 * 8;
+  nbx = (unsigned)fxadv_padded_blocks((int)nbx);  // (the workgroup map deals the blocks out in eighths)
 #endif
   const bool interior = has_box && part != 2;
   // levels per thread of the interior's blocks: as many as still leave two workgroups (of 1024 threads) per compute unit

@@ -1,6 +1,7 @@
 // Host-side launch functions (one per reference class on the hot path).
 #pragma once
 #include "common.h"
+#include "wgmap.h"
 
 // d_sw's separate wind outputs get the halo of the inputs (k_dsw.hip k_copy_wind_halo): a copy the frame workgroups of the one-launch
 // form take along (their stage A waits for a round trip anyway); `done` tells the caller whether this launch took it
@@ -127,45 +128,11 @@ struct FvMet {
 };
 static inline FvMet fv_met(const Met& m) { return FvMet{m.area, m.rarea, m.dxa, m.dya, m.dx, m.dy, m.del6_u, m.del6_v}; }
 
-// Workgroup -> (tile, level) of the transport kernels.  Workgroups are handed to the eight XCDs round-robin in launch order, and
-// every XCD has its own 4 MB L2: with the plain (x, y, z) order, neighbouring tiles of a level land on DIFFERENT XCDs and every
-// line of their overlapping footprints is fetched from memory once per XCD (measured: 1.9 x the algorithmic bytes).  Here a level
-// belongs to ONE XCD: XCD x works through levels x, x + 8, x + 16, ... tile by tile, so the halo lines shared by neighbouring
-// tiles are L2 hits.  (Affinity only: nothing depends on where a workgroup really runs.)
-struct FvTile {
-  int bx, by, bz;
-};
+// Workgroup -> (tile, level) of the transport kernels: the map of wgmap.h (a level belongs to one XCD) at this workgroup's place
+// in its launch; the emulation takes the same map
 __device__ __forceinline__ FvTile fv_tile_of_workgroup() {
-#ifdef PACE_EMU
-  return FvTile{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
-#else
   const int gx = gridDim.x, gy = gridDim.y, nlev = gridDim.z;
-  const int tpl = gx * gy;
-  const int b = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  const int full = (nlev / 8) * 8;  // levels that can be dealt out eight at a time
-  int lev, t;
-  if (b < full * tpl) {
-    const int xcd = b & 7, slot = b >> 3;
-    lev = (slot / tpl) * 8 + xcd;
-    t = slot - (slot / tpl) * tpl;
-  } else {
-    lev = b / tpl;
-    t = b - lev * tpl;
-  }
-  // within a level: the four corner tiles first, then the edge tiles, then the interior ones -- the corner and edge forms take
-  // 1.2 - 2 x as long as the straight-line interior code, and the workgroups that start last should not be the longest ones
-  if (gx >= 3 && gy >= 3) {
-    if (t < 4) return FvTile{(t & 1) ? gx - 1 : 0, (t & 2) ? gy - 1 : 0, lev};
-    t -= 4;
-    const int nsn = 2 * (gx - 2), nwe = 2 * (gy - 2);
-    if (t < nsn) return FvTile{1 + (t >> 1), (t & 1) ? gy - 1 : 0, lev};
-    t -= nsn;
-    if (t < nwe) return FvTile{(t & 1) ? gx - 1 : 0, 1 + (t >> 1), lev};
-    t -= nwe;
-    return FvTile{1 + t % (gx - 2), 1 + t / (gx - 2), lev};
-  }
-  return FvTile{t % gx, t / gx, lev};
-#endif
+  return fv_tile_of_linear(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx, gy, nlev);
 }
 int launch_delnflux(const Geo& g, const Met& m, int mode, const real* q, real* fx, real* fy,
                     const real* mass, const real* damp_k, const real* nord_k, int nmax, int mass_given,

@@ -18,7 +18,8 @@ def compare(a, b, near_zero=0.0):
     diff = np.abs(a - b)
     denom = np.abs(a) + np.abs(b)
     with np.errstate(all="ignore"):
-        rel = np.where(denom > 0, 2 * diff / np.where(denom > 0, denom, 1.0), 0.0)
+        # (denom == 0, not "not denom > 0": a NaN on one side only has a NaN denominator and must come out as an error)
+        rel = np.where(denom == 0, 0.0, 2 * diff / np.where(denom == 0, 1.0, denom))
     rel[both_nan] = 0.0
     rel[np.isnan(rel)] = np.inf
     if near_zero > 0:

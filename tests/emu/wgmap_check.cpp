@@ -1,0 +1,168 @@
+// Exhaustive check of the workgroup maps of pace_amd/csrc/wgmap.h (stand-alone host program; test infrastructure).
+//
+// For every launch shape in the ranges below: the image of the launch's workgroups under the map is EXACTLY the set of the
+// launch's pieces of work, each once -- none skipped, none repeated, none outside.  For the padded launch of the flux preparation
+// the pieces are the nblocks real blocks of every chunk: each is taken once, and the other workgroups of the launch -- exactly
+// (padded - nblocks) per chunk -- get block numbers in [nblocks, padded), whose points lie past the plane's last row, so the
+// kernel's box test returns them (k_fxadv.hip; fxadv_block_is_padding is that comparison by name, nothing more).  Prints the
+// first offending shape and workgroup and exits 1; prints one summary line per map and exits 0 otherwise.
+//
+//   wgmap_check            the full ranges
+//   wgmap_check --quick    a tenth of the level counts (for a first look; the test-suite runs the full ranges)
+//   wgmap_check --fv b gx gy nlev    prints the (tile x, tile y, level) of workgroup b of a gx x gy x nlev transport launch
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "../../pace_amd/csrc/wgmap.h"
+
+namespace {
+
+long long g_workgroups = 0;
+std::vector<unsigned char> g_seen;  // (sized per shape; its bounds are what AddressSanitizer watches)
+
+// ---- transport: gx x gy tiles x nlev levels ----
+bool check_fv(int gx, int gy, int nlev) {
+  const int total = gx * gy * nlev;
+  g_seen.assign((size_t)total, 0);
+  for (int b = 0; b < total; ++b) {
+    const FvTile t = fv_tile_of_linear(b, gx, gy, nlev);
+    const bool inside = t.bx >= 0 && t.bx < gx && t.by >= 0 && t.by < gy && t.bz >= 0 && t.bz < nlev;
+    if (!inside) {
+      std::printf("fv_tile_of_linear: gx %d gy %d nlev %d: workgroup %d -> (%d, %d, %d) is outside the launch\n", gx, gy, nlev, b, t.bx,
+                  t.by, t.bz);
+      return false;
+    }
+    unsigned char& s = g_seen[(size_t)t.bx + (size_t)gx * ((size_t)t.by + (size_t)gy * (size_t)t.bz)];
+    if (s) {
+      std::printf("fv_tile_of_linear: gx %d gy %d nlev %d: workgroup %d -> (%d, %d, %d) is taken twice\n", gx, gy, nlev, b, t.bx, t.by,
+                  t.bz);
+      return false;
+    }
+    s = 1;
+  }
+  g_workgroups += total;
+  return true;  // total distinct images among total places: nothing is skipped
+}
+
+// ---- d_sw's kinetic energy + vorticity: nbx blocks x nlev chunks of levels ----
+bool check_ke(int nbx, int nlev) {
+  const int total = nbx * nlev;
+  g_seen.assign((size_t)total, 0);
+  for (int lin = 0; lin < total; ++lin) {
+    const KeBlock t = ke_block_of_linear(lin, nbx, nlev);
+    if (!(t.bx >= 0 && t.bx < nbx && t.bz >= 0 && t.bz < nlev)) {
+      std::printf("ke_block_of_linear: nbx %d nlev %d: workgroup %d -> (%d, %d) is outside the launch\n", nbx, nlev, lin, t.bx, t.bz);
+      return false;
+    }
+    unsigned char& s = g_seen[(size_t)t.bx + (size_t)nbx * (size_t)t.bz];
+    if (s) {
+      std::printf("ke_block_of_linear: nbx %d nlev %d: workgroup %d -> (%d, %d) is taken twice\n", nbx, nlev, lin, t.bx, t.bz);
+      return false;
+    }
+    s = 1;
+  }
+  g_workgroups += total;
+  return true;
+}
+
+// ---- the flux preparation's interior: nblocks real blocks, padded to a multiple of eight, x nchunks chunks of levels ----
+bool check_fx(int nblocks, int nchunks) {
+  const int nbx = fxadv_padded_blocks(nblocks);
+  if (nbx < nblocks || nbx % 8 != 0 || nbx - nblocks > 7) {
+    std::printf("fxadv_padded_blocks: %d blocks -> %d\n", nblocks, nbx);
+    return false;
+  }
+  const int total = nbx * nchunks;
+  g_seen.assign((size_t)nblocks * (size_t)nchunks, 0);
+  int real = 0, padding = 0;
+  for (int b = 0; b < total; ++b) {
+    const FxBlock t = fxadv_block_of_workgroup(b, nbx);
+    if (!(t.block >= 0 && t.block < nbx && t.chunk >= 0 && t.chunk < nchunks)) {
+      std::printf("fxadv_block_of_workgroup: blocks %d chunks %d: workgroup %d -> (%d, %d) is outside the padded launch\n", nblocks,
+                  nchunks, b, t.block, t.chunk);
+      return false;
+    }
+    if (fxadv_block_is_padding(t, nblocks)) {  // (in [nblocks, nbx) by the test above: past the plane)
+      ++padding;
+      continue;
+    }
+    unsigned char& s = g_seen[(size_t)t.block + (size_t)nblocks * (size_t)t.chunk];
+    if (s) {
+      std::printf("fxadv_block_of_workgroup: blocks %d chunks %d: workgroup %d -> (%d, %d) is taken twice\n", nblocks, nchunks, b, t.block,
+                  t.chunk);
+      return false;
+    }
+    s = 1;
+    ++real;
+  }
+  if (real != nblocks * nchunks || padding != (nbx - nblocks) * nchunks) {
+    std::printf("fxadv_block_of_workgroup: blocks %d chunks %d: %d real and %d padding workgroups, expected %d and %d\n", nblocks, nchunks,
+                real, padding, nblocks * nchunks, (nbx - nblocks) * nchunks);
+    return false;
+  }
+  g_workgroups += total;
+  return true;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc == 6 && std::strcmp(argv[1], "--fv") == 0) {  // one workgroup of one transport launch: "bx by bz"
+    const FvTile t = fv_tile_of_linear(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]));
+    std::printf("%d %d %d\n", t.bx, t.by, t.bz);
+    return 0;
+  }
+  const int step = (argc > 1 && std::strcmp(argv[1], "--quick") == 0) ? 10 : 1;
+  // transport: every gx in 1 .. 13, gy in 1 .. 16, nlev in 1 .. 130 ...
+  long long shapes = 0;
+  for (int gx = 1; gx <= 13; ++gx)
+    for (int gy = 1; gy <= 16; ++gy)
+      for (int nlev = 1; nlev <= 130; nlev += step, ++shapes)
+        if (!check_fv(gx, gy, nlev)) return 1;
+  // ... and, outside that box, every grid a launcher makes of some n in 12 .. 384, with every nlev 1 .. 130: the general kernel's
+  // (ceil(n / 32), ceil(n / 24)), the three-planes-high launch of d_sw's three scalars (the same with 3 ceil(n / 24)), and the
+  // lean kernels' n / 32 x n / 24 and n / 16 x n / 24 where the tile divides n (k_fvt.hip covers: the 16 x 24 shape takes the
+  // multiples of 48 that are no multiples of 32 -- C48, C144, C240: 15 x 10, C336: 21 x 14)
+  std::vector<std::pair<int, int>> done;
+  const auto extra = [&](int gx, int gy) {
+    if (gx <= 13 && gy <= 16) return true;
+    for (const auto& d : done)
+      if (d.first == gx && d.second == gy) return true;
+    done.emplace_back(gx, gy);
+    for (int nlev = 1; nlev <= 130; nlev += step, ++shapes)
+      if (!check_fv(gx, gy, nlev)) return false;
+    return true;
+  };
+  for (int n = 12; n <= 384; ++n) {
+    const int gx = (n + 31) / 32, gy = (n + 23) / 24;
+    if (!extra(gx, gy) || !extra(gx, 3 * gy)) return 1;
+    if (n % 24 == 0 && n % 32 == 0 && !extra(n / 32, n / 24)) return 1;
+    if (n % 24 == 0 && n % 16 == 0 && !extra(n / 16, n / 24)) return 1;
+  }
+  std::printf("fv_tile_of_linear: %lld launch shapes, every (tile, level) once\n", shapes);
+  // kinetic energy + vorticity (blocks x chunks of one or two levels; C12: 11 blocks, C384: about 1 300): every block count
+  // 1 .. 64 with every level count 1 .. 130, every block count 65 .. 1400 with the level counts at both ends and around the
+  // multiples of eight (the map's only dependence on the level count is nlev / 8 and nlev % 8)
+  shapes = 0;
+  for (int nbx = 1; nbx <= 64; ++nbx)
+    for (int nlev = 1; nlev <= 130; nlev += step, ++shapes)
+      if (!check_ke(nbx, nlev)) return 1;
+  for (int nbx = 65; nbx <= 1400; nbx += step)
+    for (int nlev : {1, 7, 8, 9, 79, 127, 128}) {
+      ++shapes;
+      if (!check_ke(nbx, nlev)) return 1;
+    }
+  std::printf("ke_block_of_linear: %lld launch shapes, every (block, chunk) once\n", shapes);
+  // flux preparation: every block count 1 .. 160 (C384: 153) with every chunk count 1 .. 130 (a small tile takes one level per
+  // chunk)
+  shapes = 0;
+  for (int nblocks = 1; nblocks <= 160; ++nblocks)
+    for (int nchunks = 1; nchunks <= 130; nchunks += step, ++shapes)
+      if (!check_fx(nblocks, nchunks)) return 1;
+  std::printf("fxadv_block_of_workgroup: %lld launch shapes, every real (block, chunk) once, the rest past the last block\n", shapes);
+  std::printf("wgmap_check ok: %lld workgroups\n", g_workgroups);
+  return 0;
+}

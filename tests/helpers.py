@@ -77,6 +77,123 @@ def build_emu_small():
     return os.path.join(ROOT, "tests", "emu", "libpace_emu_small.so")
 
 
+def build_wgmap_check():
+    """build/wgmap_check and build/wgmap_check_asan: the stand-alone exhaustive check of the workgroup maps (csrc/wgmap.h,
+    tests/emu/wgmap_check.cpp; Makefile wgmap-check), plain and under AddressSanitizer + UBSan."""
+    _make("wgmap-check")
+    return os.path.join(ROOT, "build", "wgmap_check"), os.path.join(ROOT, "build", "wgmap_check_asan")
+
+
+def riem3_inputs(s, **over):
+    """The arguments of riem_solver3 (RIEM_ARGS) from a synthetic acoustic state; `over`: fields taken from elsewhere."""
+    inp = {"cappa": s["cappa"], "zs": s["zs"], "ws": s["ws"], "delz": s["delz"], "q_con": s["q_con"], "delp": s["delp"],
+           "pt": s["pt"], "zh": s["zh"], "p": s["pe"], "ppe": s["ppe"], "pk3": s["pk3"], "pk": s["pk"],
+           "log_p_interface": s["peln"], "w": s["w"]}
+    inp.update(over)
+    return inp
+
+
+def oracle_riem3(g, inp, last_call, dt, ptop):
+    from oracle import vertical
+
+    b = {k: v.copy() for k, v in inp.items()}
+    vertical.riem_solver3(g, last_call, dt, b["cappa"], ptop, b["zs"], b["ws"], b["delz"], b["q_con"], b["delp"], b["pt"],
+                          b["zh"], b["p"], b["ppe"], b["pk3"], b["pk"], b["log_p_interface"], b["w"], p_fac=0.05)
+    return b
+
+
+def check_other_level_counts(lib, device, nz, dsw_tol=0.0):
+    """d_sw and riem_solver3 (not the last call) at C12 with nz layers against the oracle: d_sw within dsw_tol (0: bit for bit,
+    the emulation; 3.2e-10, translate_d_sw.py:19, the device), the column solver to the exp / log rounding (5e-6,
+    overrides/standard.yaml:49-61).  Returns {variable: error} of the column solver."""
+    from oracle import dgrid_sw
+    from pace_amd import synthetic
+    from pace_amd.fv3core import DGridShallowWaterLagrangianDynamicsConfig
+    from pace_amd.fv3core.stencils.d_sw import get_column_namelist
+
+    n = 12
+    metrics = synthetic.tile_metrics(n, nz)
+    s = synthetic.acoustic_state(metrics, n, nz)
+    env = Env(lib, device, metrics, n, nz)
+    colq = get_column_namelist(DGridShallowWaterLagrangianDynamicsConfig(**DSW_CFG), env.qf)
+    col = {k: (v.numpy() if hasattr(v, "numpy") else np.asarray(v))[:nz] for k, v in colq.items()}
+    out, _ = run_d_sw(env, col, {k: s[k] for k in DSW_ARGS}, s["dt"])
+    g = oracle_grid(metrics, n, nz)
+    a = {k: s[k].copy() for k in DSW_ARGS}
+    dgrid_sw.d_sw(g, col, DSW_CFG, dgrid_sw.DSWState(s["u"].shape), *[a[k] for k in DSW_ARGS], s["dt"])
+    for k in DSW_ARGS:
+        if k != "zh":
+            assert compare(a[k][dsw_window(k, n, nz)], out[k][dsw_window(k, n, nz)]) <= dsw_tol, k
+    inp = riem3_inputs(s, q_con=a["q_con"], delp=a["delp"], pt=a["pt"], w=a["w"])
+    got = run_riem3(env, inp, False, s["dt"], metrics["ptop"])
+    b = oracle_riem3(g, inp, False, s["dt"], metrics["ptop"])
+    errs = {}
+    for k in ("delz", "zh", "ppe", "pk3", "w"):
+        nk = nz if k in ("delz", "w") else nz + 1
+        errs[k] = compare(b[k][window(n, 0, 0, nk)], got[k][window(n, 0, 0, nk)], near_zero=1e-9 * float(np.abs(b[k]).max()))
+        assert errs[k] < 5e-6, k
+    return errs
+
+
+# the near-zero floors of riem_solver3's check in tests/opchain.py (Chain.cases), as fractions of a field's magnitude: w and the
+# perturbation pressure cross zero, the rest have none
+RIEM3_OPCHAIN_FLOORS = {"w": 1e-5, "ppe": 1e-5, "delz": 0.0, "zh": 0.0, "pk3": 0.0, "p": 0.0, "pk": 0.0, "log_p_interface": 0.0}
+
+
+def check_riem_column_windows(lib, device, n, nz=33, last_call=True, solver_c=True, floors=None):
+    """riem_solver3 on the compute domain of a C<n> tile with nz layers and (solver_c) riem_solver_c on compute + 1 (other window
+    bounds of k_riem3f.hip ColumnWindows), against the oracle: riem_solver3 within 5e-6 (overrides/standard.yaml:49-61),
+    riem_solver_c within 5e-14 (translate_riem_solver_c.py:33), and nothing outside the compute domain (compute + 1) is
+    written.  floors: the near-zero escape of the comparison per variable, as a fraction of the field's magnitude (default: 1e-9
+    for all).  Returns {variable: error} ("c.pef", "c.gz": riem_solver_c)."""
+    from oracle import vertical
+    from pace_amd import synthetic
+    from pace_amd.fv3core.stencils.riem_solver_c import NonhydrostaticVerticalSolverCGrid
+
+    metrics = synthetic.tile_metrics(n, nz)
+    s = synthetic.acoustic_state(metrics, n, nz)
+    env = Env(lib, device, metrics, n, nz)
+    g = oracle_grid(metrics, n, nz)
+    inp = riem3_inputs(s)
+    got = run_riem3(env, inp, last_call, s["dt"], metrics["ptop"])
+    b = oracle_riem3(g, inp, last_call, s["dt"], metrics["ptop"])
+    errs = {}
+    for k in ("delz", "zh", "ppe", "pk3", "w", "p", "pk", "log_p_interface"):
+        nk = nz if k in ("delz", "w") else nz + 1
+        floor = 1e-9 if floors is None else floors[k]
+        errs[k] = compare(b[k][window(n, 0, 0, nk)], got[k][window(n, 0, 0, nk)], near_zero=floor * float(np.abs(b[k]).max()))
+        assert errs[k] < 5e-6, (k, errs[k])
+        # nothing outside the compute domain is written
+        outside = np.ones(b[k].shape, dtype=bool)
+        outside[window(n, 0, 0, nk)] = False
+        outside[:, :, nk:] = False
+        assert np.array_equal(got[k][outside], inp[k][outside]), k
+    if not solver_c:
+        return errs
+    # riem_solver_c: compute + 1
+    solver = NonhydrostaticVerticalSolverCGrid(env.stencil_factory, env.qf, 0.05)
+    a = {k: s[k].copy() for k in ("cappa", "pt", "q_con", "delp", "zh", "w")}
+    f = {k: env.q3(v) for k, v in a.items()}
+    hs = s["zs"] * 9.80665
+    ws3 = np.ascontiguousarray(s["ws"])
+    pef = env.q3(np.zeros_like(s["zh"]))
+    solver(0.5 * s["dt"], f["cappa"], float(metrics["ptop"]), env.q2(hs), env.q2(ws3), f["pt"], f["q_con"], f["delp"], f["zh"], pef, f["w"])
+    ref_pef = np.zeros_like(s["zh"])
+    vertical.riem_solver_c(g, 0.5 * s["dt"], a["cappa"], float(metrics["ptop"]), hs, ws3, a["pt"], a["q_con"], a["delp"], a["zh"], ref_pef,
+                           a["w"], p_fac=0.05)
+    W = (slice(2, 4 + n), slice(2, 4 + n), slice(0, nz + 1))
+    errs["c.pef"] = compare(ref_pef[W], pef.numpy()[W])
+    errs["c.gz"] = compare(a["zh"][W], f["zh"].numpy()[W])
+    assert errs["c.pef"] < 5e-14
+    assert errs["c.gz"] < 5e-14
+    # nothing outside compute + 1 is written (pef started as zeros, gz as the input heights)
+    outside = np.ones(s["zh"].shape, dtype=bool)
+    outside[W] = False
+    assert np.array_equal(pef.numpy()[outside], np.zeros_like(s["zh"])[outside])
+    assert np.array_equal(f["zh"].numpy()[outside], s["zh"][outside])
+    return errs
+
+
 def expand_riem_fixture(fix, n=12, nz=79):
     """The fixture stores 4 rows of columns; tile them over the compute domain (columns are independent)."""
     out = {}

@@ -305,9 +305,37 @@ SPHERE_CHECKS = {("riem_solver_c", "pkc"): (1e-9, 1e-2, 1e-11), ("riem_solver_c"
 SPHERE_CHAIN = ("d2a2c_vect", "c_sw", "updatedzc", "riem_solver_c", "p_grad_c", "d_sw", "updatedzd")
 
 
-def check_case(ops, case, scale_tol=1.0, report=None, sphere=False):
+# Outputs an operator only WRITES (it never reads what they held): with poison=True check_case fills their checked windows with
+# NaN before the call, as the chain fills pk3 with 1e40 -- a workgroup that is skipped then leaves NaN where the oracle has a
+# number.  (An entry that the operator did read would fail at once, under emulation as on the device: NaN propagates.)
+WRITE_ONLY = {
+    "d2a2c_vect": ("uc", "vc", "ua", "va", "utc", "vtc"),
+    "c_sw": ("omga", "uc", "vc", "ua", "va", "ut", "vt", "divgd"),
+    "updatedzc": ("ws3",),
+    "riem_solver_c": ("pkc",),
+    "d_sw": ("crx", "cry", "xfx", "yfx", "diss_estd", "vt"),
+    "updatedzd": ("wsd",),
+    "riem_solver3": ("delz", "pkc", "pk3", "pe", "pk", "peln"),
+    "compute_geopotential": ("gz",),
+}
+
+
+def poisoned(case):
+    """case.before with NaN in the checked windows of the outputs the operator only writes."""
+    before = dict(case.before)
+    for var, win, nk, _, _ in case.checks:
+        if var in WRITE_ONLY.get(case.name, ()):
+            a = before[var] = before[var].copy()
+            if a.ndim == 3:
+                a[win + (slice(0, nk),)] = np.nan
+            else:
+                a[win] = np.nan
+    return before
+
+
+def check_case(ops, case, scale_tol=1.0, report=None, sphere=False, poison=False):
     """Run the product operator on case.before and compare with case.after.  Returns {variable: error}."""
-    f = ops.run(case.name, case.before)
+    f = ops.run(case.name, poisoned(case) if poison else case.before)
     errs = {}
     bad = []
     for var, win, nk, tol, nz_frac in case.checks:

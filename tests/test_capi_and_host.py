@@ -247,3 +247,27 @@ def test_timer_and_kernel_times():
     timer = Timer()
     core.step_dynamics(state, timer)
     assert set(timer.hits) == {"DynCore", "TracerAdvection", "Remapping"} and all(v == 1 for v in timer.hits.values())
+
+
+def test_compare_counts_a_one_sided_nan_as_an_error():
+    """The comparison metric of every parity test (pace_amd.tile.compare, after util/pace/util/testing/comparison.py): NaN on both
+    sides passes, NaN or inf on ONE side is an infinite error -- also beside a near_zero floor -- and never a zero.  (It was a zero:
+    the NaN denominator failed `denom > 0` and took the branch meant for 0 / 0.)"""
+    import numpy as np
+
+    from pace_amd.tile import compare
+
+    ref = np.array([1.0, 2.0, 0.0, np.nan])
+    assert compare(ref, ref.copy()) == 0.0
+    assert compare(np.array([0.0, 0.0]), np.array([0.0, -0.0])) == 0.0
+    for bad in (np.nan, np.inf, -np.inf):
+        got = ref.copy()
+        got[1] = bad
+        assert compare(ref, got) == np.inf, bad
+        assert compare(got, ref) == np.inf, bad
+        assert compare(ref, got, near_zero=1e-3) == np.inf, bad
+    got = ref.copy()
+    got[3] = 5.0  # the reference has NaN, the result a number
+    assert compare(ref, got) == np.inf
+    assert compare(np.array([1.0, 1e-9]), np.array([1.0, 3e-9]), near_zero=1e-6) == 0.0
+    assert abs(compare(np.array([1.0]), np.array([1.0 + 1e-6])) - 1e-6) < 1e-9

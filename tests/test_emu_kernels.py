@@ -905,83 +905,24 @@ def test_d_sw_other_namelists_emulated_vs_oracle(emu_lib, cfg):
 @pytest.mark.parametrize("nz", [32, 91, 127])
 def test_other_level_counts_emulated_vs_oracle(emu_lib, nz):
     """Nothing in d_sw / riem_solver3 may assume the 79 layers of the baseline configuration: 32, 91 and 127 layers against
-    the oracle (d_sw bit for bit, the column solver to the exp / log rounding)."""
-    from helpers import DSW_CFG
+    the oracle (d_sw bit for bit, the column solver to the exp / log rounding).  (The body: helpers.check_other_level_counts,
+    which tests/test_gpu_device_paths.py runs with the device library.)"""
+    from helpers import check_other_level_counts
 
-    from oracle import dgrid_sw, vertical
-    from pace_amd import synthetic
-    from pace_amd.fv3core import DGridShallowWaterLagrangianDynamicsConfig
-    from pace_amd.fv3core.stencils.d_sw import get_column_namelist
-
-    n = 12
-    metrics = synthetic.tile_metrics(n, nz)
-    s = synthetic.acoustic_state(metrics, n, nz)
-    env = Env(emu_lib, "cpu", metrics, n, nz)
-    colq = get_column_namelist(DGridShallowWaterLagrangianDynamicsConfig(**DSW_CFG), env.qf)
-    col = {k: (v.numpy() if hasattr(v, "numpy") else np.asarray(v))[:nz] for k, v in colq.items()}
-    out, _ = run_d_sw(env, col, {k: s[k] for k in DSW_ARGS}, s["dt"])
-    g = oracle_grid(metrics, n, nz)
-    a = {k: s[k].copy() for k in DSW_ARGS}
-    dgrid_sw.d_sw(g, col, DSW_CFG, dgrid_sw.DSWState(s["u"].shape), *[a[k] for k in DSW_ARGS], s["dt"])
-    for k in DSW_ARGS:
-        if k != "zh":
-            assert compare(a[k][dsw_window(k, n, nz)], out[k][dsw_window(k, n, nz)]) == 0.0, k
-    inp = {"cappa": s["cappa"], "zs": s["zs"], "ws": s["ws"], "delz": s["delz"], "q_con": a["q_con"], "delp": a["delp"],
-           "pt": a["pt"], "zh": s["zh"], "p": s["pe"], "ppe": s["ppe"], "pk3": s["pk3"], "pk": s["pk"],
-           "log_p_interface": s["peln"], "w": a["w"]}
-    got = run_riem3(env, inp, False, s["dt"], metrics["ptop"])
-    b = {k: v.copy() for k, v in inp.items()}
-    vertical.riem_solver3(g, False, s["dt"], b["cappa"], metrics["ptop"], b["zs"], b["ws"], b["delz"], b["q_con"], b["delp"], b["pt"],
-                          b["zh"], b["p"], b["ppe"], b["pk3"], b["pk"], b["log_p_interface"], b["w"], p_fac=0.05)
-    for k in ("delz", "zh", "ppe", "pk3", "w"):
-        nk = nz if k in ("delz", "w") else nz + 1
-        assert compare(b[k][window(n, 0, 0, nk)], got[k][window(n, 0, 0, nk)], near_zero=1e-9 * float(np.abs(b[k]).max())) < 5e-6, k
+    check_other_level_counts(emu_lib, "cpu", nz, dsw_tol=0.0)
 
 
-@pytest.mark.parametrize("n", [13, 16, 40])
+@pytest.mark.parametrize("n", [13, 16, 20, 40])
 def test_riem_column_windows_emulated_vs_oracle(emu_lib, n):
     """The column solver's sixteen-column windows (k_riem3f.hip ColumnWindows) in each of their shapes: the whole row inside
-    one window with only a head (13), head and tail side by side in one workgroup (16: the shape of C48 / C96 / C192), head, a
-    whole window and a tail that do not fit together (40) -- riem_solver3 on the compute domain and riem_solver_c on
-    compute + 1 (other window bounds), against the oracle."""
-    from oracle import vertical
-    from pace_amd import synthetic
-    from pace_amd.fv3core.stencils.riem_solver_c import NonhydrostaticVerticalSolverCGrid
+    one window with only a head (13), head and tail side by side in one workgroup (16: the shape of C48 / C96 / C192), a head and
+    a tail that do not fit together with no whole window between them (20), head, a whole window and a tail that do not fit
+    together (40) -- riem_solver3 on the compute domain and riem_solver_c on
+    compute + 1 (other window bounds), against the oracle.  (The body: helpers.check_riem_column_windows, which
+    tests/test_gpu_device_paths.py runs with the device library.)"""
+    from helpers import check_riem_column_windows
 
-    nz = 33
-    metrics = synthetic.tile_metrics(n, nz)
-    s = synthetic.acoustic_state(metrics, n, nz)
-    env = Env(emu_lib, "cpu", metrics, n, nz)
-    g = oracle_grid(metrics, n, nz)
-    inp = {"cappa": s["cappa"], "zs": s["zs"], "ws": s["ws"], "delz": s["delz"], "q_con": s["q_con"], "delp": s["delp"],
-           "pt": s["pt"], "zh": s["zh"], "p": s["pe"], "ppe": s["ppe"], "pk3": s["pk3"], "pk": s["pk"],
-           "log_p_interface": s["peln"], "w": s["w"]}
-    got = run_riem3(env, inp, True, s["dt"], metrics["ptop"])
-    b = {k: v.copy() for k, v in inp.items()}
-    vertical.riem_solver3(g, True, s["dt"], b["cappa"], metrics["ptop"], b["zs"], b["ws"], b["delz"], b["q_con"], b["delp"], b["pt"],
-                          b["zh"], b["p"], b["ppe"], b["pk3"], b["pk"], b["log_p_interface"], b["w"], p_fac=0.05)
-    for k in ("delz", "zh", "ppe", "pk3", "w", "p", "pk", "log_p_interface"):
-        nk = nz if k in ("delz", "w") else nz + 1
-        assert compare(b[k][window(n, 0, 0, nk)], got[k][window(n, 0, 0, nk)], near_zero=1e-9 * float(np.abs(b[k]).max())) < 5e-6, k
-        # nothing outside the compute domain is written
-        outside = np.ones(b[k].shape, dtype=bool)
-        outside[window(n, 0, 0, nk)] = False
-        outside[:, :, nk:] = False
-        assert np.array_equal(got[k][outside], inp[k][outside]), k
-    # riem_solver_c: compute + 1
-    solver = NonhydrostaticVerticalSolverCGrid(env.stencil_factory, env.qf, 0.05)
-    a = {k: s[k].copy() for k in ("cappa", "pt", "q_con", "delp", "zh", "w")}
-    f = {k: env.q3(v) for k, v in a.items()}
-    hs = s["zs"] * 9.80665
-    ws3 = np.ascontiguousarray(s["ws"])
-    pef = env.q3(np.zeros_like(s["zh"]))
-    solver(0.5 * s["dt"], f["cappa"], float(metrics["ptop"]), env.q2(hs), env.q2(ws3), f["pt"], f["q_con"], f["delp"], f["zh"], pef, f["w"])
-    ref_pef = np.zeros_like(s["zh"])
-    vertical.riem_solver_c(g, 0.5 * s["dt"], a["cappa"], float(metrics["ptop"]), hs, ws3, a["pt"], a["q_con"], a["delp"], a["zh"], ref_pef,
-                           a["w"], p_fac=0.05)
-    W = (slice(2, 4 + n), slice(2, 4 + n), slice(0, nz + 1))
-    assert compare(ref_pef[W], pef.numpy()[W]) < 5e-14
-    assert compare(a["zh"][W], f["zh"].numpy()[W]) < 5e-14
+    check_riem_column_windows(emu_lib, "cpu", n, nz=33, last_call=True)
 
 
 @pytest.mark.parametrize("order", [2, 4])
