@@ -7,6 +7,7 @@
 import numpy as np
 import pytest
 
+from remap_columns import remap_columns
 from helpers import (acoustic_errors, check_tracer_outputs, run_in_child, DSW_ARGS, DSW_CFG, RIEM_ARGS, Env, column_for_levels, compare, dsw_window, expand_riem_fixture, golden,
                      oracle_grid, run_d_sw, run_riem3, window)
 
@@ -302,30 +303,9 @@ def test_tracer_advection_six_tiles_matches_reference_run(lib, tmp_path):
 
 def test_ord8_transport_matches_oracle_c96(lib):
     """Monotone PPM at C96 x 7 levels: edge, corner and interior workgroups of the ord-8 kernel against the oracle."""
-    import torch
+    from helpers import check_ord8_transport
 
-    from oracle import dgrid_sw
-    from oracle import ppm_transport as tr
-    from pace_amd import synthetic
-    from pace_amd.fv3core.stencils.fvtp2d import FiniteVolumeTransport
-
-    n, nz = 96, 7
-    metrics = synthetic.tile_metrics(n, nz)
-    s = synthetic.acoustic_state(metrics, n, nz)
-    g = oracle_grid(metrics, n, nz)
-    for k in ("crx", "cry", "xfx", "yfx"):
-        s[k] = np.zeros_like(s["pt"])
-    dgrid_sw.fxadv(g, s["uc"], s["vc"], s["crx"], s["cry"], s["xfx"], s["yfx"], np.zeros_like(s["pt"]), np.zeros_like(s["pt"]), s["dt"])
-    env = Env(lib, "cuda", metrics, n, nz)
-    op = FiniteVolumeTransport(env.stencil_factory, env.qf, env.grid_data, env.damping, 0, 8)
-    f = {k: env.q3(s[k]) for k in ("pt", "crx", "cry", "xfx", "yfx")}
-    fx, fy = env.q3(), env.q3()
-    op(f["pt"], f["crx"], f["cry"], f["xfx"], f["yfx"], fx, fy)
-    torch.cuda.synchronize()
-    ofx, ofy = np.zeros_like(s["pt"]), np.zeros_like(s["pt"])
-    tr.fvtp2d(g, s["pt"].copy(), s["crx"], s["cry"], s["xfx"], s["yfx"], ofx, ofy, 8)
-    assert np.array_equal(ofx[window(n, 1, 0, nz)], fx.numpy()[window(n, 1, 0, nz)])
-    assert np.array_equal(ofy[window(n, 0, 1, nz)], fy.numpy()[window(n, 0, 1, nz)])
+    check_ord8_transport(lib, "cuda", 96, 7)
 
 
 @pytest.mark.parametrize("name", sorted(__import__("helpers").REMAP_CASES))
@@ -340,24 +320,6 @@ def test_map_single_matches_reference_run(lib, name):
     assert np.array_equal(out, d[name + "_out"][:, :, :REMAP_KM])
 
 
-def _remap_columns(n, km, seed, deform):
-    """Synthetic columns: hybrid-like target interfaces, a source coordinate deformed by up to `deform` layers, a smooth field
-    plus noise (so the monotonicity constraints engage)."""
-    rng = np.random.default_rng(seed)
-    ni = n + 7
-    sig = np.linspace(0.0, 1.0, km + 1) ** 1.6
-    ps = 1.0e5 * (1.0 + 0.02 * rng.random((ni, ni)))
-    ptop = 300.0
-    pe2 = ptop + (ps - ptop)[:, :, None] * sig[None, None, :]
-    amp = deform / km * rng.random((ni, ni))
-    s1 = sig[None, None, :] + amp[:, :, None] * np.sin(2.0 * np.pi * sig)[None, None, :]
-    s1[:, :, 0], s1[:, :, km] = 0.0, 1.0
-    pe1 = ptop + (ps - ptop)[:, :, None] * s1
-    q = np.zeros((ni, ni, km + 1))
-    q[:, :, :km] = 250.0 + 40.0 * np.cos(3.0 * np.pi * sig[:km])[None, None, :] + 3.0 * rng.standard_normal((ni, ni, km))
-    return q, pe1, pe2
-
-
 @pytest.mark.parametrize("kord,iv", [(9, 1), (9, 0), (10, 1), (9, -1), (9, -2)])
 def test_map_single_matches_oracle_c48(lib, kord, iv):
     """All levels, 48 x 48 columns, strongly deformed coordinate (up to 3 layers): bit-exact against the oracle."""
@@ -369,7 +331,7 @@ def test_map_single_matches_oracle_c48(lib, kord, iv):
 
     n, km = 48, 79
     env = Env(lib, "cuda", synthetic.tile_metrics(n, km), n, km)
-    q, pe1, pe2 = _remap_columns(n, km, seed=3 + kord + iv, deform=3.0)
+    q, pe1, pe2 = remap_columns(n, km, seed=3 + kord + iv, deform=3.0)
     qs = 0.1 * q[:, :, km - 1]
     fq, f1, f2, fs = env.q3(q), env.q3(pe1), env.q3(pe2), env.q2(qs)
     MapSingle(env.stencil_factory, env.qf, kord, iv, ["x", "y", "z"])(fq, f1, f2, qs=fs if iv == -2 else None, qmin=200.0 if iv == 1 else 0.0)
@@ -390,7 +352,7 @@ def test_map_single_c192_properties(lib):
 
     n, km = 192, 79
     env = Env(lib, "cuda", synthetic.tile_metrics(n, km), n, km)
-    q, pe1, pe2 = _remap_columns(n, km, seed=17, deform=2.5)
+    q, pe1, pe2 = remap_columns(n, km, seed=17, deform=2.5)
     w = (slice(3, 3 + n), slice(3, 3 + n))
     op = MapSingle(env.stencil_factory, env.qf, 9, 1, ["x", "y", "z"])
     fq, f1, f2 = env.q3(q), env.q3(pe1), env.q3(pe2)

@@ -275,11 +275,11 @@ def test_c384x91_f32_map_single_sampled_columns_match_oracle(kord, iv):
     from oracle import remapping
     from pace_amd import _lib, synthetic
     from pace_amd.fv3core.stencils.map_single import MapSingle
-    from test_gpu_parity import _remap_columns
+    from remap_columns import remap_columns
 
     n, km = C384["n"], C384["nz"]
     env = Env(_lib.load(32), "cuda", synthetic.tile_metrics(n, km), n, km)
-    q, pe1, pe2 = _remap_columns(n, km, seed=11 + kord + iv, deform=1.2)
+    q, pe1, pe2 = remap_columns(n, km, seed=11 + kord + iv, deform=1.2)
     qs = 0.1 * q[:, :, km - 1]
     qmin = 200.0 if iv == 1 else 0.0
     fq, f1, f2, fs = env.q3(q), env.q3(pe1), env.q3(pe2), env.q2(qs)

@@ -77,6 +77,31 @@ def test_allocations_are_guarded_when_asked():
     assert torch.isnan(torch.empty(5, dtype=torch.float64)).all()
 
 
+def _guarded_pytest(mode, files):
+    """The emulated tests of `files` in one child pytest without workers, whose session fixture (tests/conftest.py,
+    PACE_GUARD_MODE) guards every allocation, after the sentinel test_allocations_are_guarded_when_asked.  The child has to end
+    clean with nothing failed or skipped and the sentinel passed.  Returns (the ids that passed, the end of its output)."""
+    env = dict(os.environ, PACE_GUARD_MODE=mode, PACE_EMU_GUARD="1")
+    env.pop("PYTEST_XDIST_WORKER", None)  # (the child is a pytest of its own, not a worker of this one)
+    env.pop("PYTEST_XDIST_WORKER_COUNT", None)
+    env.pop("PYTEST_CURRENT_TEST", None)
+    # (--capture=sys: what the emulator and the fault handler write to the process's own stderr when a kernel dies is not lost)
+    here = os.path.join(ROOT, "tests")
+    command = [sys.executable, "-X", "faulthandler", "-m", "pytest", "-n0", "-m", "not gpu", "-p", "no:cacheprovider", "-q", "-rp",
+               "--capture=sys", "test_guard_pages.py::test_allocations_are_guarded_when_asked", *files]
+    p = subprocess.run(command, cwd=here, capture_output=True, text=True, timeout=1200, env=env)
+    tail = p.stdout[-3000:] + "\n" + p.stderr[-3000:]
+    assert p.returncode == 0, f"the guarded run ({mode}) ended with {p.returncode}:\n{tail}"
+    assert " passed" in p.stdout and "failed" not in p.stdout.splitlines()[-1] and "skipped" not in p.stdout.splitlines()[-1], tail
+    # ... and it was a guarded run of what it is meant to be: the sentinel above passed in the child (the wrappers were in place),
+    # every file contributed
+    passed = set(re.findall(r"^PASSED (\S+)", p.stdout, flags=re.M))
+    assert "test_guard_pages.py::test_allocations_are_guarded_when_asked" in passed, tail
+    for name in files:
+        assert any(t.startswith(name + "::") for t in passed), (name, tail)
+    return passed, tail
+
+
 @pytest.mark.parametrize("mode", ["over", "under"])
 def test_physics_side_with_guard_pages(mode):
     """The moist side -- k_satadj.hip, k_subgridz.hip, k_updphys.hip, k_microphys.hip, k_physics.hip -- under guard pages: every
@@ -86,27 +111,34 @@ def test_physics_side_with_guard_pages(mode):
     delp[a - sk] from level 1 on, clamp their chunked loads and index 1-D edge vectors by the storage's i: an access one
     element outside ends the child, and the emulator names the kernel.  (Not seen: an overrun of exactly the one spare double
     every workspace has, and the padding of Quantity rows.)"""
-    env = dict(os.environ, PACE_GUARD_MODE=mode, PACE_EMU_GUARD="1")
-    env.pop("PYTEST_XDIST_WORKER", None)  # (the child is a pytest of its own, not a worker of this one)
-    env.pop("PYTEST_XDIST_WORKER_COUNT", None)
-    env.pop("PYTEST_CURRENT_TEST", None)
-    # (--capture=sys: what the emulator and the fault handler write to the process's own stderr when a kernel dies is not lost)
-    here = os.path.join(ROOT, "tests")
-    command = [sys.executable, "-X", "faulthandler", "-m", "pytest", "-n0", "-m", "not gpu", "-p", "no:cacheprovider", "-q", "-rp",
-               "--capture=sys", "test_guard_pages.py::test_allocations_are_guarded_when_asked", *PHYSICS_SIDE]
-    p = subprocess.run(command, cwd=here, capture_output=True, text=True, timeout=1200, env=env)
-    tail = p.stdout[-3000:] + "\n" + p.stderr[-3000:]
-    assert p.returncode == 0, f"the guarded run ({mode}) ended with {p.returncode}:\n{tail}"
-    assert " passed" in p.stdout and "failed" not in p.stdout.splitlines()[-1] and "skipped" not in p.stdout.splitlines()[-1], tail
-    # ... and it was a guarded run of what it is meant to be: the sentinel above passed in the child (the wrappers were in place),
-    # every file contributed, the C68 cases of all five operators among them
-    passed = set(re.findall(r"^PASSED (\S+)", p.stdout, flags=re.M))
-    assert "test_guard_pages.py::test_allocations_are_guarded_when_asked" in passed, tail
-    for name in PHYSICS_SIDE:
-        assert any(t.startswith(name + "::") for t in passed), (name, tail)
+    passed, tail = _guarded_pytest(mode, PHYSICS_SIDE)
+    # the C68 cases of all five operators among them
     for case in ("test_microphysics_c68[emulated-base]", "test_microphysics_c68[emulated-sub2]", "test_microphysics_c68[emulated-mptime]",
                  "test_microphysics_c68[emulated-dry]", "test_microphysics_c68[emulated-accum]", "test_physics_c68[emulated]",
                  "test_physics_to_dycore_c68[emulated]", "test_dry_convective_adjust_c68[emulated-base]",
                  "test_sat_adjust_c68[emulated-mid]", "test_l2e_sat_adj_emulated[True]"):
         assert any(t.endswith("::" + case) for t in passed), (case, tail)
     assert len(passed) >= 100, len(passed)  # (81 before the C68 cases and the workspace tests, 109 with them)
+
+
+VERTICAL_SIDE = ["test_vertical_edges.py"]
+
+
+@pytest.mark.parametrize("mode", ["over", "under"])
+def test_vertical_side_with_guard_pages(mode):
+    """The remapping and column kernels -- k_remap.hip, k_l2e.hip, k_dycore.hip -- under guard pages: every emulated case of
+    tests/test_vertical_edges.py in a guarded child pytest (_guarded_pytest).  k_remap_interfaces loads a chunk of eight levels
+    ahead with clamps at both ends of the column (level -2 .. km), k_remap_layers reads pe1[L + 1] while it walks, the remap
+    workspace has km + 1 levels per field and fillz prefetches two levels ahead: at 6 .. 128 levels, at C64 staggered in x (one
+    live lane in a second block) and at C68 an access one element before ("under") or past ("over") an array ends the child."""
+    passed, tail = _guarded_pytest(mode, VERTICAL_SIDE)
+    for case in ("test_map_single_cross_product[emulated-64-9-xstag-9]", "test_map_single_cross_product[emulated-64-9-xstag-10]",
+                 "test_map_single_cross_product[emulated-64-9-unstag-9]", "test_map_single_cross_product[emulated-64-9-ystag-10]",
+                 "test_map_single_level_counts[emulated-68-12]", "test_map_single_level_counts[emulated-13-6]",
+                 "test_map_single_level_counts[emulated-13-128]", "test_mapn_tracer_nine_tracers[emulated-68-7-10]",
+                 "test_fillz_nine_patterns[emulated-68-7]", "test_fillz_nine_patterns[emulated-13-4]",
+                 "test_neg_adj3_level_counts[emulated-68-7]", "test_lagrangian_to_eulerian_level_counts[emulated-68-9-False]",
+                 "test_lagrangian_to_eulerian_level_counts[emulated-13-6-False]", "test_c2l_and_preamble_windows[emulated-64-2-2]",
+                 "test_c2l_and_preamble_windows[emulated-68-5-4]", "test_ord8_transport_at_device_chain_shapes[emulated-40-3]"):
+        assert any(t.endswith("::" + case) for t in passed), (case, tail)
+    assert len(passed) >= 52, len(passed)  # (the sentinel + the 52 emulated cases of the module, test_column_makers among them)
