@@ -565,6 +565,21 @@ int pace_physics_tendencies_to_dycore(const pace_geom_t* geom, pace_real_t* cons
                                       const pace_real_t* const* before, pace_real_t* const* tracers, const pace_real_t* prsi,
                                       pace_real_t* delp, double rdt, void* stream);
 
+/* ---- The driver's check of the state (driver/pace/driver/safety_checks.py:80-110): the extrema and the NaN counts of up to
+ * PACE_STATE_EXTREMA_MAX_FIELDS fields in one launch pair, both storage types, no host synchronisation, no atomics (the result
+ * does not depend on the order workgroups run in).  fields: HOST array of nfields device pointers; compute_only: HOST array of
+ * nfields flags.  The window of field m is its compute domain, origin (3, 3, 0), extent (n, n, nk), where compute_only[m] != 0,
+ * and otherwise the logical storage (n + 7, n + 7, nk + 1); the padding of a row beyond n + 7 is never read.  out: DEVICE
+ * array of 4 * nfields doubles, per field
+ *   [0] the minimum of the values in the window that are no NaN (+inf if there is none), [1] their maximum (-inf),
+ *   [2] the number of NaNs in the window, [3] the number of NaNs in the compute domain
+ * (+-inf are values).  workspace: at least pace_state_extrema_workspace_bytes(geom) bytes of device memory, whatever nfields is;
+ * it holds nothing between calls and need not be cleared.  nfields < 1 or > PACE_STATE_EXTREMA_MAX_FIELDS: PACE_ERR_ARG. */
+#define PACE_STATE_EXTREMA_MAX_FIELDS 16
+int64_t pace_state_extrema_workspace_bytes(const pace_geom_t* geom);
+int pace_state_extrema(const pace_geom_t* geom, const pace_real_t* const* fields, const int* compute_only, int nfields,
+                       void* workspace, double* out, void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

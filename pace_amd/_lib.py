@@ -116,6 +116,9 @@ class MicrophysicsConfig(C.Structure):  # include/pace_hip.h pace_microphysics_c
     )
 
 
+STATE_EXTREMA_MAX_FIELDS = 16  # include/pace_hip.h PACE_STATE_EXTREMA_MAX_FIELDS
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -211,6 +214,8 @@ _PROTOS = {
     "pace_fill_gfs_delp": (C.c_int, [_P(Geom), c_dp, c_dp, C.c_double, C.c_void_p]),
     "pace_phys_thermo_pressure": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 11 + [C.c_double, C.c_void_p]),
     "pace_update_dwinds_phys": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [_P(C.c_void_p)] * 4 + [c_dp] * 4 + [C.c_double, C.c_void_p]),
+    "pace_state_extrema_workspace_bytes": (C.c_int64, [_P(Geom)]),
+    "pace_state_extrema": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_int), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

@@ -664,6 +664,18 @@ int pace_physics_tendencies_to_dycore(const pace_geom_t* geom, real* const* tend
   return launch_physics_tendencies_to_dycore(make_geo(geom), tendencies, updated, before, tracers, prsi, delp, rdt, S(stream));
 }
 
+int64_t pace_state_extrema_workspace_bytes(const pace_geom_t* geom) {
+  return (geom && geom_check(geom) == PACE_OK) ? (int64_t)state_extrema_workspace_bytes(make_geo(geom)) : 0;
+}
+
+int pace_state_extrema(const pace_geom_t* geom, const real* const* fields, const int* compute_only, int nfields, void* workspace,
+                       double* out, void* stream) {
+  NEED(geom && fields && compute_only && workspace && out);
+  if (nfields < 1 || nfields > PACE_STATE_EXTREMA_MAX_FIELDS) return PACE_ERR_ARG;
+  if (!all_set((const void* const*)fields, nfields)) return PACE_ERR_ARG;
+  return launch_state_extrema(make_geo(geom), fields, compute_only, nfields, workspace, out, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

@@ -275,6 +275,11 @@ int launch_physics_update_state(const Geo& g, const real* const* x, const real* 
 int launch_physics_tendencies_to_dycore(const Geo& g, real* const* tendencies, const real* const* updated,
                                         const real* const* before, real* const* tracers, const real* prsi, real* delp,
                                         double rdt, hipStream_t st);
+// k_driver.hip
+size_t state_extrema_workspace_bytes(const Geo& g);
+int launch_state_extrema(const Geo& g, const real* const* fields, const int* compute_only, int nfields, void* workspace,
+                         double* out, hipStream_t st);
+// k_dycore.hip
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);
 int launch_omega_from_w(const Geo& g, const real* delp, const real* delz, const real* w, real* omga, hipStream_t st);

@@ -1,0 +1,21 @@
+"""The reference's `pace.driver`: configuration, state and main loop of a model run.
+
+    from pace.driver import Driver, DriverConfig  ->  from pace_amd.driver import Driver, DriverConfig
+"""
+from .config import (  # noqa: F401
+    BaroclinicInit,
+    CreatesCommSelector,
+    DiagnosticsConfig,
+    DriverConfig,
+    GeneratedGridConfig,
+    GridInitializerSelector,
+    InitializerSelector,
+    NullCommConfig,
+    PerformanceConfig,
+    PredefinedStateInit,
+    RestartConfig,
+    TorchCommConfig,
+)
+from .driver import Driver  # noqa: F401
+from .safety_checks import SafetyChecker, VariableBounds  # noqa: F401
+from .state import DriverState, TendencyState  # noqa: F401

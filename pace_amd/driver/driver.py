@@ -1,0 +1,170 @@
+"""Driver -- the model's main loop (reference: driver/pace/driver/driver.py:372-745).
+
+    driver = Driver(DriverConfig.from_yaml("config.yaml"))
+    driver.step_all()
+    driver.cleanup()
+
+A step is the reference's (driver.py:618-640): DynamicalCore.step_dynamics, DycoreToPhysics, Physics, UpdateAtmosphereState,
+each a class of its own that can also be called by hand; the driver only strings them together, advances the time and, every
+safety_check_frequency steps, checks the state (SafetyChecker: one launch pair and one transfer).  What the reference's
+constructor does for DaCe, build modes, diagnostics, restarts and the performance collector's files is not here.
+
+One deliberate departure: the reference's constructor registers its four variables with SafetyChecker.register_variable, which
+raises on a second registration, so two reference Drivers cannot exist in one process.  Six of these do (one per tile on
+threads): the constructor registers each of the four only if it is absent, under a lock.  register_variable itself keeps raising.
+"""
+import threading
+import warnings
+
+from .. import _lib
+from ..fv3core import DynamicalCore
+from ..physics import Physics
+from ..stencils import update_atmos_state
+from ..util import CubedSphereCommunicator, Timer
+from .config import DriverConfig
+from .safety_checks import SafetyChecker
+
+_REGISTRATION_LOCK = threading.Lock()
+# driver.py:536-539
+_SAFETY_CHECKS = (("ua", -200, 200), ("va", -200, 200), ("delp", -1.0, 4000), ("pt", 100, 380))
+
+
+class PerformanceCollector:
+    """The two timers of the reference's collector (performance/collector.py): `total_timer` for initialization and the whole
+    run, `timestep_timer` for the main loop and what the dynamical core clocks inside it.  No file is written."""
+
+    def __init__(self):
+        self.total_timer = Timer()
+        self.timestep_timer = Timer()
+
+
+class Driver:
+    def __init__(self, config: DriverConfig, comm=None, lib=None, device=None):
+        """
+        Args:
+            config: driver configuration
+            comm: communication object behaving like pace_amd.util.TorchDistComm / ThreadComm / NullComm; default: what
+                config.comm_config creates
+            lib: the kernel library (default: the product library, pace_amd._lib.load())
+            device: where the fields live (default: the current device; "cpu" with the emulation test library)
+        """
+        from ..tile import setup_factories
+
+        self.config: DriverConfig = config
+        self.time = self.config.start_time
+        self.comm_config = config.comm_config
+        self.comm = comm if comm is not None else config.comm_config.get_comm()
+        self.lib = lib if lib is not None else _lib.load()
+        if device is None:
+            if "emulation" in self.lib.version():
+                device = "cpu"
+            else:
+                import torch
+
+                device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+        self.performance_collector = PerformanceCollector()
+        with self.performance_collector.total_timer.clock("initialization"):
+            communicator = CubedSphereCommunicator(self.comm, device=device, lib=self.lib)
+            self.communicator = communicator
+            self._warn_about_what_is_ignored()
+            _, self.quantity_factory, _, self.stencil_factory = setup_factories(
+                self.lib, device, config.nx_tile, config.nz, layout=config.layout, stencil_config=config.stencil_config,
+                communicator=communicator)
+            damping_coefficients, driver_grid_data, grid_data = self.config.get_grid(
+                quantity_factory=self.quantity_factory, communicator=communicator)
+            self.state = self.config.get_driver_state(
+                quantity_factory=self.quantity_factory, communicator=communicator, damping_coefficients=damping_coefficients,
+                driver_grid_data=driver_grid_data, grid_data=grid_data)
+            self._start_time = self.config.initialization.start_time
+            self.dycore = DynamicalCore(
+                comm=communicator, grid_data=self.state.grid_data, stencil_factory=self.stencil_factory,
+                quantity_factory=self.quantity_factory, damping_coefficients=self.state.damping_coefficients,
+                config=self.config.dycore_config, timestep=self.config.timestep, phis=self.state.dycore_state.phis,
+                state=self.state.dycore_state)
+            if not config.dycore_only and not config.disable_step_physics:
+                self.physics = Physics(stencil_factory=self.stencil_factory, quantity_factory=self.quantity_factory,
+                                       grid_data=self.state.grid_data, namelist=self.config.physics_config,
+                                       active_packages=["microphysics"])
+            else:
+                # Make sure those are set to None to raise any issues
+                self.physics = None
+            if not config.disable_step_physics:
+                couple = not self.config.dycore_only
+                self.dycore_to_physics = update_atmos_state.DycoreToPhysics(
+                    stencil_factory=self.stencil_factory, quantity_factory=self.quantity_factory,
+                    dycore_config=self.config.dycore_config, do_dry_convective_adjust=config.do_dry_convective_adjustment,
+                    dycore_only=self.config.dycore_only, couple_physics=couple)
+                self.end_of_step_update = update_atmos_state.UpdateAtmosphereState(
+                    stencil_factory=self.stencil_factory, grid_data=self.state.grid_data, namelist=self.config.physics_config,
+                    comm=communicator, grid_info=self.state.driver_grid_data, state=self.state.dycore_state,
+                    quantity_factory=self.quantity_factory, dycore_only=self.config.dycore_only,
+                    apply_tendencies=self.config.apply_tendencies, tendency_state=self.state.tendency_state,
+                    couple_physics=couple)
+            else:
+                # Make sure those are set to None to raise any issues
+                self.dycore_to_physics = None
+                self.end_of_step_update = None
+        self._time_run = self.config.start_time
+        self.safety_checker = SafetyChecker(self.lib)
+        with _REGISTRATION_LOCK:  # (see the module's docstring)
+            for name, minimum, maximum in _SAFETY_CHECKS:
+                if name not in SafetyChecker.checks:
+                    SafetyChecker.register_variable(name, minimum, maximum, compute_domain_only=True)
+
+    def _warn_about_what_is_ignored(self):
+        """One warning per run (rank 0's) for the settings of a reference file that are kept and not acted on."""
+        if self.comm.Get_rank() != 0:
+            return
+        ignored = []
+        if self.config.diagnostics_config.path is not None:
+            ignored.append(f"diagnostics_config (path {self.config.diagnostics_config.path!r}): no diagnostics are written, "
+                           "output_initial_state and output_frequency have no effect")
+        requested = getattr(self.config.stencil_config, "requested_backend", None)
+        if requested is not None and requested != self.config.stencil_config.backend:
+            ignored.append(f"stencil_config.compilation_config.backend {requested!r}: the backend is "
+                           f"{self.config.stencil_config.backend!r}")
+        if ignored:
+            warnings.warn("pace_amd.driver ignores " + "; ".join(ignored), UserWarning, stacklevel=3)
+
+    def _end_of_step_actions(self, step: int):
+        """
+        Gather operations unrelated to computation.
+        """
+        self.time += self.config.timestep
+        if self.config.safety_check_frequency and ((step + 1) % self.config.safety_check_frequency) == 0:
+            with self.performance_collector.total_timer.clock("safety_check"):
+                self.safety_checker.check_state(self.state.dycore_state)
+
+    def _critical_path_step_all(self, steps_count: int, timer: Timer, dt: float):
+        """Start of code path where performance is critical."""
+        for step in range(steps_count):
+            with timer.clock("mainloop"):
+                self.dycore.step_dynamics(state=self.state.dycore_state, timer=timer)
+                if not self.config.disable_step_physics:
+                    self.dycore_to_physics(dycore_state=self.state.dycore_state, physics_state=self.state.physics_state,
+                                           tendency_state=self.state.tendency_state, timestep=float(dt))
+                    if not self.config.dycore_only:
+                        self.physics(self.state.physics_state, timestep=float(dt))
+                    self.end_of_step_update(dycore_state=self.state.dycore_state, phy_state=self.state.physics_state,
+                                            u_dt=self.state.tendency_state.u_dt, v_dt=self.state.tendency_state.v_dt,
+                                            pt_dt=self.state.tendency_state.pt_dt, dt=float(dt))
+            self._end_of_step_actions(step)
+
+    def step_all(self):
+        with self.performance_collector.total_timer.clock("total"):
+            self._critical_path_step_all(steps_count=self.config.n_timesteps(), timer=self.performance_collector.timestep_timer,
+                                         dt=self.config.timestep.total_seconds())
+
+    def sypd(self) -> float:
+        """Simulated years per day of wall time, as the reference reports it (performance/report.py:116-129): dt_atmos over the
+        mean time of a main-loop step, over 365; -999.0 before the first step."""
+        timer = self.performance_collector.timestep_timer
+        hits = timer.hits.get("mainloop", 0)
+        if hits == 0:
+            return -999.0
+        mainloop = timer.times["mainloop"] / hits
+        return 1.0 / 365.0 * (self.config.dt_atmos / mainloop)
+
+    def cleanup(self):
+        self.comm_config.cleanup(self.comm)

@@ -1,7 +1,7 @@
 """Namelist-style configuration dataclasses: the subset of fv3core/pace/fv3core/_config.py:59-476 the
 acoustic step reads, with the reference's field names and defaults for the baroclinic test case."""
 import dataclasses
-from typing import Tuple
+from typing import Any, Dict, Optional, Tuple
 
 
 @dataclasses.dataclass
@@ -154,6 +154,45 @@ class DynamicalCoreConfig:
     tau_v2l: float = 90.0
     # the dry convective adjustment's time scale in seconds (util/pace/util/namelist.py: fv_sg_adj = -1, off)
     fv_sg_adj: int = -1
+    # fields of the reference's flat configuration that nothing here reads: carried so that its files load and round-trip
+    # (defaults: util/pace/util/namelist.py NamelistDefaults)
+    ntiles: int = 6
+    do_qa: bool = True
+    tau_g2r: float = 600.0
+    tau_g2v: float = 1200.0
+    tau_v2g: float = 21600.0
+    ql_mlt: float = 2.0e-3
+    regional: bool = False
+    m_split: int = 0
+    namelist_override: Optional[str] = None
+
+    def __post_init__(self):
+        if self.namelist_override is not None:
+            raise NotImplementedError("namelist_override reads a Fortran namelist file: build the configuration by keyword or "
+                                      "with from_namelist_dict")
+
+    @classmethod
+    def from_namelist_dict(cls, values: Dict[str, Any]) -> "DynamicalCoreConfig":
+        """From the reference's FLAT dycore configuration (the `dycore_config` section of a driver yaml file, the fields of
+        fv3core/pace/fv3core/_config.py:150-420): every key is set in every place that keeps a field of that name -- this class,
+        AcousticDynamicsConfig, DGridShallowWaterLagrangianDynamicsConfig, RiemannConfig -- so that the copies of nord, d_con,
+        hord_tm, p_fac, hydrostatic, grid_type, n_split, k_split, ... agree.  Strict: a key that none of them has raises
+        ValueError and names itself, and so does a value of the wrong type (an int is taken for a float field)."""
+        config = cls()
+        places = (config, config.acoustic_dynamics, config.acoustic_dynamics.d_grid_shallow_water, config.acoustic_dynamics.riemann)
+        nested = ("acoustic_dynamics", "d_grid_shallow_water", "riemann")
+        for key, value in values.items():
+            found = False
+            for place in places:
+                field = {f.name: f for f in dataclasses.fields(place)}.get(key)
+                if field is None or key in nested:
+                    continue
+                setattr(place, key, strict_value(f"dycore_config.{key}", field.type, value))
+                found = True
+            if not found:
+                raise ValueError(f"dycore_config has no setting {key!r}")
+        config.__post_init__()
+        return config
 
     @property
     def n_sponge(self) -> int:
@@ -196,3 +235,29 @@ class RemappingConfig:
     do_sat_adj: bool = False
     hydrostatic: bool = False
     sat_adjust: SatAdjustConfig = dataclasses.field(default_factory=SatAdjustConfig)
+
+
+def strict_value(where: str, kind, value):
+    """`value` as a field of type `kind` (bool, int, float, str, Tuple[int, int], Optional[str]) takes it, or a ValueError that
+    names the setting: the strictness of the reference's dacite.Config(strict=True) for the types a configuration file holds."""
+    if kind in (Optional[str], "Optional[str]"):
+        if value is None or isinstance(value, str):
+            return value
+    elif kind in (Tuple[int, int], "Tuple[int, int]"):
+        if isinstance(value, (list, tuple)) and len(value) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in value):
+            return tuple(value)
+    elif kind in (bool, "bool"):
+        if isinstance(value, bool):
+            return value
+    elif kind in (int, "int"):
+        if isinstance(value, int) and not isinstance(value, bool):
+            return value
+    elif kind in (float, "float"):
+        if isinstance(value, (int, float)) and not isinstance(value, bool):
+            return float(value)
+    elif kind in (str, "str"):
+        if isinstance(value, str):
+            return value
+    else:
+        return value
+    raise ValueError(f"{where} = {value!r}: expected {getattr(kind, '__name__', kind)}")

@@ -1,6 +1,7 @@
 """CopyDycoreToPhysics and PhysicsToDycore -- the dycore_only = False halves of the reference's DycoreToPhysics and
 UpdateAtmosphereState (stencils/pace/stencils/update_atmos_state.py:95-145, 198-232 and 40-92, 312-341), as operators of their
-own: the constructors of those two classes keep refusing dycore_only=False.  A moist step is
+own; those two classes compose them when they are built with dycore_only=False and couple_physics=True (update_atmos_state.py),
+as pace_amd.driver.Driver builds them.  By hand, a moist step is
 
     DycoreToPhysics(..., dycore_only=True)(dycore_state, None, tendency_state, timestep)     the dry convective adjustment
     CopyDycoreToPhysics(...)(dycore_state, physics_state)

@@ -67,23 +67,32 @@ def dsw_live_window(name, n, nk):
     return dsw_window(name, n, nk)
 
 
+def setup_factories(lib, device, n, nz, layout=(1, 1), stencil_config=None, communicator=None):
+    """The sizer, quantity factory, grid indexing and stencil factory of one C<n> x <nz> tile on `device` for `lib` (whose
+    storage type the fields follow: float64 for libpace_hip.so, float32 for the _f32 build) -- what the reference's driver does
+    in _setup_factories (driver/pace/driver/driver.py:705-745).  Shared by Env and pace_amd.driver.Driver."""
+    import torch
+
+    from .dsl import CompilationConfig, GridIndexing, StencilConfig, StencilFactory
+    from .util import QuantityFactory, SubtileGridSizer
+
+    sizer = SubtileGridSizer.from_tile_params(nx_tile=n, ny_tile=n, nz=nz, n_halo=3, extra_dim_lengths={}, layout=layout)
+    qf = QuantityFactory(sizer, device=device, dtype=torch.float32 if lib.real_bytes == 4 else torch.float64)
+    grid_indexing = GridIndexing.from_sizer_and_communicator(sizer, communicator)
+    if stencil_config is None:
+        stencil_config = StencilConfig(compilation_config=CompilationConfig())
+    stencil_factory = StencilFactory(stencil_config, grid_indexing, lib=lib, quantity_factory=qf)
+    return sizer, qf, grid_indexing, stencil_factory
+
+
 class Env:
     """Everything a test needs to call the host classes on one device."""
 
     def __init__(self, lib, device, metrics, n, nz):
-        from .dsl import CompilationConfig, GridIndexing, StencilConfig, StencilFactory
-        from .util import QuantityFactory, SubtileGridSizer
         from .util.grid import DampingCoefficients, GridData
 
         self.n, self.nz = n, nz
-        self.sizer = SubtileGridSizer.from_tile_params(nx_tile=n, ny_tile=n, nz=nz, n_halo=3, extra_dim_lengths={}, layout=(1, 1))
-        import torch
-
-        # the storage type follows the library: float64 for libpace_hip.so, float32 for the _f32 build
-        self.qf = QuantityFactory(self.sizer, device=device, dtype=torch.float32 if lib.real_bytes == 4 else torch.float64)
-        self.grid_indexing = GridIndexing.from_sizer_and_communicator(self.sizer, None)
-        self.stencil_factory = StencilFactory(StencilConfig(compilation_config=CompilationConfig()), self.grid_indexing, lib=lib,
-                                              quantity_factory=self.qf)
+        self.sizer, self.qf, self.grid_indexing, self.stencil_factory = setup_factories(lib, device, n, nz)
         self.grid_data = GridData(self.qf, metrics)
         self.damping = DampingCoefficients(self.grid_data)
 

@@ -1,0 +1,112 @@
+"""Run the model from one of the reference's driver configuration files: pace_amd.driver.Driver, its step_all, one JSON line.
+
+    python tools/driver_run.py CONFIG.yaml [--steps N] [--device D] [--cpu-emulation]
+
+runs ONE rank (tile 0) with the `null` communicator -- its halos receive zeros, so this exercises the loop, not the weather --
+and, launched under torch.distributed.run as tools/dycore_run.py is,
+
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node 6 --master-addr 127.0.0.1 --master-port 29511 \\
+        tools/driver_run.py CONFIG.yaml [--steps N] [--cpu-emulation]
+
+the six tiles of the cubed sphere, one process per tile (RCCL on GPUs, gloo with --cpu-emulation).  --steps replaces the
+file's run length.  Rank 0 prints: workload, steps, ms per step (mean of the main loop's clock, the slowest rank), SYPD
+(Driver.sypd()), and the time of the safety check per call with its verdict: the checks the file asks for inside the loop
+(safety_check_frequency) and, after the run, three timed calls on the final state whose verdict is reported, not raised (a lone
+tile behind zero halos need not stay within the bounds).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("config")
+    ap.add_argument("--steps", type=int, default=None, help="run this many steps instead of the file's days / hours / minutes / seconds")
+    ap.add_argument("--device", default=None, help="one-rank runs: the device (default cuda:0)")
+    ap.add_argument("--cpu-emulation", action="store_true", help="the CPU emulation library (and gloo): a logic check, not a timing")
+    args = ap.parse_args()
+    import yaml
+
+    from pace_amd import _lib
+    from pace_amd.driver import Driver, DriverConfig
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    with open(args.config) as f:
+        settings = yaml.safe_load(f)
+    if world == 1:
+        settings["comm_config"] = {"type": "null", "config": {"rank": 0, "total_ranks": 6}}
+        device = "cpu" if args.cpu_emulation else (args.device or "cuda:0")
+    elif world == 6:
+        import torch.distributed as dist
+
+        local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+        if args.cpu_emulation:
+            dist.init_process_group(backend="gloo")
+            device = "cpu"
+        else:
+            dist.init_process_group(backend="nccl", device_id=torch.device(f"cuda:{local_rank}"))
+            device = f"cuda:{local_rank}"
+        settings["comm_config"] = {"type": "torch"}
+    else:
+        raise SystemExit("a cubed sphere has six tiles: launch six ranks, or one for a lone tile")
+    if device != "cpu":
+        torch.cuda.set_device(torch.device(device))
+    if args.steps is not None:
+        settings.update(days=0, hours=0, minutes=0, seconds=0)
+    config = DriverConfig.from_dict(settings)
+    if args.steps is not None:
+        config.seconds = int(round(args.steps * config.dt_atmos))
+        if config.n_timesteps() != args.steps:
+            raise SystemExit(f"--steps {args.steps} is no whole number of seconds at dt_atmos {config.dt_atmos}")
+    lib = _lib.Library(os.path.join(ROOT, "tests", "emu", "libpace_emu.so")) if args.cpu_emulation else _lib.load()
+    driver = Driver(config, lib=lib, device=device)
+    driver.step_all()
+    if device != "cpu":
+        torch.cuda.synchronize()
+    steps = config.n_timesteps()
+    loop, total = driver.performance_collector.timestep_timer, driver.performance_collector.total_timer
+    ms_per_step = 1e3 * loop.times.get("mainloop", 0.0) / max(1, loop.hits.get("mainloop", 0))
+    checks = total.hits.get("safety_check", 0)
+    verdict, check_times = "within bounds", []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        try:
+            driver.safety_checker.check_state(driver.state.dycore_state)  # (ends in its own transfer: the host clock sees all of it)
+        except RuntimeError as e:
+            verdict = " ".join(str(e).split())
+        check_times.append(1e3 * (time.perf_counter() - t0))
+    check_ms = sorted(check_times)[1]
+    sypd = driver.sypd()
+    if world == 6:
+        t = torch.tensor([ms_per_step], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        ms_per_step = float(t.item())
+        sypd = config.dt_atmos / (ms_per_step * 1e-3) / 365.0 if ms_per_step > 0 else sypd
+    pt = driver.state.dycore_state.pt.numpy()
+    if rank == 0:
+        what = "dycore only" if config.dycore_only else ("dycore, no physics coupling" if config.disable_step_physics else "dycore + microphysics")
+        print(json.dumps({
+            "workload": f"Driver.step_all, C{config.nx_tile}x{config.nz}L, {what}, n_split={config.dycore_config.n_split}, "
+                        f"k_split={config.dycore_config.k_split}, dt_atmos={config.dt_atmos:g} s, "
+                        + ("six tiles, one process per tile" if world == 6 else "ONE tile, null communicator (zero halos)"),
+            "n_gpus": 0 if args.cpu_emulation else world, "steps": steps, "ms_per_step": ms_per_step, "sypd": sypd,
+            "safety_checks_in_loop": checks, "safety_check_ms_per_call": check_ms, "safety_check": verdict,
+            "nan_fraction_pt": float((pt != pt).mean()),
+            "transport": "CPU emulation" if args.cpu_emulation else ("RCCL" if world == 6 else "none")}))
+    driver.cleanup()
+    if world == 6:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,6 +1,8 @@
 """Per-entry-point timing on the GPU box (HIP events on the launch stream), C192 x 79 by default.
 
     python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust,apply_physics,microphysics,physics]
+    python tools/kbench.py --only safety_check      the driver's state check against a plain torch restatement (host clock
+                                                    around whole checks, which end in their own synchronisation; medians)
 """
 import argparse
 import os
@@ -128,6 +130,11 @@ def main():
 
     apply_physics = ("fill_gfs_delp", "phys_thermo_pressure", "update_dwinds_phys")
     only = [x for x in args.only.split(",") if x]
+    if "safety_check" in only:
+        safety_check_bench(lib, env, s, n, nz, max(args.reps, 50))
+        only.remove("safety_check")
+        if not only:
+            return
     if "apply_physics" in only:
         only += list(apply_physics)
     ap_cases = {}
@@ -321,6 +328,65 @@ def main():
         us = float(np.median(ts))
         gbs = nfields * field_mb * 1e6 / (us * 1e-6) / 1e9
         print(f"{name:22s} {us:10.1f} {gbs:10.1f} {100*gbs/8000:8.2f}")
+
+
+def safety_check_bench(lib, env, s, n, nz, reps):
+    """SafetyChecker.check_state on the driver's four registered fields (ua, va, delp, pt; compute domain only) against the
+    reference's check restated with torch on the same views: amin, amax and isnan().any() per variable, each bound test and the
+    NaN test a host synchronisation of its own.  Both are timed with the host clock from an idle device to the decision (each
+    ends in its own synchronisation); the two alternate, medians are reported."""
+    import time
+    import types
+
+    from pace_amd.driver import SafetyChecker
+    from pace_amd.driver.driver import _SAFETY_CHECKS
+
+    state = types.SimpleNamespace(ua=env.q3(np.clip(s["ua"], -100.0, 100.0)), va=env.q3(np.clip(s["va"], -100.0, 100.0)), delp=env.q3(np.abs(s["delp"]) * 0 + 100.0),
+                                  pt=env.q3(np.abs(s["pt"]) * 0 + 300.0))
+    SafetyChecker.clear_all_checks()
+    for name, lo, hi in _SAFETY_CHECKS:
+        SafetyChecker.register_variable(name, lo, hi, compute_domain_only=True)
+    checker = SafetyChecker(lib)
+
+    def torch_check(st):
+        for variable, b in SafetyChecker.checks.items():
+            var = getattr(st, variable)
+            view = var.view[:] if b.compute_domain_only else var.data
+            min_value, max_value = view.amin(), view.amax()
+            if b.minimum_value and min_value < b.minimum_value:
+                raise RuntimeError(f"Variable {variable} is outside of its specified bounds")
+            if b.maximum_value and max_value > b.maximum_value:
+                raise RuntimeError(f"Variable {variable} is outside of its specified bounds")
+            if torch.isnan(var.view[:]).any():
+                raise RuntimeError(f"Variable {variable} contains a NaN value")
+
+    paths = {"hip": lambda: checker.check_state(state), "torch": lambda: torch_check(state)}
+    times = {k: [] for k in paths}
+    for k, fn in paths.items():  # warm-up: code objects, the checker's buffers, torch's reduction kernels
+        for _ in range(5):
+            fn()
+    for _ in range(reps):
+        for k, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append((time.perf_counter() - t0) * 1e6)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    dev = []
+    for _ in range(reps):  # the launch pair alone, device time
+        e0.record()
+        checker.extrema([state.ua, state.va, state.delp, state.pt], [True] * 4)
+        e1.record()
+        torch.cuda.synchronize()
+        dev.append(e0.elapsed_time(e1) * 1e3)
+    mb = 4 * n * n * nz * lib.real_bytes / 1e6
+    hip, ref = float(np.median(times["hip"])), float(np.median(times["torch"]))
+    print(f"safety_check C{n} x {nz}, four fields, {mb:.1f} MB read once; medians of {reps} alternating runs")
+    print(f"  check_state (pace_state_extrema, one transfer)   {hip:9.1f} us per call   (min {min(times['hip']):.1f}, "
+          f"launch pair + transfer in device events {np.median(dev):.1f} us = {mb * 1e6 / (np.median(dev) * 1e-6) / 1e9:.0f} GB/s of the read)")
+    print(f"  torch restatement (amin / amax / isnan().any())   {ref:9.1f} us per call   (min {min(times['torch']):.1f})")
+    print(f"  ratio torch / hip {ref / hip:.2f}")
+    SafetyChecker.clear_all_checks()
 
 
 if __name__ == "__main__":
