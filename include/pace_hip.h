@@ -580,6 +580,32 @@ int64_t pace_state_extrema_workspace_bytes(const pace_geom_t* geom);
 int pace_state_extrema(const pace_geom_t* geom, const pace_real_t* const* fields, const int* compute_only, int nfields,
                        void* workspace, double* out, void* stream);
 
+/* ---- The driver's diagnostics (driver/pace/driver/diagnostics.py:144-253): up to PACE_DIAG_MAX_ITEMS items gathered from the
+ * fields, transposed to the files' axis order, narrowed and written to one packed device buffer by ONE launch, both storage
+ * types, no atomics, no workspace, no host synchronisation.  items: HOST array of nitems items; out: DEVICE array of float32, or
+ * of float64 where out_is_double != 0.  Fields are stored x-fastest; an item's output is (x, y, z) in C order, z fastest:
+ *   PACE_DIAG_WINDOW3D         out[out_offset + (i * nj + j) * nk + k] = field(i0 + i, j0 + j, k0 + k)
+ *   PACE_DIAG_PLANE            out[out_offset + i * nj + j] = field(i0 + i, j0 + j); field points at element (0, 0) of a 2-D
+ *                              field or of ONE level of a 3-D one (the caller adds level * sk); k0 = 0, nk = 1
+ *   PACE_DIAG_COLUMN_INTEGRAL  out[out_offset + i * nj + j] = RGRAV * sum over k = k0 .. k0 + nk - 1 of field * weight, summed
+ *                              in double in ascending k with one accumulator, product then add
+ * The narrowing is a plain cast (round to nearest even, overflow to +-inf).  Nothing outside an item's window is read and
+ * nothing outside its ni * nj * nk (ni * nj) output elements is written.  PACE_ERR_ARG: nitems < 1 or > PACE_DIAG_MAX_ITEMS, an
+ * unknown kind, a window that is empty or outside the storage (n + 7, n + 7, nk + 1), a negative out_offset, a
+ * COLUMN_INTEGRAL without weight. */
+#define PACE_DIAG_MAX_ITEMS 32
+enum { PACE_DIAG_WINDOW3D = 0, PACE_DIAG_PLANE = 1, PACE_DIAG_COLUMN_INTEGRAL = 2 };
+typedef struct {
+  const pace_real_t* field;  /* element (0,0,0) of the storage, or of the level's plane for a PLANE item */
+  const pace_real_t* weight; /* COLUMN_INTEGRAL: delp; otherwise NULL */
+  int32_t kind;              /* PACE_DIAG_WINDOW3D | PACE_DIAG_PLANE | PACE_DIAG_COLUMN_INTEGRAL */
+  int32_t i0, j0, k0;        /* origin of the window in the storage */
+  int32_t ni, nj, nk;        /* extent (nk = 1 for PLANE) */
+  int64_t out_offset;        /* in output elements */
+} pace_diag_item_t;
+int pace_diag_pack(const pace_geom_t* geom, const pace_diag_item_t* items, int nitems, int out_is_double, void* out,
+                   void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

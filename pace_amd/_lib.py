@@ -119,6 +119,15 @@ class MicrophysicsConfig(C.Structure):  # include/pace_hip.h pace_microphysics_c
 STATE_EXTREMA_MAX_FIELDS = 16  # include/pace_hip.h PACE_STATE_EXTREMA_MAX_FIELDS
 
 
+DIAG_MAX_ITEMS = 32  # include/pace_hip.h PACE_DIAG_MAX_ITEMS
+DIAG_WINDOW3D, DIAG_PLANE, DIAG_COLUMN_INTEGRAL = 0, 1, 2  # include/pace_hip.h PACE_DIAG_*
+
+
+class DiagItem(C.Structure):  # include/pace_hip.h pace_diag_item_t
+    _fields_ = [("field", c_dp), ("weight", c_dp), ("kind", C.c_int32), ("i0", C.c_int32), ("j0", C.c_int32), ("k0", C.c_int32),
+                ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("out_offset", C.c_int64)]
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -216,6 +225,7 @@ _PROTOS = {
     "pace_update_dwinds_phys": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [_P(C.c_void_p)] * 4 + [c_dp] * 4 + [C.c_double, C.c_void_p]),
     "pace_state_extrema_workspace_bytes": (C.c_int64, [_P(Geom)]),
     "pace_state_extrema": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_int), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
+    "pace_diag_pack": (C.c_int, [_P(Geom), _P(DiagItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

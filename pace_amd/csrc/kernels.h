@@ -279,6 +279,8 @@ int launch_physics_tendencies_to_dycore(const Geo& g, real* const* tendencies, c
 size_t state_extrema_workspace_bytes(const Geo& g);
 int launch_state_extrema(const Geo& g, const real* const* fields, const int* compute_only, int nfields, void* workspace,
                          double* out, hipStream_t st);
+// k_diag.hip
+int launch_diag_pack(const Geo& g, const pace_diag_item_t* items, int nitems, int out_is_double, void* out, hipStream_t st);
 // k_dycore.hip
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);

@@ -5,7 +5,6 @@
 from .config import (  # noqa: F401
     BaroclinicInit,
     CreatesCommSelector,
-    DiagnosticsConfig,
     DriverConfig,
     GeneratedGridConfig,
     GridInitializerSelector,
@@ -15,6 +14,14 @@ from .config import (  # noqa: F401
     PredefinedStateInit,
     RestartConfig,
     TorchCommConfig,
+)
+from .diagnostics import (  # noqa: F401
+    Diagnostics,
+    DiagnosticsConfig,
+    MonitorDiagnostics,
+    NpzMonitor,
+    NullDiagnostics,
+    ZSelect,
 )
 from .driver import Driver  # noqa: F401
 from .safety_checks import SafetyChecker, VariableBounds  # noqa: F401

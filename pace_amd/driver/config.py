@@ -1,5 +1,5 @@
 """DriverConfig and the selectors it is made of (reference: driver/pace/driver/driver.py:46-370, initialization.py, grid.py,
-comm.py, diagnostics.py:69-90, performance/config.py).  `DriverConfig.from_dict` takes what `yaml.safe_load` gives for one of
+comm.py, performance/config.py; DiagnosticsConfig lives in diagnostics.py).  `DriverConfig.from_dict` takes what `yaml.safe_load` gives for one of
 the reference's configuration files; the conversion is strict (an unknown key raises ValueError and names itself), written by
 hand where the reference uses dacite.
 
@@ -12,7 +12,9 @@ What is accepted, refused and ignored:
                         reference's default is mpi, which does not exist here
   pair_debug            NotImplementedError when true
   restart_config        NotImplementedError when it enables output (save_restart, intermediate_restart)
-  diagnostics_config, performance_config     parsed and kept; nothing is written (the Driver warns once)
+  diagnostics_config    output_format npz with a path: written (driver/diagnostics.py); zarr, netcdf: parsed and kept, nothing is
+                        written (the Driver warns once)
+  performance_config    parsed and kept; nothing is written
   stencil_config.compilation_config.backend  kept as `requested_backend`; the backend is always hip:gfx950
 """
 import dataclasses
@@ -26,6 +28,7 @@ from ..dsl import CompilationConfig, StencilConfig
 from ..fv3core import DynamicalCoreConfig
 from ..fv3core._config import strict_value
 from ..physics import PhysicsConfig, PhysicsState
+from .diagnostics import DiagnosticsConfig, ZSelect  # noqa: F401  (ZSelect: named here before diagnostics.py existed)
 from .state import DriverState, TendencyState
 
 _DERIVED = ("dt_atmos", "layout", "npx", "npy", "npz", "ntiles")
@@ -247,32 +250,6 @@ class CreatesCommSelector:
 
 # ---- kept, not acted on ---------------------------------------------------------------------------------------------------------
 @dataclasses.dataclass
-class ZSelect:
-    level: int
-    names: List[str]
-
-
-@dataclasses.dataclass
-class DiagnosticsConfig:
-    """diagnostics.py:69-90.  Parsed and kept: nothing is written."""
-
-    path: Optional[str] = None
-    output_format: str = "zarr"
-    time_chunk_size: int = 1
-    names: List[str] = dataclasses.field(default_factory=list)
-    derived_names: List[str] = dataclasses.field(default_factory=list)
-    z_select: List[ZSelect] = dataclasses.field(default_factory=list)
-
-    @classmethod
-    def from_dict(cls, config) -> "DiagnosticsConfig":
-        if isinstance(config, cls):
-            return config
-        out = _strict(cls, "diagnostics_config", dict(config or {}))
-        out.z_select = [z if isinstance(z, ZSelect) else _strict(ZSelect, "diagnostics_config.z_select", z) for z in out.z_select]
-        return out
-
-
-@dataclasses.dataclass
 class PerformanceConfig:
     """performance/config.py:14-29.  Parsed and kept: the Driver times its main loop whatever these say and writes no file."""
 
@@ -343,7 +320,8 @@ class DriverConfig:
         nz: number of gridpoints in the vertical dimension
         layout: number of ranks along the x and y dimensions: (1, 1)
         dt_atmos: atmospheric timestep in seconds
-        diagnostics_config, performance_config: kept, not acted on
+        diagnostics_config: configuration for output diagnostics
+        performance_config: kept, not acted on
         dycore_config: configuration for dynamical core
         physics_config: configuration for physics
         days, hours, minutes, seconds: add up to the total simulation time
@@ -352,7 +330,10 @@ class DriverConfig:
             including coupling code between the dycore and physics, as well as
             dry static adjustment
         pair_debug: refused when true
-        output_initial_state, output_frequency: kept; nothing is written
+        output_initial_state: flag to determine if the first output should be the
+            initial state of the model before timestepping
+        output_frequency: number of model timesteps between diagnostic timesteps,
+            defaults to every timestep
         safety_check_frequency: number of model timesteps between checks of the state, None or 0 for never
     """
 

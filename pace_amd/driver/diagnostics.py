@@ -1,0 +1,431 @@
+"""Diagnostics -- what a run leaves behind (reference: driver/pace/driver/diagnostics.py:25-253, util/pace/util/monitor/
+netcdf_monitor.py).
+
+The reference hands its monitor the state's own Quantities, and the monitor slices, transposes, narrows and copies each of
+them.  Here a diagnostics step is ONE launch of pace_diag_pack (pace_amd/csrc/k_diag.hip) per PACE_DIAG_MAX_ITEMS variables --
+it gathers the compute windows, the selected levels and the column integrals, transposes them to the files' (x, y, z) C order
+and narrows them to float32 in one packed device buffer -- ONE copy of that buffer to pinned host memory and ONE
+synchronisation of the stream.  The monitor gets host-resident Quantities that are views of the host buffer: it copies them
+(NpzMonitor: a memcpy into its time-chunk arrays), and they are overwritten by the next store.
+
+Files are written by NpzMonitor, the reference's NetCDFMonitor without its file format (neither xarray, zarr nor netCDF4 is
+required): `output_format: npz` is this project's extension.  With `zarr` and `netcdf` nothing is written, as before.
+"""
+import abc
+import ctypes as C
+import dataclasses
+import json
+import os
+import warnings
+from datetime import datetime, timedelta
+from typing import Dict, List, Optional, Union
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..util import constants as c
+from ..util.quantity import Quantity
+
+_OUTPUT_FORMATS = ("zarr", "netcdf", "npz")
+
+
+class Diagnostics(abc.ABC):
+    @abc.abstractmethod
+    def store(self, time: Union[datetime, timedelta], state):
+        ...
+
+    @abc.abstractmethod
+    def store_grid(self, grid_data):
+        ...
+
+    @abc.abstractmethod
+    def cleanup(self):
+        ...
+
+
+@dataclasses.dataclass
+class ZSelect:
+    level: int
+    names: List[str]
+
+    def variable(self, state, name: str) -> Quantity:
+        """The state's variable `name` if a level of it can be selected, by the reference's rules (diagnostics.py:44-56) -- its
+        quirk included: `Z_DIM or Z_INTERFACE_DIM` evaluates to Z_DIM, so interface fields are refused."""
+        if name not in state.__dict__.keys():
+            raise ValueError(f"Invalid state variable {name} for level select")
+        quantity = getattr(state, name)
+        assert len(quantity.dims) > 2
+        if quantity.dims[2] != c.Z_DIM:
+            raise ValueError(f"z_select only works for state variables with dimension (x, y, z). \n {name} has dimension "
+                             f"{quantity.dims}")
+        return quantity
+
+    def select_data(self, state) -> Dict[str, Quantity]:
+        """diagnostics.py:44-65: `<name>_z<level>` -> the level as a 2-D Quantity over the state's own storage."""
+        output = {}
+        for name in self.names:
+            quantity = self.variable(state, name)
+            output[f"{name}_z{self.level}"] = Quantity(quantity.data[:, :, self.level], dims=quantity.dims[0:2],
+                                                       units=quantity.units, origin=quantity.origin[0:2],
+                                                       extent=quantity.extent[0:2])
+        return output
+
+
+@dataclasses.dataclass
+class DiagnosticsConfig:
+    """
+    Attributes:
+        path: directory to save diagnostics if given, otherwise no diagnostics
+            will be stored
+        output_format: one of "zarr", "netcdf" or "npz".  Only "npz" (this project's extension: numpy archives with the
+            reference's NetCDFMonitor layout, one file per tile and time chunk) writes anything
+        time_chunk_size: number of timesteps stored in each file
+        names: state variables to save as diagnostics
+        derived_names: derived diagnostics to save
+        z_select: save a vertical slice of a 3D state
+    """
+
+    path: Optional[str] = None
+    output_format: str = "zarr"
+    time_chunk_size: int = 1
+    names: List[str] = dataclasses.field(default_factory=list)
+    derived_names: List[str] = dataclasses.field(default_factory=list)
+    z_select: List[ZSelect] = dataclasses.field(default_factory=list)
+
+    def __post_init__(self):
+        if (len(self.names) > 0 or len(self.derived_names) > 0) and self.path is None:
+            raise ValueError("DiagnosticsConfig.path must be given to enable diagnostics")
+        if self.output_format not in _OUTPUT_FORMATS:
+            raise ValueError(f"output_format must be one of 'zarr', 'netcdf' or 'npz', got {self.output_format}")
+
+    @property
+    def writes_files(self) -> bool:
+        return self.path is not None and self.output_format == "npz"
+
+    def diagnostics_factory(self, communicator, lib=None) -> Diagnostics:
+        """
+        Create a diagnostics object.
+
+        Args:
+            communicator: tells which tile this rank holds (layout (1, 1): every rank is its tile's root and writes its own
+                files; nothing is gathered)
+            lib: the kernel library the state's fields belong to (default: the product library)
+        """
+        if not self.writes_files:
+            return NullDiagnostics()
+        os.makedirs(self.path, exist_ok=True)
+        monitor = NpzMonitor(self.path, tile=communicator.partitioner.tile_index(communicator.rank),
+                             time_chunk_size=self.time_chunk_size)
+        return MonitorDiagnostics(monitor=monitor, names=self.names, derived_names=self.derived_names, z_select=self.z_select,
+                                  lib=lib)
+
+    @classmethod
+    def from_dict(cls, config) -> "DiagnosticsConfig":
+        from .config import _strict
+
+        if isinstance(config, cls):
+            return config
+        out = _strict(cls, "diagnostics_config", dict(config or {}))
+        out.z_select = [z if isinstance(z, ZSelect) else _strict(ZSelect, "diagnostics_config.z_select", z) for z in out.z_select]
+        return out
+
+
+class NullDiagnostics(Diagnostics):
+    """Diagnostics that do nothing."""
+
+    def store(self, time: Union[datetime, timedelta], state):
+        pass
+
+    def store_grid(self, grid_data):
+        pass
+
+    def cleanup(self):
+        pass
+
+
+@dataclasses.dataclass
+class _Request:
+    """One variable of a diagnostics step: what pace_diag_pack is asked for and what the monitor is told about it."""
+
+    name: str
+    kind: int
+    field: Quantity
+    weight: Optional[Quantity]
+    level: int  # PLANE of a 3-D field: the level; otherwise 0
+    window: tuple  # (i0, j0, k0, ni, nj, nk)
+    dims: tuple
+    units: str
+
+    @property
+    def shape(self):
+        ni, nj, nk = self.window[3:]
+        return (ni, nj, nk) if self.kind == _lib.DIAG_WINDOW3D else (ni, nj)
+
+
+def _layout(t):
+    """(n, sj, nk or None, sk or None) of a 2-D or 3-D field of the library's layout."""
+    if t.dim() not in (2, 3) or t.stride(0) != 1:
+        raise ValueError(f"field of shape {tuple(t.shape)}, strides {tuple(t.stride())}: diagnostics take 2-D and 3-D fields "
+                         "allocated with pace_amd.util.QuantityFactory")
+    if t.dim() == 2:
+        return t.shape[0] - 7, t.stride(1), None, None
+    return t.shape[0] - 7, t.stride(1), t.shape[2] - 1, t.stride(2)
+
+
+class MonitorDiagnostics(Diagnostics):
+    """Diagnostics that save to a sympl-style Monitor."""
+
+    def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None):
+        """
+        Args:
+            monitor: a sympl-style Monitor object
+            names: list of names of diagnostics to save
+            derived_names: list of names of derived diagnostics to save
+            z_select: the levels to save of variables of the dycore state
+            lib: the library the state's fields belong to (default: the product library, loaded at the first store)
+        """
+        self.names = names
+        self.derived_names = derived_names
+        self.z_select = z_select
+        self.monitor = monitor
+        self._lib = lib
+        self._plans = {}  # what is asked for, where and as which type -> (geometry, offsets, device buffer, host buffer)
+
+    # ---- what a step asks for ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _whole(name, quantity) -> _Request:
+        if len(quantity.dims) == 3:
+            return _Request(name, _lib.DIAG_WINDOW3D, quantity, None, 0, tuple(quantity.origin) + tuple(quantity.extent),
+                            tuple(quantity.dims), quantity.units)
+        if len(quantity.dims) == 2:
+            return _Request(name, _lib.DIAG_PLANE, quantity, None, 0, tuple(quantity.origin) + (0,) + tuple(quantity.extent) + (1,),
+                            tuple(quantity.dims), quantity.units)
+        raise ValueError(f"{name} has dimensions {quantity.dims}: diagnostics take 2-D and 3-D variables")
+
+    def _requests(self, state) -> List[_Request]:
+        """The reference's order (diagnostics.py:166-178): names, derived names, level selections.  The Quantities are looked up
+        at every call: Quantity.swap_storage replaces storages during a step."""
+        requests = []
+        for name in self.names:
+            try:
+                quantity = getattr(state.dycore_state, name)
+            except AttributeError:
+                quantity = getattr(state.physics_state, name)
+            requests.append(self._whole(name, quantity))
+        for name in self.derived_names:
+            if name.startswith("column_integrated_"):
+                q_in = getattr(state.dycore_state, name[len("column_integrated_"):])
+                assert len(q_in.dims) > 2
+                if q_in.dims[2] != c.Z_DIM:
+                    raise NotImplementedError("this function assumes the z-dimension is the third dimension")
+                requests.append(_Request(name, _lib.DIAG_COLUMN_INTEGRAL, q_in, state.dycore_state.delp,
+                                         0, tuple(q_in.origin) + tuple(q_in.extent), tuple(q_in.dims[:2]), "kg/m**2"))
+            else:
+                warnings.warn(f"{name} is not a supported diagnostic variable.")
+        for zselect in self.z_select:
+            for name in zselect.names:
+                quantity = zselect.variable(state.dycore_state, name)
+                if not 0 <= zselect.level < quantity.data.shape[2]:
+                    raise IndexError(f"z_select level {zselect.level} of {name}: the storage has {quantity.data.shape[2]} levels")
+                window = tuple(quantity.origin[:2]) + (0,) + tuple(quantity.extent[:2]) + (1,)
+                requests.append(_Request(f"{name}_z{zselect.level}", _lib.DIAG_PLANE, quantity, None, zselect.level, window,
+                                         tuple(quantity.dims[:2]), quantity.units))
+        return requests
+
+    # ---- device side ------------------------------------------------------------------------------------------------------------
+    def _plan(self, requests, out_is_double):
+        tensors = [r.field.data for r in requests] + [r.weight.data for r in requests if r.weight is not None]
+        layouts = [_layout(t) for t in tensors]
+        n, sj = layouts[0][:2]
+        levels = {(nk, sk) for _, _, nk, sk in layouts if nk is not None}
+        if any(lay[:2] != (n, sj) for lay in layouts) or len(levels) > 1 or len({(t.device, t.dtype) for t in tensors}) > 1:
+            raise ValueError("diagnostics take fields of one layout and type on one device")
+        nk, sk = levels.pop() if levels else (1, sj * (n + 7))
+        device = tensors[0].device
+        key = (device, n, nk, sj, sk, bool(out_is_double), tuple((r.name, r.kind, r.window) for r in requests))
+        if key not in self._plans:
+            offsets, total = [], 0
+            for r in requests:
+                offsets.append(total)
+                total += int(np.prod(r.shape))
+            dtype = torch.float64 if out_is_double else torch.float32
+            packed = torch.empty(total, dtype=dtype, device=device)
+            host = torch.empty(total, dtype=dtype, pin_memory=device.type != "cpu")
+            self._plans[key] = (_lib.Geom(n, nk, sj, 0, sk), offsets, packed, host)
+        return self._plans[key]
+
+    def _to_host(self, packed, host):
+        """The step's one transfer and one synchronisation."""
+        host.copy_(packed, non_blocking=True)
+        if packed.device.type != "cpu":
+            torch.cuda.current_stream(packed.device).synchronize()
+
+    def pack(self, requests: List[_Request], out_is_double: bool = False) -> Dict[str, Quantity]:
+        """name -> host-resident Quantity, C-contiguous over the request's window; views of a buffer that the next call with the
+        same requests overwrites."""
+        if not requests:
+            return {}
+        if self._lib is None:
+            self._lib = _lib.load()
+        geom, offsets, packed, host = self._plan(requests, out_is_double)
+        tensor = requests[0].field.data
+        real = torch.float32 if self._lib.real_bytes == 4 else torch.float64
+        if tensor.dtype != real:
+            raise ValueError(f"field dtype {tensor.dtype} does not match the library's storage type {real}")
+        emu = tensor.device.type == "cpu"
+        if emu != ("emulation" in self._lib.version()):
+            raise _lib.PaceError("CPU tensors go with the emulation test library, device tensors with the product library")
+        stream = None if emu else C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
+        for first in range(0, len(requests), _lib.DIAG_MAX_ITEMS):
+            chunk = requests[first:first + _lib.DIAG_MAX_ITEMS]
+            items = (_lib.DiagItem * len(chunk))()
+            for item, r, offset in zip(items, chunk, offsets[first:]):
+                item.field = r.field.ptr + r.level * geom.sk * self._lib.real_bytes  # (the pointers of THIS call's storages)
+                item.weight = r.weight.ptr if r.weight is not None else None
+                item.kind = r.kind
+                item.i0, item.j0, item.k0, item.ni, item.nj, item.nk = r.window
+                item.out_offset = offset
+            self._lib.call("pace_diag_pack", C.byref(geom), items, len(chunk), int(bool(out_is_double)),
+                           C.c_void_p(packed.data_ptr()), stream)
+        self._to_host(packed, host)
+        out = {}
+        for r, offset in zip(requests, offsets):
+            data = host[offset:offset + int(np.prod(r.shape))].view(r.shape)
+            out[r.name] = Quantity(data, dims=r.dims, units=r.units, origin=(0,) * len(r.shape), extent=r.shape)
+        return out
+
+    # ---- the reference's interface ------------------------------------------------------------------------------------------------
+    def store(self, time: Union[datetime, timedelta], state):
+        monitor_state = {"time": time}
+        monitor_state.update(self.pack(self._requests(state)))
+        self.monitor.store(monitor_state)
+
+    def store_grid(self, grid_data):
+        """lat, lon, lon_agrid, lat_agrid over their compute domains in float64.  GridData keeps these four on the host (numpy,
+        the whole storage): those are cut there; a device Quantity goes through the pack as a PLANE."""
+        dims = {"lat": (c.X_INTERFACE_DIM, c.Y_INTERFACE_DIM), "lon": (c.X_INTERFACE_DIM, c.Y_INTERFACE_DIM),
+                "lon_agrid": (c.X_DIM, c.Y_DIM), "lat_agrid": (c.X_DIM, c.Y_DIM)}
+        names = ("lat", "lon", "lon_agrid", "lat_agrid")
+        values = {name: getattr(grid_data, name) for name in names}
+        packed = self.pack([self._whole(name, v) for name, v in values.items() if hasattr(v, "dims")], out_is_double=True)
+        for name in names:
+            if name in packed:
+                self.monitor.store_constant({name: packed[name]})
+                continue
+            a = np.asarray(values[name], dtype=np.float64)
+            n, extra = a.shape[0] - 2 * c.N_HALO_DEFAULT - 1, int(dims[name][0] == c.X_INTERFACE_DIM)
+            cut = slice(c.N_HALO_DEFAULT, c.N_HALO_DEFAULT + n + extra)
+            data = torch.from_numpy(np.ascontiguousarray(a[cut, cut]))
+            self.monitor.store_constant({name: Quantity(data, dims=dims[name], units="radians")})
+
+    def cleanup(self):
+        self.monitor.cleanup()
+
+
+# ---- the monitor ------------------------------------------------------------------------------------------------------------------
+def _host_array(quantity, dims=None) -> np.ndarray:
+    if dims is not None and tuple(quantity.dims) != tuple(dims):
+        quantity = quantity.transpose(dims)
+    view = quantity.view[:]
+    return view.detach().cpu().numpy() if torch.is_tensor(view) else np.asarray(view)
+
+
+class _TimeChunkedVariable:
+    """netcdf_monitor.py:20-40 with the tile axis already in place: (time_chunk_size, 1, *extent)."""
+
+    def __init__(self, initial, time_chunk_size: int):
+        first = _host_array(initial)
+        self._data = np.zeros((time_chunk_size, 1) + first.shape, dtype=first.dtype)
+        self._data[0, 0, ...] = first
+        self.dims = tuple(initial.dims)
+        self.units = initial.units
+        self._i_time = 1
+
+    def append(self, quantity):
+        self._data[self._i_time, 0, ...] = _host_array(quantity, self.dims)
+        self._i_time += 1
+
+    @property
+    def data(self) -> np.ndarray:
+        return self._data[:self._i_time]
+
+
+class NpzMonitor:
+    """sympl.Monitor-style object storing model state dictionaries in numpy archives: the reference's NetCDFMonitor
+    (netcdf_monitor.py:43-202) without its file format.
+
+    `state_{chunk:04d}_tile{tile}.npz` holds `time` (datetime64[us] or timedelta64[us], dimension [time]), every variable with
+    the dimensions [time, tile] followed by its own, and `__meta__`, a JSON string with the dims and units of every variable.
+    `constants_<name>_tile{tile}.npz` holds one constant with the leading dimension [tile].  Nothing is pickled.  There is one
+    file per tile and no gather: with layout (1, 1) every rank is its tile's root.
+    """
+
+    FILENAME_FORMAT = "state_{chunk:04d}_tile{tile}.npz"
+    CONSTANT_FILENAME_FORMAT = "constants_{name}_tile{tile}.npz"
+
+    def __init__(self, path: str, tile: int, time_chunk_size: int = 1):
+        """
+        Args:
+            path: directory in which to store data
+            tile: the tile this rank holds
+            time_chunk_size: number of times per file
+        """
+        self._path = path
+        self._tile = int(tile)
+        self._time_chunk_size = time_chunk_size
+        self._i_time = 0
+        self._chunked: Optional[Dict[str, _TimeChunkedVariable]] = None
+        self._times = []
+        self._expected_vars = None
+
+    def store(self, state: dict) -> None:
+        """Append the model state dictionary.  Writes to disk only when a full time chunk has been accumulated, or when
+        .cleanup() is called.  The keys must be those of the first call."""
+        if self._expected_vars is None:
+            self._expected_vars = set(state.keys())
+        elif self._expected_vars != set(state.keys()):
+            raise ValueError("state keys must be the same each time store is called, "
+                             f"got {set(state.keys())} but previously got {self._expected_vars}")
+        state = {**state}  # copy so we don't mutate the input
+        time = state.pop("time", None)
+        if self._chunked is None:
+            self._chunked = {name: _TimeChunkedVariable(quantity, self._time_chunk_size) for name, quantity in state.items()}
+        else:
+            for name, quantity in state.items():
+                self._chunked[name].append(quantity)
+        self._times.append(time)
+        if (self._i_time + 1) % self._time_chunk_size == 0:
+            self.flush()
+        self._i_time += 1
+
+    @staticmethod
+    def _time_array(times) -> np.ndarray:
+        kind = "timedelta64[us]" if times and isinstance(times[0], (timedelta, np.timedelta64)) else "datetime64[us]"
+        return np.array(times, dtype=kind)
+
+    def _write(self, filename, arrays, meta):
+        path = os.path.join(self._path, filename)
+        if os.path.exists(path):
+            os.remove(path)
+        np.savez(path, __meta__=np.array(json.dumps(meta)), **arrays)
+
+    def flush(self):
+        if self._chunked is not None:
+            arrays = {"time": self._time_array(self._times)}
+            meta = {"time": {"dims": ["time"], "units": ""}}
+            for name, chunked in self._chunked.items():
+                arrays[name] = chunked.data
+                meta[name] = {"dims": ["time", "tile"] + list(chunked.dims), "units": chunked.units}
+            chunk_index = self._i_time // self._time_chunk_size
+            self._write(self.FILENAME_FORMAT.format(chunk=chunk_index, tile=self._tile), arrays, meta)
+        self._chunked = None
+        self._times.clear()
+
+    def store_constant(self, state: Dict[str, Quantity]) -> None:
+        for name, quantity in state.items():
+            self._write(self.CONSTANT_FILENAME_FORMAT.format(name=name, tile=self._tile), {name: _host_array(quantity)[None]},
+                        {name: {"dims": ["tile"] + list(quantity.dims), "units": quantity.units}})
+
+    def cleanup(self):
+        self.flush()

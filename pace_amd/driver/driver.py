@@ -6,8 +6,9 @@
 
 A step is the reference's (driver.py:618-640): DynamicalCore.step_dynamics, DycoreToPhysics, Physics, UpdateAtmosphereState,
 each a class of its own that can also be called by hand; the driver only strings them together, advances the time and, every
-safety_check_frequency steps, checks the state (SafetyChecker: one launch pair and one transfer).  What the reference's
-constructor does for DaCe, build modes, diagnostics, restarts and the performance collector's files is not here.
+safety_check_frequency steps, checks the state (SafetyChecker: one launch pair and one transfer) and, every output_frequency
+steps, stores the diagnostics (MonitorDiagnostics: one pack launch and one transfer).  What the reference's constructor does
+for DaCe, build modes, restarts and the performance collector's files is not here.
 
 One deliberate departure: the reference's constructor registers its four variables with SafetyChecker.register_variable, which
 raises on a second registration, so two reference Drivers cannot exist in one process.  Six of these do (one per tile on
@@ -105,6 +106,9 @@ class Driver:
                 # Make sure those are set to None to raise any issues
                 self.dycore_to_physics = None
                 self.end_of_step_update = None
+            self.diagnostics = config.diagnostics_config.diagnostics_factory(communicator=communicator, lib=self.lib)
+        if config.output_initial_state:
+            self.diagnostics.store(time=self.time, state=self.state)
         self._time_run = self.config.start_time
         self.safety_checker = SafetyChecker(self.lib)
         with _REGISTRATION_LOCK:  # (see the module's docstring)
@@ -117,7 +121,7 @@ class Driver:
         if self.comm.Get_rank() != 0:
             return
         ignored = []
-        if self.config.diagnostics_config.path is not None:
+        if self.config.diagnostics_config.path is not None and not self.config.diagnostics_config.writes_files:
             ignored.append(f"diagnostics_config (path {self.config.diagnostics_config.path!r}): no diagnostics are written, "
                            "output_initial_state and output_frequency have no effect")
         requested = getattr(self.config.stencil_config, "requested_backend", None)
@@ -132,6 +136,8 @@ class Driver:
         Gather operations unrelated to computation.
         """
         self.time += self.config.timestep
+        if ((step + 1) % self.config.output_frequency) == 0:
+            self.diagnostics.store(time=self.time, state=self.state)
         if self.config.safety_check_frequency and ((step + 1) % self.config.safety_check_frequency) == 0:
             with self.performance_collector.total_timer.clock("safety_check"):
                 self.safety_checker.check_state(self.state.dycore_state)
@@ -167,4 +173,6 @@ class Driver:
         return 1.0 / 365.0 * (self.config.dt_atmos / mainloop)
 
     def cleanup(self):
+        self.diagnostics.store_grid(grid_data=self.state.grid_data)
+        self.diagnostics.cleanup()
         self.comm_config.cleanup(self.comm)

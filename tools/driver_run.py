@@ -1,6 +1,6 @@
 """Run the model from one of the reference's driver configuration files: pace_amd.driver.Driver, its step_all, one JSON line.
 
-    python tools/driver_run.py CONFIG.yaml [--steps N] [--device D] [--cpu-emulation]
+    python tools/driver_run.py CONFIG.yaml [--steps N] [--device D] [--cpu-emulation] [--diagnostics DIR]
 
 runs ONE rank (tile 0) with the `null` communicator -- its halos receive zeros, so this exercises the loop, not the weather --
 and, launched under torch.distributed.run as tools/dycore_run.py is,
@@ -9,7 +9,8 @@ and, launched under torch.distributed.run as tools/dycore_run.py is,
         tools/driver_run.py CONFIG.yaml [--steps N] [--cpu-emulation]
 
 the six tiles of the cubed sphere, one process per tile (RCCL on GPUs, gloo with --cpu-emulation).  --steps replaces the
-file's run length.  Rank 0 prints: workload, steps, ms per step (mean of the main loop's clock, the slowest rank), SYPD
+file's run length.  --diagnostics DIR writes the file's diagnostics into DIR as per-tile numpy archives (it replaces
+diagnostics_config.path and sets output_format: npz; pace_amd.driver.NpzMonitor describes the files).  Rank 0 prints: workload, steps, ms per step (mean of the main loop's clock, the slowest rank), SYPD
 (Driver.sypd()), and the time of the safety check per call with its verdict: the checks the file asks for inside the loop
 (safety_check_frequency) and, after the run, three timed calls on the final state whose verdict is reported, not raised (a lone
 tile behind zero halos need not stay within the bounds).
@@ -32,6 +33,8 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="run this many steps instead of the file's days / hours / minutes / seconds")
     ap.add_argument("--device", default=None, help="one-rank runs: the device (default cuda:0)")
     ap.add_argument("--cpu-emulation", action="store_true", help="the CPU emulation library (and gloo): a logic check, not a timing")
+    ap.add_argument("--diagnostics", metavar="DIR", default=None,
+                    help="write the file's diagnostics into DIR (diagnostics_config.path = DIR, output_format = npz)")
     args = ap.parse_args()
     import yaml
 
@@ -62,6 +65,8 @@ def main():
         torch.cuda.set_device(torch.device(device))
     if args.steps is not None:
         settings.update(days=0, hours=0, minutes=0, seconds=0)
+    if args.diagnostics is not None:
+        settings["diagnostics_config"] = dict(settings.get("diagnostics_config") or {}, path=args.diagnostics, output_format="npz")
     config = DriverConfig.from_dict(settings)
     if args.steps is not None:
         config.seconds = int(round(args.steps * config.dt_atmos))

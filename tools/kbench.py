@@ -3,6 +3,8 @@
     python tools/kbench.py [--lib path/to/libpace_hip.so] [--n 192] [--reps 20] [--only fvtp2d,riem3,sat_adjust,dry_convective_adjust,apply_physics,microphysics,physics]
     python tools/kbench.py --only safety_check      the driver's state check against a plain torch restatement (host clock
                                                     around whole checks, which end in their own synchronisation; medians)
+    python tools/kbench.py --only diag_pack         a diagnostics step (the example file's fourteen variables) against a plain
+                                                    torch restatement, the same way
 """
 import argparse
 import os
@@ -133,6 +135,11 @@ def main():
     if "safety_check" in only:
         safety_check_bench(lib, env, s, n, nz, max(args.reps, 50))
         only.remove("safety_check")
+        if not only:
+            return
+    if "diag_pack" in only:
+        diag_pack_bench(lib, env, s, n, nz, max(args.reps, 50))
+        only.remove("diag_pack")
         if not only:
             return
     if "apply_physics" in only:
@@ -387,6 +394,86 @@ def safety_check_bench(lib, env, s, n, nz, reps):
     print(f"  torch restatement (amin / amax / isnan().any())   {ref:9.1f} us per call   (min {min(times['torch']):.1f})")
     print(f"  ratio torch / hip {ref / hip:.2f}")
     SafetyChecker.clear_all_checks()
+
+
+def diag_pack_bench(lib, env, s, n, nz, reps):
+    """MonitorDiagnostics.pack on what tests/golden/driver_baroclinic_c12.yaml asks for -- its twelve 3-D names, pt at level 65
+    and, as a derived variable, column_integrated_qliquid -- against the same step restated with torch: per variable the slice
+    of the compute domain, a permute to (x, y, z) C order, contiguous(), .to(float32) and .cpu(), the column integral as
+    RGRAV * sum(q * delp).  Both end with the data on the host and are timed with the host clock from an idle device; the two
+    alternate, medians are reported, as --only safety_check does."""
+    import time
+    import types
+
+    from pace_amd.driver import MonitorDiagnostics, ZSelect
+    from pace_amd.util import constants as c
+
+    names = ["u", "v", "ua", "va", "pt", "delp", "qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel"]
+    dims = {"u": ["x", "y_interface", "z"], "v": ["x_interface", "y", "z"]}
+    rng = np.random.default_rng(0)
+    fields = {}
+    for name in names:
+        q = env.qf.zeros(dims.get(name, ["x", "y", "z"]), "")
+        q.set(s[name] if name in s else rng.uniform(0.0, 1e-3, q.shape))
+        fields[name] = q
+    state = types.SimpleNamespace(dycore_state=types.SimpleNamespace(**fields), physics_state=types.SimpleNamespace())
+    level = min(65, nz - 1)
+    diag = MonitorDiagnostics(None, names, ["column_integrated_qliquid"], [ZSelect(level=level, names=["pt"])], lib=lib)
+
+    def hip_step():
+        return diag.pack(diag._requests(state))
+
+    def torch_step():
+        out = {}
+        for name in names:
+            out[name] = fields[name].view[:].contiguous().to(torch.float32).cpu()  # (data is already the (x, y, z) view: contiguous() permutes)
+        q, delp = fields["qliquid"], fields["delp"]
+        out["column_integrated_qliquid"] = (c.RGRAV * torch.sum(q.view[:] * delp.view[:], dim=2)).contiguous().to(torch.float32).cpu()
+        out[f"pt_z{level}"] = fields["pt"].view[:][:, :, level].contiguous().to(torch.float32).cpu()
+        return out
+
+    got, want = hip_step(), torch_step()
+    for name in names + [f"pt_z{level}"]:
+        assert torch.equal(got[name].view[:].view(torch.int32), want[name].view(torch.int32)), name  # (bit for bit)
+    paths = {"hip": hip_step, "torch": torch_step}
+    times = {k: [] for k in paths}
+    for k, fn in paths.items():  # warm-up: code objects, the pinned buffer, torch's copy kernels
+        for _ in range(5):
+            fn()
+    for _ in range(reps):
+        for k, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append((time.perf_counter() - t0) * 1e6)
+    requests = diag._requests(state)
+    (geom, offsets, packed, host), = diag._plans.values()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    dev, prep = [], []
+    real_to_host = diag._to_host
+    diag._to_host = lambda packed, host: None
+    burst = 10  # launches queued back to back, so that the device time is the kernel's and not the host's item table
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        for _ in range(burst):
+            diag.pack(requests)
+        e1.record()
+        prep.append((time.perf_counter() - t0) * 1e6 / burst)  # host time to build the table and launch, nothing waited for
+        torch.cuda.synchronize()
+        dev.append(e0.elapsed_time(e1) * 1e3 / burst)
+    diag._to_host = real_to_host
+    read_mb = sum(int(np.prod(r.shape)) for r in requests[:12]) * lib.real_bytes / 1e6
+    out_mb = packed.numel() * 4 / 1e6
+    hip, ref = float(np.median(times["hip"])), float(np.median(times["torch"]))
+    print(f"diag_pack C{n} x {nz}, {len(requests)} variables, {read_mb:.1f} MB read, {out_mb:.1f} MB of float32 to the host; "
+          f"medians of {reps} alternating runs")
+    print(f"  MonitorDiagnostics.pack (pace_diag_pack, one transfer)   {hip:9.1f} us per step   (min {min(times['hip']):.1f}, "
+          f"host time to build the item table and launch {np.median(prep):.1f} us; {burst} launches back to back in device events: "
+          f"{np.median(dev):.1f} us each = {(read_mb + out_mb) * 1e6 / (np.median(dev) * 1e-6) / 1e9:.0f} GB/s of read + write)")
+    print(f"  torch restatement (slice, contiguous, float32, cpu per variable)   {ref:9.1f} us per step   (min {min(times['torch']):.1f})")
+    print(f"  ratio torch / hip {ref / hip:.2f}")
 
 
 if __name__ == "__main__":
