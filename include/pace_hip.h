@@ -606,6 +606,30 @@ typedef struct {
 int pace_diag_pack(const pace_geom_t* geom, const pace_diag_item_t* items, int nitems, int out_is_double, void* out,
                    void* stream);
 
+/* ---- A host model's arrays into the state (fv3core/pace/fv3core/initialization/geos_wrapper.py:207-270): the inverse of
+ * pace_diag_pack.  Up to PACE_UNPACK_MAX_ITEMS windows of fields are filled from one packed device buffer by ONE launch, both
+ * storage types, no atomics, no workspace, no host synchronisation.  items: HOST array of nitems items; in: DEVICE array of
+ * float64 in both libraries (the float32 library narrows with a plain cast: round to nearest even, overflow to +-inf).
+ *   field(i0 + i, j0 + j, k0 + k) = (pace_real_t) in[in_offset + e * in_step]
+ *   PACE_ORDER_ZFAST  e = (i * nj + j) * nk + k   a C-ordered array; with in_step = 7 one species of a C-ordered (x, y, z, 7) one
+ *   PACE_ORDER_XFAST  e = i + ni * (j + nj * k)   Fortran order, which is the device's own
+ * and for a PACE_DIAG_PLANE item the same expressions with nk = 1, k = 0; its field points at element (0, 0) of a 2-D field or
+ * of ONE level of a 3-D one.  Nothing outside an item's window is written (not the halo, not other levels, not the row padding)
+ * and nothing outside its ni * nj * nk source elements is read.  Two items whose windows overlap on one field: undefined.
+ * PACE_ERR_ARG: nitems < 1 or > PACE_UNPACK_MAX_ITEMS, a kind other than WINDOW3D and PLANE, an unknown order, a window that is
+ * empty or outside the storage (n + 7, n + 7, nk + 1), a negative in_offset, in_step < 1, a field that is NULL. */
+#define PACE_UNPACK_MAX_ITEMS 32
+enum { PACE_ORDER_ZFAST = 0, PACE_ORDER_XFAST = 1 };
+typedef struct {
+  pace_real_t* field;      /* element (0,0,0) of the storage (2-D field for PLANE) */
+  int32_t kind;            /* PACE_DIAG_WINDOW3D | PACE_DIAG_PLANE */
+  int32_t order;           /* layout of the item's source elements */
+  int32_t i0, j0, k0, ni, nj, nk;   /* destination window in the storage; nk = 1, k0 = 0 for PLANE */
+  int32_t in_step;         /* >= 1: distance in elements between consecutive source elements along the fastest axis */
+  int64_t in_offset;       /* in source elements */
+} pace_unpack_item_t;
+int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, int nitems, const double* in, void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

@@ -128,6 +128,15 @@ class DiagItem(C.Structure):  # include/pace_hip.h pace_diag_item_t
                 ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("out_offset", C.c_int64)]
 
 
+UNPACK_MAX_ITEMS = 32  # include/pace_hip.h PACE_UNPACK_MAX_ITEMS
+ORDER_ZFAST, ORDER_XFAST = 0, 1  # include/pace_hip.h PACE_ORDER_*
+
+
+class UnpackItem(C.Structure):  # include/pace_hip.h pace_unpack_item_t
+    _fields_ = [("field", c_dp), ("kind", C.c_int32), ("order", C.c_int32), ("i0", C.c_int32), ("j0", C.c_int32), ("k0", C.c_int32),
+                ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("in_step", C.c_int32), ("in_offset", C.c_int64)]
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -226,6 +235,7 @@ _PROTOS = {
     "pace_state_extrema_workspace_bytes": (C.c_int64, [_P(Geom)]),
     "pace_state_extrema": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_int), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_diag_pack": (C.c_int, [_P(Geom), _P(DiagItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pace_state_unpack": (C.c_int, [_P(Geom), _P(UnpackItem), C.c_int, c_dp, C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

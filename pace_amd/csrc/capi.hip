@@ -692,6 +692,21 @@ int pace_diag_pack(const pace_geom_t* geom, const pace_diag_item_t* items, int n
   return launch_diag_pack(make_geo(geom), items, nitems, out_is_double, out, S(stream));
 }
 
+int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, int nitems, const double* in, void* stream) {
+  NEED(geom && items && in);
+  if (nitems < 1 || nitems > PACE_UNPACK_MAX_ITEMS) return PACE_ERR_ARG;
+  const int ni = geom->n + 7, nlev = geom->nk + 1;
+  for (int m = 0; m < nitems; ++m) {
+    const pace_unpack_item_t& it = items[m];
+    if (it.kind != PACE_DIAG_WINDOW3D && it.kind != PACE_DIAG_PLANE) return PACE_ERR_ARG;
+    if (it.order != PACE_ORDER_ZFAST && it.order != PACE_ORDER_XFAST) return PACE_ERR_ARG;
+    if (!it.field || it.in_offset < 0 || it.in_step < 1) return PACE_ERR_ARG;
+    if (it.i0 < 0 || it.ni < 1 || it.ni > ni - it.i0 || it.j0 < 0 || it.nj < 1 || it.nj > ni - it.j0) return PACE_ERR_ARG;
+    if (it.kind == PACE_DIAG_PLANE ? (it.k0 != 0 || it.nk != 1) : (it.k0 < 0 || it.nk < 1 || it.nk > nlev - it.k0)) return PACE_ERR_ARG;
+  }
+  return launch_state_unpack(make_geo(geom), items, nitems, in, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

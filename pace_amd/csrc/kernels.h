@@ -281,6 +281,8 @@ int launch_state_extrema(const Geo& g, const real* const* fields, const int* com
                          double* out, hipStream_t st);
 // k_diag.hip
 int launch_diag_pack(const Geo& g, const pace_diag_item_t* items, int nitems, int out_is_double, void* out, hipStream_t st);
+// k_state.hip
+int launch_state_unpack(const Geo& g, const pace_unpack_item_t* items, int nitems, const double* in, hipStream_t st);
 // k_dycore.hip
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);

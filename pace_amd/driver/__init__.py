@@ -21,6 +21,7 @@ from .diagnostics import (  # noqa: F401
     MonitorDiagnostics,
     NpzMonitor,
     NullDiagnostics,
+    WindowPacker,
     ZSelect,
 )
 from .driver import Driver  # noqa: F401

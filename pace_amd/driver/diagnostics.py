@@ -173,67 +173,16 @@ def _layout(t):
     return t.shape[0] - 7, t.stride(1), t.shape[2] - 1, t.stride(2)
 
 
-class MonitorDiagnostics(Diagnostics):
-    """Diagnostics that save to a sympl-style Monitor."""
+class WindowPacker:
+    """Windows of fields to the host: ONE pace_diag_pack launch per PACE_DIAG_MAX_ITEMS requests, ONE transfer of the packed
+    buffer to pinned host memory and ONE synchronisation.  What MonitorDiagnostics stores with, and what
+    pace_amd.fv3core.GeosDycoreWrapper hands a host model its arrays with."""
 
-    def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None):
-        """
-        Args:
-            monitor: a sympl-style Monitor object
-            names: list of names of diagnostics to save
-            derived_names: list of names of derived diagnostics to save
-            z_select: the levels to save of variables of the dycore state
-            lib: the library the state's fields belong to (default: the product library, loaded at the first store)
-        """
-        self.names = names
-        self.derived_names = derived_names
-        self.z_select = z_select
-        self.monitor = monitor
+    def __init__(self, lib=None):
+        """lib: the library the fields belong to (default: the product library, loaded at the first pack)"""
         self._lib = lib
         self._plans = {}  # what is asked for, where and as which type -> (geometry, offsets, device buffer, host buffer)
 
-    # ---- what a step asks for ---------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _whole(name, quantity) -> _Request:
-        if len(quantity.dims) == 3:
-            return _Request(name, _lib.DIAG_WINDOW3D, quantity, None, 0, tuple(quantity.origin) + tuple(quantity.extent),
-                            tuple(quantity.dims), quantity.units)
-        if len(quantity.dims) == 2:
-            return _Request(name, _lib.DIAG_PLANE, quantity, None, 0, tuple(quantity.origin) + (0,) + tuple(quantity.extent) + (1,),
-                            tuple(quantity.dims), quantity.units)
-        raise ValueError(f"{name} has dimensions {quantity.dims}: diagnostics take 2-D and 3-D variables")
-
-    def _requests(self, state) -> List[_Request]:
-        """The reference's order (diagnostics.py:166-178): names, derived names, level selections.  The Quantities are looked up
-        at every call: Quantity.swap_storage replaces storages during a step."""
-        requests = []
-        for name in self.names:
-            try:
-                quantity = getattr(state.dycore_state, name)
-            except AttributeError:
-                quantity = getattr(state.physics_state, name)
-            requests.append(self._whole(name, quantity))
-        for name in self.derived_names:
-            if name.startswith("column_integrated_"):
-                q_in = getattr(state.dycore_state, name[len("column_integrated_"):])
-                assert len(q_in.dims) > 2
-                if q_in.dims[2] != c.Z_DIM:
-                    raise NotImplementedError("this function assumes the z-dimension is the third dimension")
-                requests.append(_Request(name, _lib.DIAG_COLUMN_INTEGRAL, q_in, state.dycore_state.delp,
-                                         0, tuple(q_in.origin) + tuple(q_in.extent), tuple(q_in.dims[:2]), "kg/m**2"))
-            else:
-                warnings.warn(f"{name} is not a supported diagnostic variable.")
-        for zselect in self.z_select:
-            for name in zselect.names:
-                quantity = zselect.variable(state.dycore_state, name)
-                if not 0 <= zselect.level < quantity.data.shape[2]:
-                    raise IndexError(f"z_select level {zselect.level} of {name}: the storage has {quantity.data.shape[2]} levels")
-                window = tuple(quantity.origin[:2]) + (0,) + tuple(quantity.extent[:2]) + (1,)
-                requests.append(_Request(f"{name}_z{zselect.level}", _lib.DIAG_PLANE, quantity, None, zselect.level, window,
-                                         tuple(quantity.dims[:2]), quantity.units))
-        return requests
-
-    # ---- device side ------------------------------------------------------------------------------------------------------------
     def _plan(self, requests, out_is_double):
         tensors = [r.field.data for r in requests] + [r.weight.data for r in requests if r.weight is not None]
         layouts = [_layout(t) for t in tensors]
@@ -294,6 +243,66 @@ class MonitorDiagnostics(Diagnostics):
             data = host[offset:offset + int(np.prod(r.shape))].view(r.shape)
             out[r.name] = Quantity(data, dims=r.dims, units=r.units, origin=(0,) * len(r.shape), extent=r.shape)
         return out
+
+
+class MonitorDiagnostics(Diagnostics, WindowPacker):
+    """Diagnostics that save to a sympl-style Monitor."""
+
+    def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None):
+        """
+        Args:
+            monitor: a sympl-style Monitor object
+            names: list of names of diagnostics to save
+            derived_names: list of names of derived diagnostics to save
+            z_select: the levels to save of variables of the dycore state
+            lib: the library the state's fields belong to (default: the product library, loaded at the first store)
+        """
+        self.names = names
+        self.derived_names = derived_names
+        self.z_select = z_select
+        self.monitor = monitor
+        WindowPacker.__init__(self, lib)
+
+    # ---- what a step asks for ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _whole(name, quantity) -> _Request:
+        if len(quantity.dims) == 3:
+            return _Request(name, _lib.DIAG_WINDOW3D, quantity, None, 0, tuple(quantity.origin) + tuple(quantity.extent),
+                            tuple(quantity.dims), quantity.units)
+        if len(quantity.dims) == 2:
+            return _Request(name, _lib.DIAG_PLANE, quantity, None, 0, tuple(quantity.origin) + (0,) + tuple(quantity.extent) + (1,),
+                            tuple(quantity.dims), quantity.units)
+        raise ValueError(f"{name} has dimensions {quantity.dims}: diagnostics take 2-D and 3-D variables")
+
+    def _requests(self, state) -> List[_Request]:
+        """The reference's order (diagnostics.py:166-178): names, derived names, level selections.  The Quantities are looked up
+        at every call: Quantity.swap_storage replaces storages during a step."""
+        requests = []
+        for name in self.names:
+            try:
+                quantity = getattr(state.dycore_state, name)
+            except AttributeError:
+                quantity = getattr(state.physics_state, name)
+            requests.append(self._whole(name, quantity))
+        for name in self.derived_names:
+            if name.startswith("column_integrated_"):
+                q_in = getattr(state.dycore_state, name[len("column_integrated_"):])
+                assert len(q_in.dims) > 2
+                if q_in.dims[2] != c.Z_DIM:
+                    raise NotImplementedError("this function assumes the z-dimension is the third dimension")
+                requests.append(_Request(name, _lib.DIAG_COLUMN_INTEGRAL, q_in, state.dycore_state.delp,
+                                         0, tuple(q_in.origin) + tuple(q_in.extent), tuple(q_in.dims[:2]), "kg/m**2"))
+            else:
+                warnings.warn(f"{name} is not a supported diagnostic variable.")
+        for zselect in self.z_select:
+            for name in zselect.names:
+                quantity = zselect.variable(state.dycore_state, name)
+                if not 0 <= zselect.level < quantity.data.shape[2]:
+                    raise IndexError(f"z_select level {zselect.level} of {name}: the storage has {quantity.data.shape[2]} levels")
+                window = tuple(quantity.origin[:2]) + (0,) + tuple(quantity.extent[:2]) + (1,)
+                requests.append(_Request(f"{name}_z{zselect.level}", _lib.DIAG_PLANE, quantity, None, zselect.level, window,
+                                         tuple(quantity.dims[:2]), quantity.units))
+        return requests
 
     # ---- the reference's interface ------------------------------------------------------------------------------------------------
     def store(self, time: Union[datetime, timedelta], state):

@@ -1,6 +1,7 @@
 """Namelist-style configuration dataclasses: the subset of fv3core/pace/fv3core/_config.py:59-476 the
 acoustic step reads, with the reference's field names and defaults for the baroclinic test case."""
 import dataclasses
+from collections.abc import Mapping
 from typing import Any, Dict, Optional, Tuple
 
 
@@ -180,18 +181,43 @@ class DynamicalCoreConfig:
         ValueError and names itself, and so does a value of the wrong type (an int is taken for a float field)."""
         config = cls()
         places = (config, config.acoustic_dynamics, config.acoustic_dynamics.d_grid_shallow_water, config.acoustic_dynamics.riemann)
-        nested = ("acoustic_dynamics", "d_grid_shallow_water", "riemann")
         for key, value in values.items():
             found = False
             for place in places:
                 field = {f.name: f for f in dataclasses.fields(place)}.get(key)
-                if field is None or key in nested:
+                if field is None or key in _NESTED:
                     continue
                 setattr(place, key, strict_value(f"dycore_config.{key}", field.type, value))
                 found = True
             if not found:
                 raise ValueError(f"dycore_config has no setting {key!r}")
         config.__post_init__()
+        return config
+
+    @classmethod
+    def from_f90nml(cls, namelist) -> "DynamicalCoreConfig":
+        """From a namelist as a host model holds it (fv3core/pace/fv3core/_config.py:288-290 with util/pace/util/namelist.py:452-479):
+        any mapping, an f90nml.Namelist included, in one of the two forms SubtileGridSizer.from_namelist takes --
+
+            top-level nx_tile, nz, layout, dt_atmos and a `dycore_config` group   (the reference's test_init_from_geos.py)
+            Fortran groups, with npx, npy, npz, layout in `fv_core_nml`           (dt_atmos in whichever group holds it)
+
+        The groups are flattened (a key in two groups: ValueError), keys that no configuration class knows are dropped as the
+        reference's filter drops them, and the rest goes through from_namelist_dict: a known key of the wrong type still raises."""
+        flat = namelist_to_flatish_dict(namelist)
+        if "fv_core_nml" in namelist.keys():
+            core = namelist["fv_core_nml"]
+            npx, npy, npz, layout = core["npx"], core["npy"], core["npz"], core["layout"]
+        elif "nx_tile" in namelist.keys():
+            npx, npy, npz, layout = namelist["nx_tile"] + 1, namelist["nx_tile"] + 1, namelist["nz"], namelist["layout"]
+        else:
+            raise KeyError("Namelist format is unrecognized, expected to find nx_tile or fv_core_nml")
+        places = (cls, AcousticDynamicsConfig, DGridShallowWaterLagrangianDynamicsConfig, RiemannConfig)
+        known = {f.name for place in places for f in dataclasses.fields(place)} - set(_NESTED) - set(_DERIVED)
+        config = cls.from_namelist_dict({key: value for key, value in flat.items() if key in known})
+        config.npx, config.npy, config.npz = (strict_value(f"namelist.{k}", int, v) for k, v in (("npx", npx), ("npy", npy), ("npz", npz)))
+        config.layout = strict_value("namelist.layout", Tuple[int, int], layout)
+        config.dt_atmos = strict_value("namelist.dt_atmos", float, flat["dt_atmos"])
         return config
 
     @property
@@ -221,6 +247,26 @@ class DynamicalCoreConfig:
     @property
     def riemann(self):
         return self.acoustic_dynamics.riemann
+
+
+_NESTED = ("acoustic_dynamics", "d_grid_shallow_water", "riemann")
+# what from_f90nml takes from the grid's keys and not from a dycore setting of that name
+_DERIVED = ("layout", "npx", "npy", "npz", "dt_atmos", "ntiles")
+
+
+def namelist_to_flatish_dict(namelist) -> Dict[str, Any]:
+    """util/pace/util/namelist.py:463-479: the keys of every group of a namelist side by side with its top-level keys (one
+    level: a group inside a group stays a value).  A key that two groups hold, or a group and the top level before it, raises."""
+    flat = {}
+    for key, value in dict(namelist).items():
+        if isinstance(value, Mapping):
+            for subkey, subvalue in value.items():
+                if subkey in flat:
+                    raise ValueError("Cannot flatten this namelist, duplicate keys: " + subkey)
+                flat[subkey] = subvalue
+        else:
+            flat[key] = value
+    return flat
 
 
 @dataclasses.dataclass(frozen=True)

@@ -5,6 +5,9 @@
                                                     around whole checks, which end in their own synchronisation; medians)
     python tools/kbench.py --only diag_pack         a diagnostics step (the example file's fourteen variables) against a plain
                                                     torch restatement, the same way
+    python tools/kbench.py --only geos_wrapper      GeosDycoreWrapper's ingest and export (30 windows each way) against a torch
+                                                    restatement (one .copy_ per window, .cpu() per output), the same way, with the
+                                                    split into host staging, H2D, unpack launch, pack launch and D2H
 """
 import argparse
 import os
@@ -40,6 +43,9 @@ def main():
 
     lib = _lib.Library(args.lib) if args.lib else _lib.load(args.precision)
     n, nz = args.n, args.nz
+    if args.only == "geos_wrapper":  # (its own state: nothing of the set-up below)
+        geos_wrapper_bench(lib, n, nz, args.reps)
+        return
     m = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(m, n, nz)
     env = Env(lib, "cuda", m, n, nz)
@@ -474,6 +480,140 @@ def diag_pack_bench(lib, env, s, n, nz, reps):
           f"{np.median(dev):.1f} us each = {(read_mb + out_mb) * 1e6 / (np.median(dev) * 1e-6) / 1e9:.0f} GB/s of read + write)")
     print(f"  torch restatement (slice, contiguous, float32, cpu per variable)   {ref:9.1f} us per step   (min {min(times['torch']):.1f})")
     print(f"  ratio torch / hip {ref / hip:.2f}")
+
+
+def geos_wrapper_bench(lib, n, nz, reps):
+    """GeosDycoreWrapper's two ends without the step between them: the ingest (_put_fortran_data_in_dycore: np.copyto per
+    argument into the pinned staging buffer, one H2D copy, one pace_state_unpack launch) and the export (_prep_outputs_for_geos:
+    one pace_diag_pack launch, one D2H copy, one synchronisation) against the same work restated with torch -- per window one
+    .copy_ of the argument's slice into the field's window, per output .contiguous().cpu() of the field's window.  Both ends of
+    both paths finish with the data where it belongs and are timed with the host clock from an idle device; the paths alternate,
+    medians are reported.  The split of the HIP path comes from device events around the two copies and the two launches
+    (Library.timing), and the host clock up to the H2D copy."""
+    import time
+
+    from pace_amd.fv3core import GeosDycoreWrapper
+    from pace_amd.fv3core.initialization.geos_wrapper import ARGUMENTS, TRACERS
+    from pace_amd.util import KernelTimes, NullComm
+
+    namelist = {"nx_tile": n, "nz": nz, "dt_atmos": 225, "layout": [1, 1], "dycore_config": {"k_split": 1, "n_split": 1}}
+    wrapper = GeosDycoreWrapper(namelist, NullComm(rank=0, total_ranks=6, fill_value=0.0), "hip:gfx950", lib=lib)
+    state = wrapper.dycore_state
+    rng = np.random.default_rng(0)
+    c_args = [rng.uniform(-1.0, 1.0, wrapper._ingest[name][0]) for name in ARGUMENTS]
+    f_args = [np.asfortranarray(a) for a in c_args]
+
+    def window(field, w):
+        i0, j0, k0, ni, nj, nk = w
+        return field.data[i0:i0 + ni, j0:j0 + nj, k0:k0 + nk] if field.data.dim() == 3 else field.data[i0:i0 + ni, j0:j0 + nj]
+
+    def hip_ingest(arguments=c_args):
+        wrapper._put_fortran_data_in_dycore(*arguments)
+        torch.cuda.current_stream().synchronize()
+
+    def torch_ingest():
+        for name, a in zip(ARGUMENTS, c_args):
+            _, cut, w = wrapper._ingest[name]
+            if name == "q":
+                for t, tracer in enumerate(TRACERS):
+                    window(getattr(state, tracer), w).copy_(torch.from_numpy(a[cut + (slice(None), t)]))
+            else:
+                window(getattr(state, name), w).copy_(torch.from_numpy(a[cut]))
+        torch.cuda.current_stream().synchronize()
+
+    def hip_export():
+        return wrapper._prep_outputs_for_geos()
+
+    def torch_export():
+        return {name: window(getattr(state, name), w).contiguous().to(torch.float64).cpu() for name, w in wrapper._export.items()}
+
+    # the two paths do the same thing
+    names = list(wrapper._export)
+    torch_ingest()
+    want_state = {name: getattr(state, name).data.clone() for name in names}
+    for name in names:
+        getattr(state, name).data.zero_()
+    for arguments in (c_args, f_args):
+        hip_ingest(arguments)
+        for name in names:
+            assert torch.equal(getattr(state, name).data, want_state[name]), name
+    got, want = hip_export(), torch_export()
+    for name in names:
+        assert np.array_equal(got[name].view(np.uint64), want[name].numpy().view(np.uint64)), name  # (bit for bit)
+
+    def hip_ingest_one_thread():
+        wrapper.staging_threads, threads = 1, wrapper.staging_threads
+        hip_ingest()
+        wrapper.staging_threads = threads
+
+    paths = {"hip ingest": hip_ingest, "torch ingest": torch_ingest, "hip export": hip_export, "torch export": torch_export,
+             "hip ingest, F-ordered arguments": lambda: hip_ingest(f_args), "hip ingest, one staging thread": hip_ingest_one_thread}
+    times = {k: [] for k in paths}
+    for fn in paths.values():  # warm-up: code objects, the pinned buffers, torch's copy kernels
+        for _ in range(2):
+            fn()
+    for _ in range(reps):
+        for k, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append((time.perf_counter() - t0) * 1e3)
+
+    # the split: events around the copies, Library.timing around the launches, the host clock up to the H2D copy
+    split = {k: [] for k in ("staging C", "staging F", "h2d", "d2h")}
+    events = []
+    to_device, to_host = wrapper._to_device, wrapper._packer._to_host
+    mark = {}
+
+    def timed(kind, fn):
+        def run(a, b):
+            if kind == "h2d":
+                split[mark["staging"]].append((time.perf_counter() - mark["t0"]) * 1e3)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(a, b)
+            e1.record()
+            events.append((kind, e0, e1))
+        return run
+
+    wrapper._to_device, wrapper._packer._to_host = timed("h2d", to_device), timed("d2h", to_host)
+    launches = {"C": KernelTimes(), "F": KernelTimes()}
+    for _ in range(reps):
+        for order, arguments in (("C", c_args), ("F", f_args)):
+            lib.timing = launches[order]
+            torch.cuda.synchronize()
+            mark.update(staging="staging " + order, t0=time.perf_counter())
+            hip_ingest(arguments)
+        lib.timing = launches["C"]
+        hip_export()
+        lib.timing = None
+        torch.cuda.synchronize()
+    wrapper._to_device, wrapper._packer._to_host = to_device, to_host
+    for kind, e0, e1 in events:
+        split[kind].append(e0.elapsed_time(e1))
+    info = {order: kt.resolve() for order, kt in launches.items()}
+
+    def per_call(order, name):
+        return info[order][name]["total_run_time"] / info[order][name]["ncalls"] * 1e3
+
+    in_elems, out_elems = wrapper._staging.numel(), sum(int(np.prod(w[3:])) for w in wrapper._export.values())
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(f"geos_wrapper C{n} x {nz}, float{8 * lib.real_bytes} fields: 30 windows in ({in_elems * 8 / 1e6:.0f} MB of float64), 30 out "
+          f"({out_elems * 8 / 1e6:.0f} MB of float64); medians of {reps} alternating runs, ms")
+    for k in paths:
+        print(f"  {k:34s} {med[k]:9.2f}   (min {min(times[k]):.2f})")
+    print(f"  ratio torch / hip: ingest {med['torch ingest'] / med['hip ingest']:.2f}, export {med['torch export'] / med['hip export']:.2f}, "
+          f"both {(med['torch ingest'] + med['torch export']) / (med['hip ingest'] + med['hip export']):.2f}")
+    unpack_c, unpack_f, pack = per_call("C", "pace_state_unpack"), per_call("F", "pace_state_unpack"), per_call("C", "pace_diag_pack")
+    h2d, d2h = float(np.median(split["h2d"])), float(np.median(split["d2h"]))
+    print(f"  split of the HIP path, {wrapper.staging_threads} staging threads (medians; launches: mean device time between events):")
+    print(f"    host staging (np.copyto per argument)  C-ordered {np.median(split['staging C']):8.2f}   F-ordered {np.median(split['staging F']):8.2f}")
+    print(f"    H2D copy  {h2d:8.2f} = {in_elems * 8 / (h2d * 1e-3) / 1e9:6.1f} GB/s      D2H copy + synchronisation {d2h:8.2f} = "
+          f"{out_elems * 8 / (d2h * 1e-3) / 1e9:6.1f} GB/s")
+    gb_in, gb_out = in_elems * (8 + lib.real_bytes) / 1e9, out_elems * (8 + lib.real_bytes) / 1e9
+    print(f"    pace_state_unpack  ZFAST items (in_step 7 for q) {unpack_c:7.3f} = {gb_in / (unpack_c * 1e-3):6.0f} GB/s of read + write   "
+          f"XFAST items {unpack_f:7.3f} = {gb_in / (unpack_f * 1e-3):6.0f} GB/s")
+    print(f"    pace_diag_pack     {pack:7.3f} = {gb_out / (pack * 1e-3):6.0f} GB/s of read + write")
 
 
 if __name__ == "__main__":
