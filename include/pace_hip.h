@@ -630,6 +630,58 @@ typedef struct {
 } pace_unpack_item_t;
 int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, int nitems, const double* in, void* stream);
 
+/* ---- The checkpointers (util/pace/util/checkpointer/thresholds.py:59-162, validation.py:14-143): calibration and validation
+ * of up to PACE_CKPT_MAX_ITEMS variables per call, both storage types, no atomics, no host synchronisation.  items: HOST array.
+ * A variable is its base pointer, its logical extents (ni, nj, nk) in storage order and its strides (1, sj, sk) in elements --
+ * no pace_geom_t: 2-D fields (nk = 1), dense 1-D arrays (nj = nk = 1) and temporaries are variables too.  Elements are widened
+ * to double first; accumulators, expected values and results are double in both libraries.  The padding of a row (i >= ni) is
+ * never read.
+ *   pace_ckpt_accumulate  ONE launch.  mn, mx, asum: dense DEVICE arrays of ni * nj * nk doubles, x fastest.  first != 0:
+ *                         mn = mx = v, asum = |v| (they need no initialisation); otherwise mn = minimum(mn, v), mx =
+ *                         maximum(mx, v), asum = asum + |v| with numpy's NaN propagation; one accumulator per element, added
+ *                         to in call order.
+ *   pace_ckpt_thresholds  partials, then a combine.  out: DEVICE array of 4 * nitems doubles, per item
+ *                           [0] the maximum of (mx - mn) / (asum / n_trials) over the quotients that are no NaN (numpy's nanmax:
+ *                               0 / 0 is skipped, x / 0 is inf and counts), NaN if every quotient is a NaN
+ *                           [1] the maximum of mx - mn, NaN if one of them is (numpy's max)
+ *                           [2] 1.0 if asum / n_trials == 0 everywhere, else 0.0
+ *                           [3] the number of elements whose mx - mn is a NaN
+ *   pace_ckpt_validate    partials, then a combine.  The window (i0, j0, k0, wi, wj, wk) of the storage against expected, a
+ *                         DEVICE array of doubles whose element for window point (i, j, k) is expected[i * ei + j * ej + k * ek].
+ *                         With output a and expected d, numpy.testing.assert_allclose's rules: the relative test where d != 0
+ *                         with bound rtol * |d|, the absolute test everywhere with bound atol; a NaN rtol / atol skips that test;
+ *                         both NaN match, one NaN violates; if either is infinite they match only if a == d; otherwise a
+ *                         violation iff !(|a - d| <= bound).  out: DEVICE array of 6 * nitems doubles, per item
+ *                           [0] violations of the relative test, [1] of the absolute test,
+ *                           [2] the largest |a - d| over finite pairs, [3] the largest |a - d| / |d| over finite pairs with d != 0,
+ *                           [4] the smallest expected-array offset i * ei + j * ej + k * ek of a violating element (its flat
+ *                               index in a dense expected array), -1 if there is none, [5] the number of elements compared.
+ *                         Nothing outside the window is read.
+ * workspace: at least pace_ckpt_*_workspace_bytes(items, nitems) bytes of device memory (0: invalid items); it holds nothing
+ * between calls and need not be cleared.  PACE_ERR_ARG: nitems < 1 or > PACE_CKPT_MAX_ITEMS, a NULL pointer the call uses, an
+ * extent < 1, sj < ni, sk < sj * (nj - 1) + ni, n_trials < 1, a window that is empty or outside the extents, a negative expected
+ * stride.  PACE_ERR_UNSUPPORTED: a variable of 2^31 elements or more. */
+#define PACE_CKPT_MAX_ITEMS 32
+typedef struct {
+  const pace_real_t* field; /* element (0, 0, 0) of the storage */
+  int32_t ni, nj, nk;       /* logical extents in storage order, x fastest */
+  int32_t pad_;
+  int64_t sj, sk;           /* strides in elements; the stride along i is 1 */
+  double* mn;               /* accumulate (written), thresholds (read): dense, ni * nj * nk */
+  double* mx;
+  double* asum;
+  int32_t i0, j0, k0;       /* validate: origin of the window in the storage */
+  int32_t wi, wj, wk;       /* ... and its extent */
+  const double* expected;   /* validate: the expected values */
+  int64_t ei, ej, ek;       /* ... and their element strides along the storage axes i, j, k */
+  double rtol, atol;        /* validate: NaN skips the test */
+} pace_ckpt_item_t;
+int pace_ckpt_accumulate(const pace_ckpt_item_t* items, int nitems, int first, void* stream);
+int64_t pace_ckpt_thresholds_workspace_bytes(const pace_ckpt_item_t* items, int nitems);
+int pace_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_trials, void* workspace, double* out, void* stream);
+int64_t pace_ckpt_validate_workspace_bytes(const pace_ckpt_item_t* items, int nitems);
+int pace_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspace, double* out, void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

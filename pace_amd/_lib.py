@@ -137,6 +137,16 @@ class UnpackItem(C.Structure):  # include/pace_hip.h pace_unpack_item_t
                 ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("in_step", C.c_int32), ("in_offset", C.c_int64)]
 
 
+CKPT_MAX_ITEMS = 32  # include/pace_hip.h PACE_CKPT_MAX_ITEMS
+
+
+class CkptItem(C.Structure):  # include/pace_hip.h pace_ckpt_item_t
+    _fields_ = [("field", c_dp), ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("pad_", C.c_int32),
+                ("sj", C.c_int64), ("sk", C.c_int64), ("mn", c_dp), ("mx", c_dp), ("asum", c_dp),
+                ("i0", C.c_int32), ("j0", C.c_int32), ("k0", C.c_int32), ("wi", C.c_int32), ("wj", C.c_int32), ("wk", C.c_int32),
+                ("expected", c_dp), ("ei", C.c_int64), ("ej", C.c_int64), ("ek", C.c_int64), ("rtol", C.c_double), ("atol", C.c_double)]
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -236,6 +246,11 @@ _PROTOS = {
     "pace_state_extrema": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_int), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_diag_pack": (C.c_int, [_P(Geom), _P(DiagItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pace_state_unpack": (C.c_int, [_P(Geom), _P(UnpackItem), C.c_int, c_dp, C.c_void_p]),
+    "pace_ckpt_accumulate": (C.c_int, [_P(CkptItem), C.c_int, C.c_int, C.c_void_p]),
+    "pace_ckpt_thresholds_workspace_bytes": (C.c_int64, [_P(CkptItem), C.c_int]),
+    "pace_ckpt_thresholds": (C.c_int, [_P(CkptItem), C.c_int, C.c_int, C.c_void_p, c_dp, C.c_void_p]),
+    "pace_ckpt_validate_workspace_bytes": (C.c_int64, [_P(CkptItem), C.c_int]),
+    "pace_ckpt_validate": (C.c_int, [_P(CkptItem), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

@@ -707,6 +707,66 @@ int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, 
   return launch_state_unpack(make_geo(geom), items, nitems, in, S(stream));
 }
 
+// the checkpointers' items: `accumulators`: mn / mx / asum are used; `window`: the window and the expected values are
+static int ckpt_check(const pace_ckpt_item_t* items, int nitems, bool accumulators, bool window) {
+  if (!items || nitems < 1 || nitems > PACE_CKPT_MAX_ITEMS) return PACE_ERR_ARG;
+  for (int m = 0; m < nitems; ++m) {
+    const pace_ckpt_item_t& it = items[m];
+    if (it.ni < 1 || it.nj < 1 || it.nk < 1) return PACE_ERR_ARG;
+    if ((int64_t)it.ni * it.nj * it.nk >= ((int64_t)1 << 31)) return PACE_ERR_UNSUPPORTED;
+    if (accumulators && (!it.mn || !it.mx || !it.asum)) return PACE_ERR_ARG;
+    if (window) {
+      if (!it.field || !it.expected || it.ei < 0 || it.ej < 0 || it.ek < 0) return PACE_ERR_ARG;
+      if (it.i0 < 0 || it.wi < 1 || it.wi > it.ni - it.i0 || it.j0 < 0 || it.wj < 1 || it.wj > it.nj - it.j0 || it.k0 < 0 ||
+          it.wk < 1 || it.wk > it.nk - it.k0)
+        return PACE_ERR_ARG;
+    }
+  }
+  return PACE_OK;
+}
+static int ckpt_check_storage(const pace_ckpt_item_t* items, int nitems) {
+  for (int m = 0; m < nitems; ++m) {
+    const pace_ckpt_item_t& it = items[m];
+    if (!it.field || it.sj < it.ni || it.sk < it.sj * (it.nj - 1) + it.ni) return PACE_ERR_ARG;
+  }
+  return PACE_OK;
+}
+
+int pace_ckpt_accumulate(const pace_ckpt_item_t* items, int nitems, int first, void* stream) {
+  int rc = ckpt_check(items, nitems, true, false);
+  if (rc == PACE_OK) rc = ckpt_check_storage(items, nitems);
+  if (rc != PACE_OK) return rc;
+  (void)hipGetLastError();
+  return launch_ckpt_accumulate(items, nitems, first, S(stream));
+}
+
+int64_t pace_ckpt_thresholds_workspace_bytes(const pace_ckpt_item_t* items, int nitems) {
+  if (ckpt_check(items, nitems, false, false) != PACE_OK) return 0;
+  return (int64_t)ckpt_thresholds_blocks(items, nitems) * 4 * (int64_t)sizeof(double);
+}
+
+int pace_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_trials, void* workspace, double* out, void* stream) {
+  const int rc = ckpt_check(items, nitems, true, false);
+  if (rc != PACE_OK) return rc;
+  if (n_trials < 1 || !workspace || !out) return PACE_ERR_ARG;
+  (void)hipGetLastError();
+  return launch_ckpt_thresholds(items, nitems, n_trials, workspace, out, S(stream));
+}
+
+int64_t pace_ckpt_validate_workspace_bytes(const pace_ckpt_item_t* items, int nitems) {
+  if (ckpt_check(items, nitems, false, true) != PACE_OK) return 0;
+  return (int64_t)ckpt_validate_blocks(items, nitems) * 6 * (int64_t)sizeof(double);
+}
+
+int pace_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspace, double* out, void* stream) {
+  int rc = ckpt_check(items, nitems, false, true);
+  if (rc == PACE_OK) rc = ckpt_check_storage(items, nitems);
+  if (rc != PACE_OK) return rc;
+  if (!workspace || !out) return PACE_ERR_ARG;
+  (void)hipGetLastError();
+  return launch_ckpt_validate(items, nitems, workspace, out, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

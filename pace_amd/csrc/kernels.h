@@ -283,6 +283,12 @@ int launch_state_extrema(const Geo& g, const real* const* fields, const int* com
 int launch_diag_pack(const Geo& g, const pace_diag_item_t* items, int nitems, int out_is_double, void* out, hipStream_t st);
 // k_state.hip
 int launch_state_unpack(const Geo& g, const pace_unpack_item_t* items, int nitems, const double* in, hipStream_t st);
+// k_ckpt.hip
+long ckpt_thresholds_blocks(const pace_ckpt_item_t* items, int nitems);
+long ckpt_validate_blocks(const pace_ckpt_item_t* items, int nitems);
+int launch_ckpt_accumulate(const pace_ckpt_item_t* items, int nitems, int first, hipStream_t st);
+int launch_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_trials, void* workspace, double* out, hipStream_t st);
+int launch_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspace, double* out, hipStream_t st);
 // k_dycore.hip
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);

@@ -4,3 +4,6 @@ from .comm import LoopbackComm, NullComm, ThreadComm, TorchDistComm, run_tiles  
 from .halo import CubedSphereCommunicator, HaloUpdater, QuantityHaloSpec, WrappedHaloUpdater  # noqa: F401,E402
 from .partitioner import CubedSpherePartitioner, RingPartitioner, TilePartitioner  # noqa: F401,E402
 from ._timing import KernelTimes, NullTimer, Timer  # noqa: F401,E402
+from .checkpointer import (Checkpointer, InsufficientTrialsError, NullCheckpointer, SavepointThresholds, SnapshotCheckpointer,  # noqa: F401,E402
+                           Threshold, ThresholdCalibrationCheckpointer, ValidationCheckpointer)
+from . import testing  # noqa: F401,E402

@@ -8,6 +8,8 @@
     python tools/kbench.py --only geos_wrapper      GeosDycoreWrapper's ingest and export (30 windows each way) against a torch
                                                     restatement (one .copy_ per window, .cpu() per output), the same way, with the
                                                     split into host staging, H2D, unpack launch, pack launch and D2H
+    python tools/kbench.py --only checkpointer      a calibration call and a validation call with the sixteen fields of D_SW-In
+                                                    against a torch restatement and against "to the host and numpy", the same way
 """
 import argparse
 import os
@@ -45,6 +47,9 @@ def main():
     n, nz = args.n, args.nz
     if args.only == "geos_wrapper":  # (its own state: nothing of the set-up below)
         geos_wrapper_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "checkpointer":  # (its own fields)
+        checkpointer_bench(lib, n, nz, args.reps)
         return
     m = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(m, n, nz)
@@ -480,6 +485,118 @@ def diag_pack_bench(lib, env, s, n, nz, reps):
           f"{np.median(dev):.1f} us each = {(read_mb + out_mb) * 1e6 / (np.median(dev) * 1e-6) / 1e9:.0f} GB/s of read + write)")
     print(f"  torch restatement (slice, contiguous, float32, cpu per variable)   {ref:9.1f} us per step   (min {min(times['torch']):.1f})")
     print(f"  ratio torch / hip {ref / hip:.2f}")
+
+
+def checkpointer_bench(lib, n, nz, reps):
+    """A calibration call and a validation call with sixteen whole fields (what D_SW-In hands over) of the C<n> x <nz> storage.
+
+    calibration   ThresholdCalibrationCheckpointer.__call__ in a second trial (one pace_ckpt_accumulate launch: 1 pass read
+                  and 3 read-modify-write of doubles, 7 element passes) against the reference's fold restated with torch:
+                  minimum, maximum, abs and add per field, 64 launches and 11 element passes.  Neither synchronises; both are
+                  timed with the host clock from an idle device to the end of a synchronisation added for the measurement.
+    validation    ValidationCheckpointer.__call__ against an npz savepoint file with all thresholds 0 (staging, one H2D copy,
+                  one launch pair, one transfer of 96 doubles) against "transfer every field to the host and compare in numpy":
+                  .cpu().numpy() per field and the reference's two assert_allclose calls on host copies of the same slabs.
+    The two of a pair alternate; medians are reported."""
+    import tempfile
+    import time
+
+    from pace_amd.util import (QuantityFactory, SavepointThresholds, SubtileGridSizer, Threshold, ThresholdCalibrationCheckpointer,
+                               ValidationCheckpointer)
+
+    real = torch.float32 if lib.real_bytes == 4 else torch.float64
+    sizer = SubtileGridSizer.from_tile_params(nx_tile=n, ny_tile=n, nz=nz, n_halo=3, extra_dim_lengths={}, layout=(1, 1))
+    qf = QuantityFactory(sizer, device="cuda", dtype=real)
+    rng = np.random.default_rng(0)
+    names = [f"f{m}" for m in range(16)]
+    host = {name: rng.uniform(1.0, 2.0, (n + 7, n + 7, nz + 1)).astype(np.float32 if lib.real_bytes == 4 else np.float64)
+            for name in names}
+    fields = {name: qf.from_array(a, ["x", "y", "z_interface"], "u") for name, a in host.items()}
+    elements = (n + 7) * (n + 7) * (nz + 1)
+
+    calibration = ThresholdCalibrationCheckpointer(lib=lib)
+    with calibration.trial():
+        calibration("D_SW-In", **fields)
+    state = {name: [torch.full_like(q.data, float("inf")), torch.full_like(q.data, float("-inf")), torch.zeros_like(q.data)]
+             for name, q in fields.items()}
+
+    def hip_calibrate():
+        calibration._n_calls["D_SW-In"] = 0
+        calibration("D_SW-In", **fields)
+
+    def torch_calibrate():
+        for name, q in fields.items():
+            acc = state[name]
+            acc[0] = torch.minimum(acc[0], q.data)
+            acc[1] = torch.maximum(acc[1], q.data)
+            acc[2] += torch.abs(q.data)
+
+    scratch = tempfile.TemporaryDirectory()  # (406 MB of savepoint data: removed at the end)
+    directory = scratch.name
+    np.savez(os.path.join(directory, "D_SW-In.npz"), **{name: a[None, None].astype(np.float64) for name, a in host.items()})
+    zero = SavepointThresholds({"D_SW-In": [{name: Threshold(0.0, 0.0) for name in names}]})
+    validation = ValidationCheckpointer(directory, zero, 0, lib=lib)
+    expected = {name: a.astype(np.float64) for name, a in host.items()}
+
+    def hip_validate():
+        validation._n_calls["D_SW-In"] = 0
+        validation("D_SW-In", **fields)
+
+    def numpy_validate():
+        for name, q in fields.items():
+            output, want = q.data.cpu().numpy(), expected[name]
+            not_zero = want != 0
+            np.testing.assert_allclose(output[not_zero], want[not_zero], rtol=0.0, atol=0.0, err_msg=name)
+            np.testing.assert_allclose(output, want, rtol=0.0, atol=0.0, err_msg=name)
+
+    print(f"checkpointer C{n} x {nz}, float{8 * lib.real_bytes} fields: sixteen fields of {elements} elements "
+          f"({16 * elements * lib.real_bytes / 1e6:.0f} MB); medians of alternating runs, ms")
+    for title, paths, count in (("calibration call", {"hip": hip_calibrate, "torch": torch_calibrate}, reps),
+                                ("validation call", {"hip": hip_validate, "numpy on the host": numpy_validate}, max(3, reps // 4))):
+        times = {k: [] for k in paths}
+        for fn in paths.values():
+            for _ in range(2):
+                fn()
+        for _ in range(count):
+            for k, fn in paths.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) * 1e3)
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        for k in paths:
+            print(f"  {title:18s} {k:18s} {med[k]:10.3f} ms   (min {min(times[k]):.3f}, {count} runs)")
+        other = [k for k in paths if k != "hip"][0]
+        print(f"  {title:18s} ratio {other} / hip {med[other] / med['hip']:.2f}")
+    moved = 16 * elements * (lib.real_bytes + 6 * 8)
+    print(f"  the accumulate launch moves {moved / 1e6:.0f} MB: {moved / (np.median(times_hip_calibrate(hip_calibrate)) * 1e-3) / 1e9:.0f} GB/s in device events")
+    # the validation's launch pair alone: device events around the entry point (Library.timing)
+    from pace_amd.util import KernelTimes
+
+    lib.timing = launches = KernelTimes()
+    for _ in range(5):
+        hip_validate()
+    lib.timing = None
+    pair = launches.resolve()["pace_ckpt_validate"]
+    pair_ms = pair["total_run_time"] / pair["ncalls"] * 1e3
+    read = 16 * elements * (lib.real_bytes + 8)
+    print(f"  pace_ckpt_validate alone (launch pair, device events, mean of {pair['ncalls']}): {pair_ms:.3f} ms for {read / 1e6:.0f} MB read "
+          f"= {read / (pair_ms * 1e-3) / 1e9:.0f} GB/s (the expected slabs are C-ordered: lanes read them with a stride of {(n + 7) * (nz + 1)} doubles)")
+    scratch.cleanup()
+
+
+def times_hip_calibrate(fn, reps=10):
+    """device-event times (ms) of the calibration call"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for _ in range(reps):
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
 
 
 def geos_wrapper_bench(lib, n, nz, reps):
