@@ -630,6 +630,16 @@ typedef struct {
 } pace_unpack_item_t;
 int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, int nitems, const double* in, void* stream);
 
+/* ---- The interface pressures of a state read from a Fortran restart, which holds delp only
+ * (driver/pace/driver/initialization.py:422-442), ONE launch:
+ *   pe(i, j, k) = ptop + sum over l < k of delp(i, j, l),  peln = log(pe),  k = 0 .. nk
+ * on every column of the WHOLE storage (n + 7) x (n + 7), halo and stagger row included (the reference writes .data, not the
+ * view); the row padding is neither read nor written.  The sum is one double accumulator in ascending k (the order of a
+ * sequential numpy cumsum), the logarithm is taken of that double, and both results are narrowed on the store only (float32
+ * library).  No atomics, no workspace, no host synchronisation.  PACE_ERR_ARG: a NULL pointer, nk < 1. */
+int pace_pe_peln_from_delp(const pace_geom_t* geom, const pace_real_t* delp, double ptop, pace_real_t* pe, pace_real_t* peln,
+                           void* stream);
+
 /* ---- The checkpointers (util/pace/util/checkpointer/thresholds.py:59-162, validation.py:14-143): calibration and validation
  * of up to PACE_CKPT_MAX_ITEMS variables per call, both storage types, no atomics, no host synchronisation.  items: HOST array.
  * A variable is its base pointer, its logical extents (ni, nj, nk) in storage order and its strides (1, sj, sk) in elements --

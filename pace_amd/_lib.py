@@ -246,6 +246,7 @@ _PROTOS = {
     "pace_state_extrema": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_int), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_diag_pack": (C.c_int, [_P(Geom), _P(DiagItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pace_state_unpack": (C.c_int, [_P(Geom), _P(UnpackItem), C.c_int, c_dp, C.c_void_p]),
+    "pace_pe_peln_from_delp": (C.c_int, [_P(Geom), c_dp, C.c_double, c_dp, c_dp, C.c_void_p]),
     "pace_ckpt_accumulate": (C.c_int, [_P(CkptItem), C.c_int, C.c_int, C.c_void_p]),
     "pace_ckpt_thresholds_workspace_bytes": (C.c_int64, [_P(CkptItem), C.c_int]),
     "pace_ckpt_thresholds": (C.c_int, [_P(CkptItem), C.c_int, C.c_int, C.c_void_p, c_dp, C.c_void_p]),

@@ -707,6 +707,11 @@ int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, 
   return launch_state_unpack(make_geo(geom), items, nitems, in, S(stream));
 }
 
+int pace_pe_peln_from_delp(const pace_geom_t* geom, const real* delp, double ptop, real* pe, real* peln, void* stream) {
+  NEED(geom && delp && pe && peln);
+  return launch_pe_peln_from_delp(make_geo(geom), delp, ptop, pe, peln, S(stream));
+}
+
 // the checkpointers' items: `accumulators`: mn / mx / asum are used; `window`: the window and the expected values are
 static int ckpt_check(const pace_ckpt_item_t* items, int nitems, bool accumulators, bool window) {
   if (!items || nitems < 1 || nitems > PACE_CKPT_MAX_ITEMS) return PACE_ERR_ARG;

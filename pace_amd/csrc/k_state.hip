@@ -32,8 +32,18 @@
 // nothing outside its ni * nj * nk (ni * nj) source elements is read.  No atomics, no workspace.  The narrowing is a plain cast:
 // round to nearest even, overflow to +-inf, as ndarray.astype(np.float32).  Two items whose windows overlap on one field: the
 // result is undefined (their workgroups run in any order).
+//
+//   k_pe_peln_from_delp  the interface pressures a Fortran restart does not hold (driver/pace/driver/initialization.py:422-442):
+//                   pe(i, j, k) = ptop + sum of delp(i, j, l) over l < k and peln = log(pe), k = 0 .. nk, on every column of the
+//                   WHOLE storage (n + 7) x (n + 7), halo and stagger row included, as the reference writes .data.  One thread
+//                   per column; the plane is flattened over its padded rows, so lane l of a wave reads and writes element l of a
+//                   512-byte (float32: 256-byte) aligned run at every level; the lanes of the row padding return before they
+//                   touch memory.  One double accumulator in ascending k, pe = ptop + s, then s += delp: additions only, the
+//                   order of a sequential numpy cumsum.  peln = lean_log of that double (lean_math.h: <= 0.546 ulp); both are
+//                   narrowed on the store only.  nk loads and 2 (nk + 1) stores per column, no LDS, no atomics, no workspace.
 #include "common.h"
 #include "kernels.h"
+#include "lean_math.h"
 
 #define SU_TI 64
 #define SU_TS 32
@@ -120,6 +130,32 @@ int launch_state_unpack(const Geo& g, const pace_unpack_item_t* items, int nitem
   }
   const dim3 grid((unsigned)tab.first[nitems]), block(64 * SU_WAVES);
   hipLaunchKernelGGL(k_state_unpack, grid, block, 0, st, g, tab, in);
+  PACE_CHECK_LAUNCH();
+  return PACE_OK;
+}
+
+__global__ void __launch_bounds__(64) k_pe_peln_from_delp(Geo g, const real* __restrict__ delp, double ptop, real* __restrict__ pe,
+                                                          real* __restrict__ peln) {
+  const long p = (long)blockIdx.x * 64 + threadIdx.x;
+  const int j = (int)(p / g.sj);
+  const int i = (int)(p - (long)j * g.sj);
+  if (j >= g.nj || i >= g.ni) return;
+  long c = IDX2(g, i, j);
+  double s = 0.0;
+  for (int k = 0; k < g.nk; ++k, c += g.sk) {
+    const double v = ptop + s;
+    pe[c] = (real)v;
+    peln[c] = (real)lean_log(v);
+    s += (double)delp[c];
+  }
+  const double v = ptop + s;
+  pe[c] = (real)v;
+  peln[c] = (real)lean_log(v);
+}
+
+int launch_pe_peln_from_delp(const Geo& g, const real* delp, double ptop, real* pe, real* peln, hipStream_t st) {
+  const dim3 grid((unsigned)(((long)g.sj * g.nj + 63) / 64)), block(64);
+  hipLaunchKernelGGL(k_pe_peln_from_delp, grid, block, 0, st, g, delp, ptop, pe, peln);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }

@@ -283,6 +283,7 @@ int launch_state_extrema(const Geo& g, const real* const* fields, const int* com
 int launch_diag_pack(const Geo& g, const pace_diag_item_t* items, int nitems, int out_is_double, void* out, hipStream_t st);
 // k_state.hip
 int launch_state_unpack(const Geo& g, const pace_unpack_item_t* items, int nitems, const double* in, hipStream_t st);
+int launch_pe_peln_from_delp(const Geo& g, const real* delp, double ptop, real* pe, real* peln, hipStream_t st);
 // k_ckpt.hip
 long ckpt_thresholds_blocks(const pace_ckpt_item_t* items, int nitems);
 long ckpt_validate_blocks(const pace_ckpt_item_t* items, int nitems);

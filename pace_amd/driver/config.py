@@ -5,8 +5,10 @@ hand where the reference uses dacite.
 
 What is accepted, refused and ignored:
 
-  initialization.type   baroclinic, predefined; restart / fortran_restart / serialbox / tropicalcyclone: NotImplementedError
-  grid_config.type      generated (the gnomonic grid of pace_amd.util.gridgen, not stretched); serialbox: NotImplementedError
+  initialization.type   baroclinic, predefined, fortran_restart (the Fortran model's restart files: FortranRestartInit);
+                        restart / serialbox / tropicalcyclone: NotImplementedError
+  grid_config.type      generated (the gnomonic grid of pace_amd.util.gridgen, not stretched; config.restart_path: ak / bk and
+                        what derives from them come from <restart_path>/fv_core.res.nc); serialbox: NotImplementedError
   layout                (1, 1)
   comm_config.type      null (null_comm), torch; mpi, write, read: NotImplementedError.  Absent: null, rank 0 of 6 -- the
                         reference's default is mpi, which does not exist here
@@ -17,8 +19,10 @@ What is accepted, refused and ignored:
   performance_config    parsed and kept; nothing is written
   stencil_config.compilation_config.backend  kept as `requested_backend`; the backend is always hip:gfx950
 """
+import ctypes as C
 import dataclasses
 import functools
+import os
 import warnings
 from datetime import datetime, timedelta
 from math import floor
@@ -92,8 +96,48 @@ class PredefinedStateInit:
                            driver_grid_data=self.driver_grid_data)
 
 
-_INITIALIZERS = {"baroclinic": BaroclinicInit, "predefined": PredefinedStateInit}
-_REFUSED_INITIALIZERS = ("restart", "fortran_restart", "serialbox", "tropicalcyclone")
+@dataclasses.dataclass
+class FortranRestartInit:
+    """Configuration for fortran restart initialization (initialization.py:223-276): the state of `path`'s fv_core, fv_tracer
+    and fv_srf_wnd files, the time of its coupler.res."""
+
+    path: str = "."
+
+    @property
+    def start_time(self) -> datetime:
+        """Reads the last line in coupler.res to find the restart time"""
+        from ..util.restart import get_current_date_from_coupler_res
+
+        coupler_files = sorted(name for name in os.listdir(self.path) if name.endswith("coupler.res"))
+        if not coupler_files:
+            raise ValueError(f"no coupler.res found at {self.path}")
+        return get_current_date_from_coupler_res(os.path.join(self.path, coupler_files[0]))
+
+    def get_driver_state(self, quantity_factory, communicator, damping_coefficients, driver_grid_data, grid_data) -> DriverState:
+        from ..fv3core.initialization.dycore_state import DycoreState
+
+        dycore_state = DycoreState.from_fortran_restart(quantity_factory=quantity_factory, communicator=communicator, path=self.path)
+        state = DriverState(dycore_state=dycore_state,
+                            physics_state=PhysicsState.init_zeros(quantity_factory=quantity_factory, active_packages=["microphysics"]),
+                            tendency_state=TendencyState.init_zeros(quantity_factory=quantity_factory), grid_data=grid_data,
+                            damping_coefficients=damping_coefficients, driver_grid_data=driver_grid_data)
+        _update_fortran_restart_pe_peln(state, quantity_factory, communicator)
+        return state
+
+
+def _update_fortran_restart_pe_peln(state: DriverState, quantity_factory, communicator) -> None:
+    """Fortran restart data don't have information on pressure interface values and their logs (initialization.py:422-442):
+    pe = ptop + the sum of delp above, peln = log(pe), over the whole storage, with ptop = ak[0] -- ONE launch of
+    pace_pe_peln_from_delp (pace_amd/csrc/k_state.hip)."""
+    from ..util.grid import geom_struct
+
+    dycore_state = state.dycore_state
+    communicator.lib.call("pace_pe_peln_from_delp", C.byref(geom_struct(quantity_factory)), dycore_state.delp.ptr,
+                          float(state.grid_data.ak[0]), dycore_state.pe.ptr, dycore_state.peln.ptr, communicator.stream())
+
+
+_INITIALIZERS = {"baroclinic": BaroclinicInit, "predefined": PredefinedStateInit, "fortran_restart": FortranRestartInit}
+_REFUSED_INITIALIZERS = ("restart", "serialbox", "tropicalcyclone")
 
 
 @dataclasses.dataclass
@@ -114,8 +158,8 @@ class InitializerSelector:
             return config
         kind = _selector_type("initialization", config, ("type", "config"))
         if kind in _REFUSED_INITIALIZERS:
-            raise NotImplementedError(f"initialization.type {kind!r}: pace_amd.driver initialises from 'baroclinic' or a "
-                                      "'predefined' state (no restart or Serialbox reader)")
+            raise NotImplementedError(f"initialization.type {kind!r}: pace_amd.driver initialises from 'baroclinic', a "
+                                      "'fortran_restart' or a 'predefined' state (no reader of pace's own restart or of Serialbox)")
         if kind not in _INITIALIZERS:
             raise ValueError(f"initialization.type {kind!r} is none of {sorted(_INITIALIZERS)}")
         values = dict(config.get("config") or {})
@@ -139,7 +183,8 @@ def _selector_type(where, config, keys, default=None):
 # ---- grid ---------------------------------------------------------------------------------------------------------------------
 @dataclasses.dataclass
 class GeneratedGridConfig:
-    """grid.py:80-131: the gnomonic cubed sphere, generated; stretching and the restart grid are refused."""
+    """grid.py:80-131: the gnomonic cubed sphere, generated; stretching is refused.  restart_path: the directory of a Fortran
+    restart whose fv_core.res.nc gives the vertical grid (ak, bk) in place of the generated one."""
 
     stretch_factor: Optional[float] = 1.0
     lon_target: Optional[float] = 350.0
@@ -149,17 +194,28 @@ class GeneratedGridConfig:
     def __post_init__(self):
         if self.stretch_factor not in (None, 1.0):
             raise NotImplementedError(f"grid_config.config.stretch_factor {self.stretch_factor}: the stretched grid is not generated")
-        if self.restart_path is not None:
-            raise NotImplementedError("grid_config.config.restart_path: the grid is generated, never read")
 
     def get_grid(self, quantity_factory, communicator):
         from ..util.grid import DampingCoefficients, DriverGridData, GridData, MetricTerms
 
         metric_terms = MetricTerms(quantity_factory=quantity_factory, communicator=communicator)
         grid_data = GridData.new_from_metric_terms(metric_terms)
+        if self.restart_path is not None:
+            grid_data.set_vertical_grid(*_vertical_grid_from_restart(self.restart_path))
         damping_coefficients = DampingCoefficients.new_from_metric_terms(metric_terms, grid_data)
         driver_grid_data = DriverGridData.new_from_metric_terms(metric_terms)
         return damping_coefficients, driver_grid_data, grid_data
+
+
+def _vertical_grid_from_restart(restart_path: str):
+    """-> (ak, bk) of <restart_path>/[label.]fv_core.res.nc (grid/helper.py:152-176, VerticalGridData.from_restart)."""
+    from ..util.checkpointer.validation import _open_nc
+
+    data_files = sorted(name for name in os.listdir(restart_path) if name.endswith("fv_core.res.nc"))
+    if not data_files:
+        raise ValueError(f"grid_config.config.restart_path is set, but there is no fv_core.res.nc in {restart_path}")
+    file = _open_nc(os.path.join(restart_path, data_files[0]))
+    return file.record("ak"), file.record("bk")
 
 
 @dataclasses.dataclass
@@ -314,7 +370,7 @@ class DriverConfig:
 
     Attributes:
         stencil_config: configuration for stencil compilation (kept; there is one backend)
-        initialization: "baroclinic" or "predefined", with the chosen type's configuration
+        initialization: "baroclinic", "fortran_restart" or "predefined", with the chosen type's configuration
         nx_tile: number of gridpoints along the horizontal dimension of a cube
             tile face, same value used for both horizontal dimensions
         nz: number of gridpoints in the vertical dimension

@@ -19,6 +19,15 @@ _FIELDS = {
     "qgraupel": (_C, "kg/kg"), "qo3mr": (_C, "kg/kg"), "qsgs_tke": (_C, "m**2/s**2"), "qcld": (_C, ""),
 }
 
+# the fields DycoreState.from_fortran_restart fills -> their standard names (pace_amd.util.restart.RESTART_PROPERTIES)
+FORTRAN_RESTART_FIELDS = {
+    "pt": "air_temperature", "delp": "pressure_thickness_of_atmospheric_layer", "phis": "surface_geopotential",
+    "w": "vertical_wind", "u": "x_wind", "v": "y_wind", "qvapor": "specific_humidity",
+    "qliquid": "cloud_liquid_water_mixing_ratio", "qice": "cloud_ice_mixing_ratio", "qrain": "rain_mixing_ratio",
+    "qsnow": "snow_mixing_ratio", "qgraupel": "graupel_mixing_ratio", "qo3mr": "ozone_mixing_ratio", "qcld": "cloud_fraction",
+    "delz": "vertical_thickness_of_atmospheric_layer",
+}
+
 
 @dataclasses.dataclass
 class DycoreState:
@@ -68,3 +77,15 @@ class DycoreState:
         for name, a in dict_of_numpy_arrays.items():
             getattr(state, name).set(a)
         return state
+
+    @classmethod
+    def from_fortran_restart(cls, *, quantity_factory, communicator, path: str):
+        """dycore_state.py:361-427: zeros, then the compute domains of the fifteen fields a Fortran restart holds, through
+        pace_amd.util.open_restart -- one staging buffer, one host-to-device copy, one pace_state_unpack launch.  Halos and every
+        other field (ua, va, pe, peln, pk, pkz, ps, q_con, ...) stay zero, as in the reference."""
+        from ...util.restart import open_restart
+
+        new = cls.init_zeros(quantity_factory=quantity_factory)
+        open_restart(dirname=path, communicator=communicator, only_names=list(FORTRAN_RESTART_FIELDS.values()),
+                     to_state={name: getattr(new, field) for field, name in FORTRAN_RESTART_FIELDS.items()})
+        return new

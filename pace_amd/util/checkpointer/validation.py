@@ -7,8 +7,8 @@ six doubles per variable; the fields are never copied, clipped or transposed.
 
 Savepoint data: <savepoint_data_path>/<savepoint>.nc or .npz, holding per variable name an array [savepoint call, rank, ...].
 A .nc file is read through whichever of xarray, netCDF4 and h5py imports, else through scipy.io.netcdf_file, which reads
-NetCDF-3 classic only.  Where none of the three is installed only the NetCDF-3 and the npz routes can be, and are, tested.  A
-file is opened once and kept.  Of an npz file the slabs of this rank are kept in host memory once read -- 8 B per element per
+NetCDF-3 only (a NetCDF-4 / HDF5 file then raises a ValueError that names the file and the format).  Where none of the three is
+installed only the NetCDF-3 and the npz routes can be, and are, tested.  A file is opened once and kept.  Of an npz file the slabs of this rank are kept in host memory once read -- 8 B per element per
 savepoint, call and variable, a third of a calibration's figure (thresholds.py) -- and the .nc routes read a slab per call.
 """
 import collections
@@ -73,6 +73,17 @@ class _VariablesFile:
     def slab(self, name, call, rank):
         return np.asarray(self._values(self._variables[name], call, rank))
 
+    def names(self):
+        return list(self._variables.keys())
+
+    def record(self, name, index=0):
+        """Entry `index` of the variable's first axis (a restart file's one Time level) as a host array in the file's own type and
+        byte order (pace_amd.util.open_restart)."""
+        return np.asarray(np.ma.filled(self._variables[name][index], np.nan))
+
+
+_HDF5_SIGNATURE = b"\x89HDF\r\n\x1a\n"
+
 
 def _open_nc(path):
     try:
@@ -94,6 +105,10 @@ def _open_nc(path):
             return _VariablesFile(path, h5py.File(path, "r"), lambda v, c, r: v[c, r])
     except ImportError:
         pass
+    with open(path, "rb") as f:
+        if f.read(len(_HDF5_SIGNATURE)) == _HDF5_SIGNATURE:
+            raise ValueError(f"{path} is a NetCDF-4 / HDF5 file: reading it needs one of xarray, netCDF4 and h5py, and none of them "
+                             "is installed (scipy.io.netcdf_file reads NetCDF-3 only)")
     import scipy.io
 
     return _VariablesFile(path, scipy.io.netcdf_file(path, "r", mmap=False).variables, lambda v, c, r: v[c, r])

@@ -90,6 +90,27 @@ class GridData:
         gd._tile = metric_terms._tile
         return gd
 
+    def set_vertical_grid(self, ak, bk):
+        """The hybrid coefficients of a restart in place of the generated ones (grid/helper.py:152-236, VerticalGridData): ak,
+        bk and what derives from them -- ptop, p, p_ref, dp_ref -- by the reference's expressions.  Before c_struct() is first
+        built, so that nothing handed to the kernels predates it."""
+        if self._struct is not None:
+            raise RuntimeError("set_vertical_grid: the grid data are already in use (c_struct() has been built)")
+        ak, bk = np.array(ak, dtype=float).ravel(), np.array(bk, dtype=float).ravel()
+        nz = self._qf.sizer.nz
+        if len(ak) != nz + 1 or len(bk) != nz + 1:
+            raise ValueError(f"the restart's vertical grid has {len(ak)} interfaces (ak) and {len(bk)} (bk), "
+                             f"but nz = {nz} needs nz + 1 = {nz + 1}")
+        if bk[0] != 0:
+            raise ValueError("ptop is not well-defined when top-of-atmosphere bk != 0")
+        p_ref = 1e5
+        p_interface = ak + bk * p_ref
+        self.ak, self.bk = ak, bk
+        self.ptop = float(ak[0])
+        self.p_ref = np.asarray(p_ref, dtype=float)
+        self.p = (p_interface[1:] - p_interface[:-1]) / np.log(p_interface[1:] / p_interface[:-1])
+        self.dp_ref = ak[1:] - ak[:-1] + (bk[1:] - bk[:-1]) * p_ref
+
     def c_struct(self) -> _lib.Metrics:
         if self._struct is None:
             m = _lib.Metrics()
