@@ -11,10 +11,13 @@
 #else
 #include <hip/hip_runtime.h>
 #endif
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "../../include/pace_hip.h"
 
@@ -43,6 +46,38 @@ typedef pace_metrics_t Met;
 // storage type of fields, metrics and device K-arrays (include/pace_hip.h); arithmetic is double in both builds
 typedef pace_real_t real;
 #define REAL_SHIFT (sizeof(real) == 8 ? 3 : 2)  // log2 of the element size, for the byte-offset addressing of some kernels
+
+// Kernel arguments read in place.  A kernel whose argument list is a table of pointers larger than the scalar register file (102
+// SGPRs) gets all of it loaded in its prologue, spilled into lanes of vector registers and read back with v_readlane in front of
+// almost every memory access.  Such a kernel takes ONE trivially copyable struct by value -- it then begins at offset 0 of the
+// kernel-argument segment -- and reads it through a reference in the constant address space: a member is fetched by a scalar load
+// where it is used.  No offsets are computed by hand: the struct's layout is the only map.  The emulation reads the by-value object.
+//   __global__ void k(Args A_) { PACE_KERNARG(Args, A, A_); ... A.member ... }
+// Device functions that take such a reference are templates over the referenced type (`template <class ST> f(ST& S)`).
+#ifdef PACE_EMU
+#define PACE_KERNARG_T(T) const T
+#define PACE_KERNARG(T, name, byvalue) const T& name = (byvalue)
+#else
+#define PACE_KERNARG_T(T) const __attribute__((address_space(4))) T
+#define PACE_KERNARG(T, name, byvalue)                                                                                  \
+  static_assert(std::is_trivially_copyable<T>::value && alignof(T) <= 64 && sizeof(T) % 8 == 0 && sizeof(T) <= 4096, \
+                "a kernel-argument table: plain data, 8-byte units, within the argument segment");                     \
+  (void)(byvalue);                                                                                                      \
+  PACE_KERNARG_T(T)& name = *(PACE_KERNARG_T(T)*)__builtin_amdgcn_kernarg_segment_ptr()
+#endif
+// The same table through an empty asm: what a stage reads through the result is fetched in that stage -- the compiler can neither
+// merge it with another stage's fetch of the same member nor move it in front of the pin (it would otherwise gather every
+// fetch at the top of the kernel, which is the prologue this scheme removes).
+template <class T>
+__device__ __forceinline__ T& pace_kernarg_pin(T& table) {
+#ifdef PACE_EMU
+  return table;
+#else
+  T* p = &table;
+  asm volatile("" : "+s"(p));
+  return *p;
+#endif
+}
 
 #define IDX2(g, i, j) ((long)(i) + (long)(j) * (g).sj)
 #define IDX3(g, i, j, k) ((long)(i) + (long)(j) * (g).sj + (long)(k) * (g).sk)

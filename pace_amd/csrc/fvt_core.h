@@ -264,7 +264,8 @@ using FvtPieces = FvtPiecesT<256>;
 // The stages of one tile.  EX / EY: the tile holds a west or east / south or north edge of the cubed-sphere tile (block-uniform).
 // NT = 256: every thread owns one y-run AND one x-run.  NT = 512 (the scalar-phase kernel): the first four waves own the x-runs,
 // the last four the y-runs -- half the persistent state per thread, twice the waves per SIMD.
-template <int MORD, bool EX, bool EY, int NT = 256, class LT = FvtLds>
+// MT: the metric planes' pointers as the kernel holds them (a plain object, or read in place: common.h PACE_KERNARG)
+template <int MORD, bool EX, bool EY, int NT = 256, class LT = FvtLds, class MT = const FvMet>
 struct FvtTile {
   static constexpr bool RES = std::is_same<LT, FvtLdsRes>::value;  // the damping's planes have places of their own
   static constexpr bool RC = EX && EY;  // the footprint reaches a corner of the halo: the corner copies apply
@@ -277,7 +278,7 @@ struct FvtTile {
   using Pieces = FvtPiecesT<NT>;
   LT& L;
   const Geo& g;
-  const FvMet& m;
+  MT& m;
   int tid, i0, j0, ilo, jlo, sj8, k;
   unsigned kb8;  // byte offset of the level
   bool west, east, south, north;
@@ -299,7 +300,7 @@ struct FvtTile {
   double *plane, *sdv, *sdu;
 
   // fx_cached (resident form, corner tiles): the corner cells' places are read from L.fxs (put there by publish_corner_places)
-  __device__ __forceinline__ FvtTile(LT& L_, const Geo& g_, const FvMet& m_, int bx, int by, int k_, int tid_, bool fx_cached = false)
+  __device__ __forceinline__ FvtTile(LT& L_, const Geo& g_, MT& m_, int bx, int by, int k_, int tid_, bool fx_cached = false)
       : L(L_), g(g_), m(m_) {
     tid = tid_;
     k = k_;
@@ -1053,32 +1054,49 @@ __device__ __forceinline__ void fvt_tile(FvtLds& L, const Geo& g, const FvMet& m
 // accumulated (flux_capacitor, :33-60), new delp (apply_pt_delp_fluxes, :148-201).  w: DelnFluxNoSG -> heat_diss (:63-103),
 // transport with the mass fluxes, flux-form update / new delp + dw (adjust_w_and_qcon, :331-350).  q_con, pt: transport with
 // the mass fluxes + mass-weighted damping, flux-form update / new delp.  All outputs to buffers of their own.
+// One pass's share of the table: input (never written), output, damping factor / order columns (device, dsw_prepare) and the
+// column's highest order -- one 32-byte-aligned record, so that a pass fetches it with one wide scalar load
+struct alignas(32) FvtPass {
+  const real* q;
+  real* qout;  // (the winds' pass has none)
+  const real* fac;
+  const real* nord;
+  int nmax;
+  int pad_[7];
+};
+static_assert(sizeof(FvtPass) == 64, "two records per 128 bytes");
+// (grouped by the stage that reads them: the kernel fetches a member where it uses it -- common.h PACE_KERNARG)
 struct FvtScalars {
-  // in the order delp, w, q_con, pt (and, with the winds, the relative vorticity): input (never written), output, damping factor /
-  // order columns (device, dsw_prepare)
-  const real* q[5];
-  real* qout[4];
-  const real* fac[5];
-  const real* nord[5];
-  int nmax[5];
+  FvtPass pass[5];  // in the order delp, w, q_con, pt (and, with the winds, the relative vorticity)
+  // ---- the prologue (Courant numbers, area fluxes), delp's pass (the accumulated mass fluxes) and w's (one workspace field, the heating)
   const real *crx, *cry, *xfx, *yfx;
-  real *mfx, *mfy;  // accumulated mass fluxes
-  real *dw;         // one workspace field
-  real *heat_s, *diss_est;
-  const real *damp_w, *ke_bg;
+  real *mfx, *mfy;
+  const real* damp_w;
   double dt;
+  real *dw, *heat_s, *diss_est;
+  const real* ke_bg;
   // ---- the winds (512-thread form only; winds != 0): the vorticity transport, u / v from it and the kinetic energy, the
   // dissipative heating and the final winds as a fifth pass of the tile (d_sw.py:406-477,493-608) ----
-  int winds, do_skeb, copy_wind_halo;
-  int ke_plus_vort;          // ke is the plain kinetic energy: ke + vort_b (the divergence damping's increment) is formed here
-  double d_con;
   const real *u, *v;         // the winds before d_sw (read at the tile's faces only)
   real *u_out, *v_out;       // the winds after it: buffers of their own (a tile reads the old wind on the face its neighbour writes)
   const real *ke, *vort_b;   // kinetic energy (+ divergence damping) and damped vorticity at the B-grid points
   real* heat_source;         // += the dissipative heating
   const real *damp_vt, *d_con_k;
   const real *fC, *rdx, *rdy, *rsin2, *cosa_s;  // metric fields FvMet does not carry
+  double d_con;
+  int winds, do_skeb, copy_wind_halo;
+  int ke_plus_vort;          // ke is the plain kinetic energy: ke + vort_b (the divergence damping's increment) is formed here
 };
+// The one argument of k_fvt_scalars (common.h PACE_KERNARG): 60 pointers and the scalars are more than the scalar register file
+// holds, so the resident form reads S where it uses it instead of carrying the table through the kernel in spilled registers.
+struct FvtScalarsArgs {
+  Geo g;
+  FvMet m;
+  FvtScalars S;
+};
+static_assert(std::is_trivially_copyable<FvtScalarsArgs>::value && alignof(FvtScalarsArgs) == 32 && offsetof(FvtScalarsArgs, g) == 0 &&
+                  offsetof(FvtScalarsArgs, S) % 32 == 0 && sizeof(FvtScalarsArgs) == offsetof(FvtScalarsArgs, S) + sizeof(FvtScalars),
+              "one kernel argument at offset 0 of the argument segment, the passes' records on 32-byte boundaries");
 
 
 template <int MORD, bool EX, bool EY>
@@ -1109,11 +1127,11 @@ __device__ __forceinline__ void fvt_scalars_tile(FvtLdsScalars& LS, const Geo& g
 #pragma unroll
   for (int s = 0; s < 4; ++s) {  // delp, w, q_con, pt
     FVT_STAMP(4 * s);
-    const real* const q = S.q[s] + kb;
-    real* const qout = S.qout[s] + kb;
+    const real* const q = S.pass[s].q + kb;
+    real* const qout = S.pass[s].qout + kb;
     const bool is_delp = s == 0, is_w = s == 1;
     const bool mass_weighted = s >= 2;  // DelnFlux with mass (q_con, pt); delp: plain DelnFlux; w: DelnFluxNoSG -> heat_diss
-    const double damp = S.fac[s][k];
+    const double damp = S.pass[s].fac[k];
     T.load_footprint(q, qout);
     T.stage_damping_metrics();
     __syncthreads();
@@ -1126,7 +1144,7 @@ __device__ __forceinline__ void fvt_scalars_tile(FvtLdsScalars& LS, const Geo& g
     }
     {
       double dvx[NF], dvy[NF];
-      const auto D = T.damp(mass_weighted ? 1.0 : damp, S.nord[s][k] > 0.0, S.nmax[s]);
+      const auto D = T.damp(mass_weighted ? 1.0 : damp, S.pass[s].nord[k] > 0.0, S.pass[s].nmax);
       if (is_w) {
         T.heat_diss(D, S.dw + kb, S.heat_s + kb, S.diss_est + kb, w_on, S.ke_bg[k] * fabs(S.dt));
       } else {
@@ -1268,8 +1286,8 @@ __device__ __forceinline__ void fvt_scalars_tile_split(FvtLdsScalars& LS, const 
   {
     Tile T(L, g, m, bx, by, k, tid);
 #pragma unroll
-    for (int s = 0; s < 4; ++s) T.fetch_footprint(S.q[s] + kb, fp[s]);
-    if (S.winds) T.fetch_footprint(S.q[4] + kb, fp[4]);
+    for (int s = 0; s < 4; ++s) T.fetch_footprint(S.pass[s].q + kb, fp[s]);
+    if (S.winds) T.fetch_footprint(S.pass[4].q + kb, fp[4]);
     const unsigned roff = xrole ? T.xoff : T.yoff;
   if (xrole) {
 #pragma unroll
@@ -1291,11 +1309,11 @@ __device__ __forceinline__ void fvt_scalars_tile_split(FvtLdsScalars& LS, const 
     constexpr int s = decltype(s_)::value;
     constexpr bool is_delp = s == 0, is_w = s == 1, is_vort = s == 4;
     FVT_STAMP(4 * s);
-    const real* const q = S.q[s] + kb;
-    real* const qout = is_vort ? nullptr : S.qout[is_vort ? 0 : s] + kb;
+    const real* const q = S.pass[s].q + kb;
+    real* const qout = is_vort ? nullptr : S.pass[is_vort ? 0 : s].qout + kb;
     // DelnFlux with mass (q_con, pt); delp: plain DelnFlux; w: DelnFluxNoSG -> heat_diss; vorticity: DelnFluxNoSG -> the winds
     const bool mass_weighted = s == 2 || s == 3;
-    const double damp = S.fac[s][k];
+    const double damp = S.pass[s].fac[k];
     // the thread's places, derived again for every scalar: only the operands above live through the whole kernel
     Tile T(L, g, m, bx, by, k, FVT_LAUNDER(tid));
     // the thread's run: its five faces in memory (first face, step), whether it takes part in the inner / the outer sweep
@@ -1339,7 +1357,7 @@ __device__ __forceinline__ void fvt_scalars_tile_split(FvtLdsScalars& LS, const 
       }
     }
     {
-      const auto D = T.damp(mass_weighted ? 1.0 : damp, S.nord[s][k] > 0.0, S.nmax[s]);
+      const auto D = T.damp(mass_weighted ? 1.0 : damp, S.pass[s].nord[k] > 0.0, S.pass[s].nmax);
       if (is_w) {
         // (w has no face values: priv is free for dw; with the winds its heating term stays in the LDS as well)
         T.heat_diss(D, S.dw + kb, S.heat_s + kb, S.diss_est + kb, w_on, S.ke_bg[k] * fabs(S.dt), priv, S.winds ? LS.heat : nullptr);
@@ -1658,8 +1676,12 @@ struct FvtLdsScalarsRes {
 };
 static_assert(2 * sizeof(FvtLdsScalarsRes) <= 160 * 1024, "two workgroups per CU");
 
-template <int MORD, bool EX, bool EY>
-__device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const Geo& g, const FvMet& m, const FvtScalars& S, int bx, int by, int k) {
+// ST, MT: FvtScalars and FvMet as the kernel reads them -- in the kernel-argument segment (common.h PACE_KERNARG), or plain const
+// objects.  m serves the prologue (del6_u, del6_v, dxa, dya: used once, fetched there); mv is the by-value copy, of which the passes
+// keep area, rarea, dx and dy in registers.  (All of FvMet in place costs nothing in spills but makes the compiler duplicate a few
+// blocks of the edge tiles' arithmetic; all of it by value leaves two spilled SGPRs in two of the four builds.)
+template <int MORD, bool EX, bool EY, class MT, class ST>
+__device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const Geo& g, const FvMet& mv, MT& m, ST& S, int bx, int by, int k) {
   constexpr int NT = 512;
   using Tile = FvtTile<MORD, EX, EY, NT, FvtLdsRes>;
   constexpr int NCU = Tile::NCU, DRC = Tile::DRC;
@@ -1679,15 +1701,15 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
 #pragma unroll
   for (int t = 0; t < NCU; ++t) nm[t] = 1.0, heat_r[t] = 0.0;
   {
-    Tile T(L, g, m, bx, by, k, tid);
+    FvtTile<MORD, EX, EY, NT, FvtLdsRes, MT> T(L, g, m, bx, by, k, tid);
     if (FVT_RA_REGS) {
       T.load_damping_rarea();
 #pragma unroll
       for (int t = 0; t < DRC; ++t) ra_keep[t] = T.dra[t];
     }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) T.fetch_footprint(S.q[s] + kb, fp[s]);
-    if (S.winds) T.fetch_footprint(S.q[4] + kb, fp[4]);
+    for (int s = 0; s < 4; ++s) T.fetch_footprint(S.pass[s].q + kb, fp[s]);
+    if (S.winds) T.fetch_footprint(S.pass[4].q + kb, fp[4]);
     T.stage_damping_planes();  // once per tile
     T.stage_spacings();
     T.publish_corner_places();
@@ -1712,15 +1734,15 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
     constexpr int s = decltype(s_)::value;
     constexpr bool is_delp = s == 0, is_w = s == 1, is_vort = s == 4;
     FVT_STAMP(4 * s);
-    const real* const q = S.q[s] + kb;
-    real* const qout = is_vort ? nullptr : S.qout[is_vort ? 0 : s] + kb;
+    const real* const q = S.pass[s].q + kb;
+    real* const qout = is_vort ? nullptr : S.pass[is_vort ? 0 : s].qout + kb;
     // DelnFlux with mass (q_con, pt); delp: plain DelnFlux; w: DelnFluxNoSG -> heat_diss; vorticity: DelnFluxNoSG -> the winds
     const bool mass_weighted = s == 2 || s == 3;
-    const double damp = S.fac[s][k];
+    const double damp = S.pass[s].fac[k];
     const double d0 = mass_weighted ? 1.0 : damp;
-    const int iters = (S.nord[s][k] > 0.0) ? S.nmax[s] : 0;  // passes of the damping before its fluxes: 0, 1 or 2 (block-uniform)
+    const int iters = (S.pass[s].nord[k] > 0.0) ? S.pass[s].nmax : 0;  // passes of the damping before its fluxes: 0, 1 or 2 (block-uniform)
     // the thread's places, derived again for every scalar: only the operands above live through the whole kernel
-    Tile T(L, g, m, bx, by, k, FVT_LAUNDER(tid), s > 0);  // (pass 0's barrier has published the corner cells' places)
+    Tile T(L, g, mv, bx, by, k, FVT_LAUNDER(tid), s > 0);  // (pass 0's barrier has published the corner cells' places)
     const unsigned roff = xrole ? T.xoff : T.yoff;
     const bool run_outer = xrole ? T.x_outer : T.y_outer;
     const bool lane_lo = xrole ? (T.west && T.xg == 0) : (T.south && T.yg == 0);
@@ -1836,7 +1858,7 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
         fvt_run<MORD, EX>(Q, c, lane_lo, lane_hi, spacing(), si);
         FVT_FENCE();
 #pragma unroll
-        for (int t = 0; t < C; ++t) ar[t] = LDG(m.area, roff + (unsigned)(t * RB));
+        for (int t = 0; t < C; ++t) ar[t] = LDG(mv.area, roff + (unsigned)(t * RB));
         if (T.x_outer) {
 #pragma unroll
           for (int f = 0; f < C; ++f) slot[f * XS] = si[f];
@@ -1855,7 +1877,7 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
         fvt_run<MORD, EY>(Q, c, lane_lo, lane_hi, spacing(), si);
         FVT_FENCE();
 #pragma unroll
-        for (int t = 0; t < C; ++t) ar[t] = LDG(m.area, roff + (unsigned)(t * sj8));
+        for (int t = 0; t < C; ++t) ar[t] = LDG(mv.area, roff + (unsigned)(t * sj8));
         if (T.y_outer) {
 #pragma unroll
           for (int f = 0; f < C; ++f) slot[f * YS] = si[f];
@@ -1891,10 +1913,10 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
     auto load_spacings = [&]() {
       if (xrole) {
 #pragma unroll
-        for (int f = 0; f < NF; ++f) dsp[f] = LDG(m.dy, roff + (unsigned)(f * RB)), rdsp[f] = LDG(S.rdy, roff + (unsigned)(f * RB));
+        for (int f = 0; f < NF; ++f) dsp[f] = LDG(mv.dy, roff + (unsigned)(f * RB)), rdsp[f] = LDG(S.rdy, roff + (unsigned)(f * RB));
       } else {
 #pragma unroll
-        for (int f = 0; f < NF; ++f) dsp[f] = LDG(m.dx, roff + (unsigned)(f * sj8)), rdsp[f] = LDG(S.rdx, roff + (unsigned)(f * sj8));
+        for (int f = 0; f < NF; ++f) dsp[f] = LDG(mv.dx, roff + (unsigned)(f * sj8)), rdsp[f] = LDG(S.rdx, roff + (unsigned)(f * sj8));
       }
     };
     if (is_vort && run_outer) {
@@ -2063,7 +2085,7 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
     double ra[NCU];  // (loaded before the barrier, like the winds' cell stage)
     T.cell_places(jj, ii, c2);
 #pragma unroll
-    for (int t = 0; t < NCU; ++t) ra[t] = LDG(m.rarea, c2[t]);
+    for (int t = 0; t < NCU; ++t) ra[t] = LDG(mv.rarea, c2[t]);
     __syncthreads();
 
     // ---- interval 5: the cell update (apply_fluxes / apply_pt_delp_fluxes / adjust_w_and_qcon, d_sw.py:122-201,331-350)

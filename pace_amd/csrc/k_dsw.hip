@@ -240,7 +240,9 @@ k_copy_wind_halo(Geo g, const real* __restrict__ u, const real* __restrict__ v, 
 // ------------------------------------------------------------------------------------------------
 // DivergenceDamping, sponge levels (nord_col == 0): divergence_damping.py:30-158
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double dd_u_contra_dyc(const Geo& g, const Met& m, const real* u, const real* va,
+// (MT: the metrics as the kernel holds them -- a plain object, or read in place from the argument segment: common.h PACE_KERNARG)
+template <class MT>
+__device__ __forceinline__ double dd_u_contra_dyc(const Geo& g, MT& m, const real* u, const real* va,
                                                   const real* vc, long c, long c2, int j) {
   double uc_;
   if (j == g.js || j == g.je + 1) {
@@ -252,7 +254,8 @@ __device__ __forceinline__ double dd_u_contra_dyc(const Geo& g, const Met& m, co
   return uc_ * m.dyc[c2];
 }
 
-__device__ __forceinline__ double dd_v_contra_dxc(const Geo& g, const Met& m, const real* v, const real* ua,
+template <class MT>
+__device__ __forceinline__ double dd_v_contra_dxc(const Geo& g, MT& m, const real* v, const real* ua,
                                                   const real* uc, long c, long c2, int i) {
   double vc_;
   if (i == g.is || i == g.ie + 1) {
@@ -265,7 +268,8 @@ __device__ __forceinline__ double dd_v_contra_dxc(const Geo& g, const Met& m, co
 }
 
 // one B-grid point of the sponge levels: delpc, the damped vorticity and ke += it (divergence_damping.py:30-158)
-__device__ __forceinline__ void divdamp_low_point(const Geo& g, const Met& m, const real* __restrict__ u, const real* __restrict__ v,
+template <class MT>
+__device__ __forceinline__ void divdamp_low_point(const Geo& g, MT& m, const real* __restrict__ u, const real* __restrict__ v,
                                                   const real* __restrict__ ua, const real* __restrict__ va, const real* __restrict__ uc,
                                                   const real* __restrict__ vc, real* __restrict__ delpc, real* __restrict__ vort_b,
                                                   real* __restrict__ ke, double d2, double dddmp, double dt, int i, int j, int k) {
@@ -329,10 +333,10 @@ struct PlaneInLds {
   __device__ __forceinline__ double operator()(int i, int j) const { return s[(j - jlo) * pitch + (i - ilo)]; }
 };
 
-template <class Plane>
+template <class Plane, class MT = const Met>
 struct DivIterT {
   const Geo& g;
-  const Met& m;
+  MT& m;
   Plane d;  // divergence of the previous iterate
   bool fill;
   __device__ __forceinline__ double dx_(int i, int j) const {  // divg with corners filled in x
@@ -397,21 +401,27 @@ __device__ __forceinline__ double a2b_interior_point(const Plane& Q, int i, int 
 // (the edge forms are chains of a dozen dependent reads: from memory, one round trip each)
 struct A2BInMemory {
   const real* q;  // level base applied
-  __device__ __forceinline__ double Q(const Geo& g, const Met&, int i, int j) const { return q[IDX2(g, i, j)]; }
-  __device__ __forceinline__ double DXA(const Geo& g, const Met& m, int i, int j) const { return m.dxa[IDX2(g, i, j)]; }
-  __device__ __forceinline__ double DYA(const Geo& g, const Met& m, int i, int j) const { return m.dya[IDX2(g, i, j)]; }
+  template <class MT>
+  __device__ __forceinline__ double Q(const Geo& g, MT&, int i, int j) const { return q[IDX2(g, i, j)]; }
+  template <class MT>
+  __device__ __forceinline__ double DXA(const Geo& g, MT& m, int i, int j) const { return m.dxa[IDX2(g, i, j)]; }
+  template <class MT>
+  __device__ __forceinline__ double DYA(const Geo& g, MT& m, int i, int j) const { return m.dya[IDX2(g, i, j)]; }
 };
 struct A2BInLds {
   const double *q, *xa, *ya;
   int ilo, jlo, pitch;
-  __device__ __forceinline__ double Q(const Geo&, const Met&, int i, int j) const { return q[(j - jlo) * pitch + (i - ilo)]; }
-  __device__ __forceinline__ double DXA(const Geo&, const Met&, int i, int j) const { return xa[(j - jlo) * pitch + (i - ilo)]; }
-  __device__ __forceinline__ double DYA(const Geo&, const Met&, int i, int j) const { return ya[(j - jlo) * pitch + (i - ilo)]; }
+  template <class MT>
+  __device__ __forceinline__ double Q(const Geo&, MT&, int i, int j) const { return q[(j - jlo) * pitch + (i - ilo)]; }
+  template <class MT>
+  __device__ __forceinline__ double DXA(const Geo&, MT&, int i, int j) const { return xa[(j - jlo) * pitch + (i - ilo)]; }
+  template <class MT>
+  __device__ __forceinline__ double DYA(const Geo&, MT&, int i, int j) const { return ya[(j - jlo) * pitch + (i - ilo)]; }
 };
-template <class Src>
+template <class Src, class MT = const Met>
 struct A2BT {
   const Geo& g;
-  const Met& m;
+  MT& m;
   Src src;
   __device__ __forceinline__ double Q(int i, int j) const { return src.Q(g, m, i, j); }
   __device__ __forceinline__ double DXA(int i, int j) const { return src.DXA(g, m, i, j); }
@@ -588,8 +598,8 @@ struct DdSponge {
   int nch_row, len_row, nch_col, len_col;  // chunks per edge and their length, rows (south / north) and columns (west / east)
 };
 
-template <class Plane>
-__device__ __forceinline__ void divdamp_point(const Geo& g, const Met& m, const Plane& src, int i, int j, bool fill, double& d,
+template <class Plane, class MT>
+__device__ __forceinline__ void divdamp_point(const Geo& g, MT& m, const Plane& src, int i, int j, bool fill, double& d,
                                               double& uc_here, double& vc_here) {
   const long c2 = IDX2(g, i, j);
   if (i > g.is && i <= g.ie) {
@@ -604,7 +614,7 @@ __device__ __forceinline__ void divdamp_point(const Geo& g, const Met& m, const 
     uc_here = uc0;
     vc_here = vc0;
   } else {
-    DivIterT<Plane> it{g, m, src, fill};
+    DivIterT<Plane, MT> it{g, m, src, fill};
     const double ucm = it.uc(i, j - 1), uc0 = it.uc(i, j), vcm = it.vc(i - 1, j), vc0 = it.vc(i, j);
     d = ucm - uc0 + vcm - vc0;  // redo_divg_d :212-240
     const bool ic = (i == g.is || i == g.ie + 1);
@@ -627,12 +637,15 @@ __device__ __forceinline__ void divdamp_point(const Geo& g, const Met& m, const 
 // MODE 0: a tile -- the tail at the own points where a2b_ord4 is the 16-point mean (the rest of them belong to the strips);
 // 2: a strip of the frame -- the tail at every own point, a2b_ord4's general forms on LDS planes; 1: the same from memory (a
 // tile too small to have an interior: its footprint leaves no room for the planes of the cell widths).
-template <int TI, int TJ, int MODE>
-__device__ __forceinline__ void
-divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, const Geo& g, const Met& m,
-             const real* __restrict__ wk, const real* din, real* divg_d, real* __restrict__ vort_b,
-             real* __restrict__ ke, real* __restrict__ uc_out, real* __restrict__ vc_out, const real* __restrict__ d2_bg, double dddmp,
-             double dd8, double absdt, int nord, bool full) {
+// AT: the kernel's argument table (DdArgs below), read in place: the metrics' planes and the fields are fetched in the load phase, the
+// outputs' pointers and the tail's coefficients where the tail begins -- nothing of the table lives through the passes.
+template <int TI, int TJ, int MODE, class AT>
+__device__ __forceinline__ void divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, const Geo& g, AT& A_) {
+  using MT = typename std::remove_reference<decltype((A_.m))>::type;
+  const int nord = A_.nord;
+  AT& A0 = pace_kernarg_pin(A_);  // the load phase's fetches
+  const real* const wk = A0.wk;
+  const real* const din = A0.din;
   // The divergence before the passes: `din` at the tile's own B-grid points [is, ie+1]^2, divg_d in the halo.  full (the
   // reference's contract): din = delpc, which the caller has set to the divergence there (copy_computeplus), and divg_d is
   // WRITTEN at the tile's points only -- no workgroup reads what another one writes.  full == false
@@ -653,18 +666,18 @@ divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, c
     const bool ok = e < W * H && gi < g.ni && gj < g.nj;
     const long c2 = ok ? IDX2(g, gi, gj) : 0;
     const bool own_pt = gi >= g.is && gi <= g.ie + 1 && gj >= g.js && gj <= g.je + 1;
-    dreg[t] = (own_pt ? din : (const real*)divg_d)[kb + c2];
+    dreg[t] = (own_pt ? din : (const real*)A0.divg_d)[kb + c2];
     if (!ok) dreg[t] = 0.0;
     // (the widest pass reaches two points beyond the own points: nord <= 3)
     const bool pl = ok && gi >= i0 - 2 && gi <= i1 + 2 && gj >= j0 - 2 && gj <= j1 + 2 &&
                     ((gi > g.is && gi <= g.ie) || (gj > g.js && gj <= g.je));
     plain |= (pl ? 1u : 0u) << t;
     const long cm = pl ? c2 : IDX2(g, g.is + 1, g.js + 1);
-    gvm[t] = m.divg_v[cm - sj];
-    gv0[t] = m.divg_v[cm];
-    gum[t] = m.divg_u[cm - 1];
-    gu0[t] = m.divg_u[cm];
-    ra[t] = m.rarea_c[cm];
+    gvm[t] = A0.m.divg_v[cm - sj];
+    gv0[t] = A0.m.divg_v[cm];
+    gum[t] = A0.m.divg_u[cm - 1];
+    gu0[t] = A0.m.divg_u[cm];
+    ra[t] = A0.m.rarea_c[cm];
   }
   {
     // the relative vorticity under the tile to a plane of its own, a strip's cell widths behind its planes of the passes
@@ -676,7 +689,7 @@ divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, c
       const bool ok = e < W * H && ilo + ii < g.ni && jlo + jj < g.nj;
       const long c2 = ok ? IDX2(g, ilo + ii, jlo + jj) : 0;
       wreg[t] = wk[kb + c2];
-      if (MODE == 2) xreg[t] = m.dxa[c2], yreg[t] = m.dya[c2];
+      if (MODE == 2) xreg[t] = A0.m.dxa[c2], yreg[t] = A0.m.dya[c2];
     }
 #pragma unroll
     for (int t = 0; t < NE; ++t) {
@@ -721,6 +734,7 @@ divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, c
     const int ncol = ncl + ncr, total = ncol * (nrb + nrt);
     if (total > 0) {  // block-uniform
       const PlaneInLds plane{src, ilo, jlo, W};
+      MT& m = pace_kernarg_pin(A_).m;  // (a handful of points of the corner tiles: their fetches stay in here)
       for (int p = tid; p < total; p += DD_NT) {
         const int r = p / ncol, cx = p - r * ncol;
         const int gi = cx < ncl ? ia + cx : cr0 + (cx - ncl), gj = r < nrb ? ja + r : rt0 + (r - nrb);
@@ -733,7 +747,16 @@ divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, c
     cur ^= 1;
   }
   DD_STAMP(2);
-  const double d2 = d2_bg[kk];
+  AT& A = pace_kernarg_pin(A_);  // the tail's fetches
+  MT& m = A.m;
+  const bool full = A.full != 0;
+  real* const divg_d = A.divg_d;
+  real* const vort_b = A.vort_b;
+  real* const ke = A.ke;
+  real* const uc_out = A.uc_out;
+  real* const vc_out = A.vc_out;
+  const double dddmp = A.dddmp, dd8 = A.dd8, absdt = A.absdt;
+  const double d2 = A.d2_bg[kk];
   const double* src = sbuf[cur];
   const double* swk = sbuf[2];
 #pragma unroll
@@ -771,10 +794,10 @@ divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, c
       if (MODE == 0) {
         qb = a2b_interior_point(PlaneInLds{swk, ilo, jlo, W}, i, j);
       } else if (MODE == 2) {
-        A2BT<A2BInLds> a{g, m, A2BInLds{swk, sbuf[0] + W * H, sbuf[1] + W * H, ilo, jlo, W}};
+        A2BT<A2BInLds, MT> a{g, m, A2BInLds{swk, sbuf[0] + W * H, sbuf[1] + W * H, ilo, jlo, W}};
         qb = a.point(i, j);
       } else {
-        A2B a{g, m, {wk + kb}};
+        A2BT<A2BInMemory, MT> a{g, m, {wk + kb}};
         qb = a.point(i, j);
       }
       vb = absdt * sqrt(dpc * dpc + qb * qb);
@@ -788,14 +811,29 @@ divdamp_tile(double (*sbuf)[DD_PLANE], int i0, int i1, int j0, int j1, int kk, c
   DD_STAMP(3);
 }
 
-__global__ void __launch_bounds__(DD_NT) DD_ATTR
-k_divdamp_fused(Geo g, Met m, const real* __restrict__ wk, const real* din, real* divg_d,
-                real* __restrict__ vort_b, real* __restrict__ ke, real* __restrict__ uc_out, real* __restrict__ vc_out,
-                const real* __restrict__ d2_bg, double dddmp, double dd8, double absdt, int k0, int nord, int ntx, int ntiles, int full_,
-                DdSponge sp) {
+// The one argument of k_divdamp_fused (common.h PACE_KERNARG): the 43 pointers of the metrics, nine fields and the sponge's seven are
+// twice the scalar register file; read in place, a pointer is fetched where a tile's load phase (or a point function) uses it.
+struct DdArgs {
+  Geo g;
+  Met m;
+  const real *wk, *din;
+  real *divg_d, *vort_b, *ke, *uc_out, *vc_out;
+  const real* d2_bg;
+  double dddmp, dd8, absdt;
+  int k0, nord, ntx, ntiles, full, pad_;
+  DdSponge sp;
+};
+static_assert(std::is_trivially_copyable<DdArgs>::value && alignof(DdArgs) == 8 && offsetof(DdArgs, g) == 0 &&
+                  sizeof(DdArgs) == sizeof(Geo) + sizeof(Met) + 8 * sizeof(void*) + 3 * sizeof(double) + 6 * sizeof(int) + sizeof(DdSponge),
+              "one kernel argument at offset 0 of the argument segment, no padding between its parts");
+
+__global__ void __launch_bounds__(DD_NT) DD_ATTR k_divdamp_fused(DdArgs A_) {
   __shared__ double sbuf[3][DD_PLANE];  // two planes of the passes, one of the relative vorticity
+  PACE_KERNARG(DdArgs, A, A_);
+  const Geo& g = A_.g;  // (twelve registers, used everywhere)
+  auto& m = A.m;
+  auto& sp = A.sp;
   int b = (int)blockIdx.x;
-  const bool full = full_ != 0;
   DD_STAMP(0);
   if (b < sp.nblocks) {
     // a sponge level: 256 B-grid points of it
@@ -803,8 +841,8 @@ k_divdamp_fused(Geo g, Met m, const real* __restrict__ wk, const real* din, real
     const int q = (b - kk * per) * DD_NT + (int)threadIdx.x;
     if (q < w * w) {
       const int jj = q / w;
-      divdamp_low_point(g, m, sp.u, sp.v, sp.ua, sp.va, sp.uc, sp.vc, sp.delpc, vort_b, ke, d2_bg[kk], dddmp, sp.dt, g.is + (q - jj * w),
-                        g.js + jj, kk);
+      divdamp_low_point(g, m, sp.u, sp.v, sp.ua, sp.va, sp.uc, sp.vc, sp.delpc, A.vort_b, A.ke, A.d2_bg[kk], A.dddmp, sp.dt,
+                        g.is + (q - jj * w), g.js + jj, kk);
     }
     DD_STAMP(7);
     return;
@@ -817,31 +855,28 @@ k_divdamp_fused(Geo g, Met m, const real* __restrict__ wk, const real* din, real
       const int side = id / sp.nch_row, ch = id - side * sp.nch_row;
       const int i0 = g.is + ch * sp.len_row, j0 = side == 0 ? g.js : g.je;
       const int i1 = i0 + sp.len_row - 1 < g.ie + 1 ? i0 + sp.len_row - 1 : g.ie + 1;
-      divdamp_tile<DD_STRIP, 2, 2>(sbuf, i0, i1, j0, j0 + 1, lev + k0, g, m, wk, din, divg_d, vort_b, ke, uc_out, vc_out, d2_bg, dddmp, dd8,
-                                      absdt, nord, full);
+      divdamp_tile<DD_STRIP, 2, 2>(sbuf, i0, i1, j0, j0 + 1, lev + A.k0, g, A);
     } else {  // west, east columns between them
       const int id2 = id - 2 * sp.nch_row;
       const int side = id2 / sp.nch_col, ch = id2 - side * sp.nch_col;
       const int j0 = g.js + 2 + ch * sp.len_col, i0 = side == 0 ? g.is : g.ie;
       const int j1 = j0 + sp.len_col - 1 < g.je - 1 ? j0 + sp.len_col - 1 : g.je - 1;
-      divdamp_tile<2, DD_STRIP, 2>(sbuf, i0, i0 + 1, j0, j1, lev + k0, g, m, wk, din, divg_d, vort_b, ke, uc_out, vc_out, d2_bg, dddmp, dd8,
-                                      absdt, nord, full);
+      divdamp_tile<2, DD_STRIP, 2>(sbuf, i0, i0 + 1, j0, j1, lev + A.k0, g, A);
     }
     DD_STAMP(7);
     return;
   }
   b -= sp.nstrips;
+  const int ntiles = A.ntiles, ntx = A.ntx;
   const int zblock = b / ntiles, tile = b - zblock * ntiles;
   const int by = tile / ntx, bx = tile - by * ntx;
   const int i0 = g.is + bx * DD_TI, j0 = g.js + by * DD_TJ;
   const int i1 = i0 + DD_TI - 1 < g.ie + 1 ? i0 + DD_TI - 1 : g.ie + 1;
   const int j1 = j0 + DD_TJ - 1 < g.je + 1 ? j0 + DD_TJ - 1 : g.je + 1;
   if (sp.nstrips > 0)
-    divdamp_tile<DD_TI, DD_TJ, 0>(sbuf, i0, i1, j0, j1, zblock + k0, g, m, wk, din, divg_d, vort_b, ke, uc_out, vc_out, d2_bg, dddmp, dd8,
-                                      absdt, nord, full);
+    divdamp_tile<DD_TI, DD_TJ, 0>(sbuf, i0, i1, j0, j1, zblock + A.k0, g, A);
   else  // a tile too small for a frame and an interior
-    divdamp_tile<DD_TI, DD_TJ, 1>(sbuf, i0, i1, j0, j1, zblock + k0, g, m, wk, din, divg_d, vort_b, ke, uc_out, vc_out, d2_bg, dddmp, dd8,
-                                     absdt, nord, full);
+    divdamp_tile<DD_TI, DD_TJ, 1>(sbuf, i0, i1, j0, j1, zblock + A.k0, g, A);
   DD_STAMP(7);
 }
 
@@ -1451,9 +1486,9 @@ int launch_divergence_damping(const Geo& g, const Met& m, const real* u, const r
     sp.len_col = (ncol + sp.nch_col - 1) / sp.nch_col;
     sp.nstrips = 2 * (sp.nch_row + sp.nch_col) * nhigh;
   }
-  hipLaunchKernelGGL(k_divdamp_fused, dim3((unsigned)(sp.nblocks + sp.nstrips + ntx * nty * nhigh)), dim3(DD_NT), 0, st, g, m,
-                     rel_vort_agrid, skip_dead ? divg_d : delpc, divg_d, vort_b, ke, uc, vc, d2_bg_dev, dddmp, dd8, fabs(dt), kstart,
-                     nonzero_nord, ntx, ntx * nty, skip_dead ? 0 : 1, sp);
+  const DdArgs A{g, m, rel_vort_agrid, skip_dead ? divg_d : delpc, divg_d, vort_b, ke, uc, vc, d2_bg_dev, dddmp, dd8, fabs(dt), kstart,
+                 nonzero_nord, ntx, ntx * nty, skip_dead ? 0 : 1, 0, sp};
+  hipLaunchKernelGGL(k_divdamp_fused, dim3((unsigned)(sp.nblocks + sp.nstrips + ntx * nty * nhigh)), dim3(DD_NT), 0, st, A);
   // the full contract: the halo of divg_d, uc, vc as the reference's in-place passes leave it
   if (!skip_dead && nonzero_nord > 0) {
     const bool mem = pace_env_on("PACE_DDH_MEM");  // (tests: the memory form on a small tile; read at every call)

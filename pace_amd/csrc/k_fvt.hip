@@ -52,20 +52,27 @@ __global__ void __launch_bounds__(256, FVT_WAVES) k_fvt(Geo g, FvMet m, const re
 #define FVT_RESIDENT 1  // the 512-thread form on the layout with the damping's planes resident (round 6; 0: round 5's, for A/B builds)
 #endif
 template <int MORD>
-__global__ void __launch_bounds__(FVT_SCALARS_NT) FVT_SCALARS_ATTR k_fvt_scalars(Geo g, FvMet m, FvtScalars S) {
+__global__ void __launch_bounds__(FVT_SCALARS_NT) FVT_SCALARS_ATTR k_fvt_scalars(FvtScalarsArgs A_) {
 #if FVT_SCALARS_NT == 512 && FVT_RESIDENT
   __shared__ FvtLdsScalarsRes L;
+  PACE_KERNARG(FvtScalarsArgs, A, A_);  // (the table is read where it is used: no SGPR spills)
+  const Geo& g = A_.g;  // (twelve registers, used everywhere)
+  auto& m = A.m;
+  auto& S = A.S;
 #else
   __shared__ FvtLdsScalars L;
+  const Geo& g = A_.g;
+  const FvMet& m = A_.m;
+  const FvtScalars& S = A_.S;
 #endif
   const FvTile wg = fv_tile_of_workgroup();
   const int gx = g.n / TI, gy = g.n / TJ;
   const bool ex = wg.bx == 0 || wg.bx == gx - 1, ey = wg.by == 0 || wg.by == gy - 1;
 #if FVT_SCALARS_NT == 512 && FVT_RESIDENT
-  if (ex && ey) fvt_scalars_tile_res<MORD, true, true>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else if (ex) fvt_scalars_tile_res<MORD, true, false>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else if (ey) fvt_scalars_tile_res<MORD, false, true>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else fvt_scalars_tile_res<MORD, false, false>(L, g, m, S, wg.bx, wg.by, wg.bz);
+  if (ex && ey) fvt_scalars_tile_res<MORD, true, true>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
+  else if (ex) fvt_scalars_tile_res<MORD, true, false>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
+  else if (ey) fvt_scalars_tile_res<MORD, false, true>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
+  else fvt_scalars_tile_res<MORD, false, false>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
 #elif FVT_SCALARS_NT == 512
   if (ex && ey) fvt_scalars_tile_split<MORD, true, true>(L, g, m, S, wg.bx, wg.by, wg.bz);
   else if (ex) fvt_scalars_tile_split<MORD, true, false>(L, g, m, S, wg.bx, wg.by, wg.bz);
@@ -156,11 +163,11 @@ int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const DswFields& f, real*
   FvtScalars S{};
   const auto column = [&](DswColumn slot) { return dsw_column(kc, g, slot); };
   // delp, w, q_con, pt
-  S.q[0] = f.delp, S.q[1] = f.w, S.q[2] = f.q_con, S.q[3] = f.pt;
-  S.qout[0] = outs[0], S.qout[1] = outs[2], S.qout[2] = outs[3], S.qout[3] = outs[1];
-  S.fac[0] = column(DSWC_FAC_VT), S.fac[1] = column(DSWC_FAC_W_C), S.fac[2] = column(DSWC_FAC_T), S.fac[3] = S.fac[0];
-  S.nord[0] = column(DSWC_NORD_V), S.nord[1] = column(DSWC_NORD_W), S.nord[2] = column(DSWC_NORD_T), S.nord[3] = S.nord[0];
-  S.nmax[0] = nmax_v, S.nmax[1] = nmax_w, S.nmax[2] = nmax_t, S.nmax[3] = nmax_v;
+  S.pass[0].q = f.delp, S.pass[1].q = f.w, S.pass[2].q = f.q_con, S.pass[3].q = f.pt;
+  S.pass[0].qout = outs[0], S.pass[1].qout = outs[2], S.pass[2].qout = outs[3], S.pass[3].qout = outs[1];
+  S.pass[0].fac = column(DSWC_FAC_VT), S.pass[1].fac = column(DSWC_FAC_W_C), S.pass[2].fac = column(DSWC_FAC_T), S.pass[3].fac = S.pass[0].fac;
+  S.pass[0].nord = column(DSWC_NORD_V), S.pass[1].nord = column(DSWC_NORD_W), S.pass[2].nord = column(DSWC_NORD_T), S.pass[3].nord = S.pass[0].nord;
+  S.pass[0].nmax = nmax_v, S.pass[1].nmax = nmax_w, S.pass[2].nmax = nmax_t, S.pass[3].nmax = nmax_v;
   S.crx = f.crx, S.cry = f.cry, S.xfx = f.xfx, S.yfx = f.yfx, S.mfx = f.mfx, S.mfy = f.mfy, S.dw = dw, S.heat_s = heat_s,
   S.diss_est = f.diss_est;
   S.damp_w = column(DSWC_DAMP_W), S.ke_bg = column(DSWC_KE_BG);
@@ -169,7 +176,7 @@ int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const DswFields& f, real*
     // the relative vorticity: DelnFluxNoSG with nord_v and (damp_vt * da_min_c) ^ (nord_v + 1) (d_sw.py:1187-1195)
     if (((uintptr_t)winds->rel_vort & 15) != 0 || winds->u_out == winds->u || winds->v_out == winds->v) return PACE_ERR_UNSUPPORTED;
     S.winds = 1;
-    S.q[4] = winds->rel_vort, S.fac[4] = column(DSWC_FAC_VT_C), S.nord[4] = S.nord[0], S.nmax[4] = nmax_v;
+    S.pass[4].q = winds->rel_vort, S.pass[4].fac = column(DSWC_FAC_VT_C), S.pass[4].nord = S.pass[0].nord, S.pass[4].nmax = nmax_v;
     S.u = winds->u, S.v = winds->v, S.u_out = winds->u_out, S.v_out = winds->v_out, S.ke = winds->ke, S.vort_b = winds->vort_b;
     S.heat_source = winds->heat_source, S.do_skeb = winds->do_skeb, S.d_con = winds->d_con, S.copy_wind_halo = winds->copy_halo;
     S.ke_plus_vort = winds->ke_plus_vort;
@@ -177,8 +184,9 @@ int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const DswFields& f, real*
     S.fC = m.fC_agrid, S.rdx = m.rdx, S.rdy = m.rdy, S.rsin2 = m.rsin2, S.cosa_s = m.cosa_s;
   }
   const dim3 grid(g.n / TI, g.n / TJ, g.nk);
-  if (hord == 5) hipLaunchKernelGGL(k_fvt_scalars<5>, grid, dim3(FVT_SCALARS_NT), 0, st, g, fv_met(m), S);
-  else hipLaunchKernelGGL(k_fvt_scalars<6>, grid, dim3(FVT_SCALARS_NT), 0, st, g, fv_met(m), S);
+  const FvtScalarsArgs A{g, fv_met(m), S};
+  if (hord == 5) hipLaunchKernelGGL(k_fvt_scalars<5>, grid, dim3(FVT_SCALARS_NT), 0, st, A);
+  else hipLaunchKernelGGL(k_fvt_scalars<6>, grid, dim3(FVT_SCALARS_NT), 0, st, A);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 #else
