@@ -41,18 +41,23 @@ __device__ __forceinline__ long zc_yfill(const Geo& g, int i, int j) {
 // updatedzc: interface winds by dp_ref-weighted averages (p_weighted_average_*, updatedzc.py:15-31), first-order
 // upwind advection of gz (xy_flux :34-52, update_dz_c :61-117) on compute +- 1, interface levels
 // ------------------------------------------------------------------------------------------------
+// (every operand is widened to double BEFORE the first operation: with float32 storage `dp[0] + dp[1]`, `f[c] - f[c + sk]` and
+// `dp[0] / ...` of two `real` values would be float operations, rounded to float)
 __device__ __forceinline__ double pavg(const real* __restrict__ f, long c, long sk, int k, int km,
                                        const real* __restrict__ dp) {
   if (k == 0) {
-    const double ratio = dp[0] / (dp[0] + dp[1]);
-    return f[c] + (f[c] - f[c + sk]) * ratio;
+    const double d0 = dp[0], d1 = dp[1], f0 = f[c], f1 = f[c + sk];
+    const double ratio = d0 / (d0 + d1);
+    return f0 + (f0 - f1) * ratio;
   }
   if (k == km) {
-    const double ratio = dp[km - 1] / (dp[km - 2] + dp[km - 1]);
-    return f[c - sk] + (f[c - sk] - f[c - 2 * sk]) * ratio;
+    const double d1 = dp[km - 1], d2 = dp[km - 2], f1 = f[c - sk], f2 = f[c - 2 * sk];
+    const double ratio = d1 / (d2 + d1);
+    return f1 + (f1 - f2) * ratio;
   }
-  const double int_ratio = 1.0 / (dp[k - 1] + dp[k]);
-  return (dp[k] * f[c - sk] + dp[k - 1] * f[c]) * int_ratio;
+  const double dm = dp[k - 1], d0 = dp[k], fm = f[c - sk], f0 = f[c];
+  const double int_ratio = 1.0 / (dm + d0);
+  return (d0 * fm + dm * f0) * int_ratio;
 }
 
 // A thread takes ZC_CH consecutive interfaces of its column: the winds of layer k are the "layer above" of interface k + 1 and
@@ -100,11 +105,12 @@ k_updatedzc_advect(Geo g, Met m, const real* __restrict__ dp_ref, const real* __
         un[q] = ut[c + q];
         vn[q] = vt[c + (long)q * g.sj];
       }
-      const double int_ratio = 1.0 / (dp_ref[k - 1] + dp_ref[k]);
+      const double dpm = dp_ref[k - 1], dp0 = dp_ref[k];  // (widened first: see pavg)
+      const double int_ratio = 1.0 / (dpm + dp0);
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        xfx[q] = (dp_ref[k] * up[q] + dp_ref[k - 1] * un[q]) * int_ratio;  // (pavg's interior expression)
-        yfx[q] = (dp_ref[k] * vp[q] + dp_ref[k - 1] * vn[q]) * int_ratio;
+        xfx[q] = (dp0 * up[q] + dpm * un[q]) * int_ratio;  // (pavg's interior expression)
+        yfx[q] = (dp0 * vp[q] + dpm * vn[q]) * int_ratio;
         up[q] = un[q];
         vp[q] = vn[q];
       }
@@ -328,7 +334,8 @@ k_apply_height_fluxes(Geo g, Met m, real* __restrict__ zh, const real* __restric
   const double area = m.area[IDX2(g, i, j)];
   const double area_after = (area + xfx[c] - xfx[c + 1]) + (area + yfx[c] - yfx[c + g.sj]) - area;
   const double adv = (zh[c] * area + fx[c] - fx[c + 1] + fy[c] - fy[c + g.sj]) / area_after;
-  zh[c] = adv + (fx2[c] - fx2[c + 1] + fy2[c] - fy2[c + g.sj]) / area;
+  const double fx2w = fx2[c], fx2e = fx2[c + 1], fy2s = fy2[c], fy2n = fy2[c + g.sj];  // (widened first: see pavg)
+  zh[c] = adv + (fx2w - fx2e + fy2s - fy2n) / area;
 }
 
 // column part of update_dz_d (updatedzd.py:56-67 after the flux update): ws from the bottom interface, then the heights kept
@@ -903,8 +910,10 @@ struct Del2 {
     const int ci = (i <= g.is) ? g.is : g.ie, cj = (j <= g.js) ? g.js : g.je;
     const int xo = (ci == g.is) ? g.is - 1 : g.ie + 1, yo = (cj == g.js) ? g.js - 1 : g.je + 1;
     const bool hit = (i == ci && j == cj) || (i == xo && j == cj) || (i == ci && j == yo);
-    if (hit && (i <= g.is || i >= g.ie) && (j <= g.js || j >= g.je))
-      return (q[IDX2(g, ci, cj)] + q[IDX2(g, xo, cj)] + q[IDX2(g, ci, yo)]) * (1.0 / 3.0);
+    if (hit && (i <= g.is || i >= g.ie) && (j <= g.js || j >= g.je)) {
+      const double q0 = q[IDX2(g, ci, cj)], q1 = q[IDX2(g, xo, cj)], q2 = q[IDX2(g, ci, yo)];  // (widened first: see pavg)
+      return (q0 + q1 + q2) * (1.0 / 3.0);
+    }
     return q[IDX2(g, i, j)];
   }
   __device__ __forceinline__ double qx(int i, int j, bool cc) const {

@@ -25,6 +25,35 @@ from oracle._np import Grid
 
 P_FAC, RF_CUTOFF, TAU, DELT_MAX, HORD_TM = 0.05, 3000.0, 10.0, 0.002, 6
 
+# ----------------------------------------------------------------------------------------------------------------------
+# float32 STORAGE (the _f32 libraries: fields, metrics and K-tables held as float, arithmetic in double).  The oracle stays
+# float64; with storage="f32" everything a kernel would LOAD is a float32 value (as float64), so that `before` is exactly what
+# ProductOps._load puts into float32 fields and `after` is float32(oracle(before)) -- tests/test_f32_operators.py.
+# ----------------------------------------------------------------------------------------------------------------------
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+def f32(a):
+    """float64 -> float32 -> float64, clipped to the largest finite float32 first (pk3's 1e40 fill becomes that value, as
+    pace_amd/fv3core/stencils/dyn_core.py:135 says); NaN stays NaN."""
+    return np.clip(np.asarray(a, dtype=np.float64), -F32_MAX, F32_MAX).astype(np.float32).astype(np.float64)
+
+
+def f32_dict(d):
+    """The float arrays of a dictionary rounded with f32; scalars (dt, ptop, da_min: passed to the kernels as double) untouched."""
+    return {k: (f32(v) if isinstance(v, np.ndarray) and v.dtype.kind == "f" else v) for k, v in d.items()}
+
+
+def f32_neighbours(a, rng):
+    """Every non-zero finite float32 value of `a` moved to its float32 neighbour, up or down at random (the fill value F32_MAX
+    stays): one rounding's worth of storage noise."""
+    a32 = np.asarray(a).astype(np.float32)
+    up = rng.integers(0, 2, a32.shape).astype(bool)
+    with np.errstate(over="ignore"):  # (the neighbour above F32_MAX: not taken)
+        moved = np.where(up, np.nextafter(a32, np.float32(np.inf)), np.nextafter(a32, np.float32(-np.inf)))
+    keep = (a32 == 0) | ~np.isfinite(a32) | (np.abs(a32) >= np.float32(F32_MAX))
+    return np.where(keep, a32, moved).astype(np.float64)
+
 
 def _win(n, lo=0, hi=0, di=0, dj=0):
     """(i, j) slices: the compute domain widened by lo cells below / hi above, + di / dj staggered points."""
@@ -47,14 +76,19 @@ def column(nz):
 
 
 class Chain:
-    def __init__(self, n, nz, metrics=None, state=None):
+    def __init__(self, n, nz, metrics=None, state=None, storage=None):
+        """storage=None: the float64 chain.  storage="f32": metrics (before Grid is built), column tables, the initial state and
+        the whole state at every operator boundary are float32 values (f32 above); the arithmetic stays float64."""
         from pace_amd import synthetic
 
-        self.n, self.nz = n, nz
+        assert storage in (None, "f32")
+        self.n, self.nz, self.storage = n, nz, storage
         self.metrics = metrics if metrics is not None else synthetic.tile_metrics(n, nz)
         s = state if state is not None else synthetic.acoustic_state(self.metrics, n, nz)
-        self.g = Grid(n, nz, self.metrics)
         self.col = column(nz)
+        if storage:
+            self.metrics, s, self.col = f32_dict(self.metrics), f32_dict(s), f32_dict(self.col)
+        self.g = Grid(n, nz, self.metrics)
         self.dt = float(s["dt"])
         self.ptop = float(self.metrics["ptop"])
         z3 = lambda: np.zeros(s["u"].shape)  # noqa: E731
@@ -67,39 +101,69 @@ class Chain:
         S["gz"] = s["zh"].copy()  # dyn_core.py:760-776: on the first substep zh := gz (heights, like the reference's gz here)
         S["pk3"] = np.full(s["u"].shape, 1.0e40)
         self.S = S
+        self._store()
         self.csw = cgrid_sw.CSWState(s["u"].shape)
         self.dsw = dgrid_sw.DSWState(s["u"].shape)
 
     def _snap(self):
         return {k: v.copy() for k, v in self.S.items()}
 
-    def cases(self, only=None):
+    def _store(self):
+        """An operator boundary: with float32 storage the whole state goes through `real` fields."""
+        if self.storage:
+            for v in self.S.values():
+                v[...] = f32(v)
+
+    def cases(self, only=None, inject=None):
         """Generator of OpCase in loop order.  The chain always advances through every operator (later ones need the
-        fields of the earlier ones); ``only`` just limits what is handed out."""
+        fields of the earlier ones); ``only`` just limits what is handed out.  ``inject(name)``, if given, returns the state
+        that replaces this chain's own before operator `name` (the noise pass of tests/test_f32_operators.py: a second chain
+        fed the perturbed `before` of the first).  With float32 storage every case carries `raw`: the oracle's checked
+        outputs BEFORE they are rounded for storage."""
         S, g, n, nz = self.S, self.g, self.n, self.nz
         dt, dt2, ptop = self.dt, 0.5 * self.dt, self.ptop
         K = nz + 1
         C0, C1 = _win(n), _win(n, 1, 1)
 
+        def take(name):
+            if inject is not None:
+                for k, v in inject(name).items():
+                    S[k][...] = v
+
         def emit(name, fn, checks):
             want = only is None or name in only
+            take(name)
             before = self._snap() if want else None
             fn()
+            raw = {c[0]: S[c[0]].copy() for c in checks} if want and self.storage else None
+            self._store()
             if want:
-                yield OpCase(name, before, self._snap(), checks)
+                case = OpCase(name, before, self._snap(), checks)
+                case.raw = raw
+                yield case
 
         # --- D2A2C_Vect on the initial winds (translate_d2a2c_vect.py:36-47); does not advance the chain ---
         if only is None or "d2a2c_vect" in only:
+            saved = self._snap() if inject is not None else None
+            take("d2a2c_vect")
             before = self._snap()
             T = {k: S[k].copy() for k in ("uc", "vc", "u", "v", "ua", "va", "utc", "vtc")}
             cgrid_sw.d2a2c_vect(g, cgrid_sw.D2A2CState(S["u"].shape), T["uc"], T["vc"], T["u"], T["v"], T["ua"], T["va"], T["utc"], T["vtc"])
             after = dict(before)
             after.update(T)
             W1 = _win(n, 1, 1)
-            yield OpCase("d2a2c_vect", before, after,
-                         [("uc", _win(n, 1, 1, 1, 0), nz, 2e-10, 1e-13), ("vc", _win(n, 1, 1, 0, 1), nz, 2e-10, 1e-13),
-                          ("ua", W1, nz, 2e-10, 1e-13), ("va", W1, nz, 2e-10, 1e-13),
-                          ("utc", _win(n, 1, 1, 1, 0), nz, 2e-10, 1e-13), ("vtc", _win(n, 1, 1, 0, 1), nz, 2e-10, 1e-13)])
+            case = OpCase("d2a2c_vect", before, after,
+                          [("uc", _win(n, 1, 1, 1, 0), nz, 2e-10, 1e-13), ("vc", _win(n, 1, 1, 0, 1), nz, 2e-10, 1e-13),
+                           ("ua", W1, nz, 2e-10, 1e-13), ("va", W1, nz, 2e-10, 1e-13),
+                           ("utc", _win(n, 1, 1, 1, 0), nz, 2e-10, 1e-13), ("vtc", _win(n, 1, 1, 0, 1), nz, 2e-10, 1e-13)])
+            case.raw = None
+            if self.storage:
+                case.raw = {c[0]: T[c[0]] for c in case.checks}
+                case.after = f32_dict(after)
+            if saved is not None:  # (this operator does not advance the chain: neither does what was injected for it)
+                for k, v in saved.items():
+                    S[k][...] = v
+            yield case
 
         def f_csw():
             cgrid_sw.c_sw(g, self.csw, S["delp"], S["pt"], S["u"], S["v"], S["w"], S["uc"], S["vc"], S["ua"], S["va"], S["ut"], S["vt"],
@@ -537,9 +601,34 @@ def loop_errors(ref, got, n, nz, detail=None, geometry="synthetic"):
 # ----------------------------------------------------------------------------------------------------------------------
 # The operators the reference also tests on their own (TranslateXPPM / YPPM / DivergenceDamping) as stand-alone classes
 # ----------------------------------------------------------------------------------------------------------------------
-def check_standalone_operators(lib, device, n, nz, exact):
+def staged_bound(scale, S, factor=2.0):
+    """The bound on max |got - float32(ref)| of an output with intermediates in `real` storage: one float32 ulp of the magnitude
+    `scale` = max |ref| for the output's own rounding + factor x the oracle's response S to one rounding of its inputs
+    (tests/test_f32_operators.py has the reasoning).  The one place it is written."""
+    return 2.0 ** -23 * scale + factor * S
+
+
+def _staged_f32(name, got, ref, noisy, report):
+    """float32 storage, an output with intermediates in `real` storage, against staged_bound with
+    S = max |oracle(inputs (+) noise) - oracle(inputs)| over the draws `noisy`."""
+    assert got.dtype == np.float32, (name, got.dtype)
+    S = max(float(np.abs(x - ref).max()) for x in noisy)
+    err = float(np.abs(got.astype(np.float64) - f32(ref)).max())
+    scale = float(np.abs(ref).max())
+    if report is not None:
+        report[name] = dict(err_in_u=err / (2.0 ** -24 * scale + 1e-300), err_over_S=err / S if S > 0 else (0.0 if err == 0 else np.inf))
+    assert err <= staged_bound(scale, S), (name, err, scale, S)
+    return err / (scale + 1e-300)
+
+
+def check_standalone_operators(lib, device, n, nz, exact, storage=None, report=None):
     """XPiecewiseParabolic / YPiecewiseParabolic (iord 5, 6, 8; the windows fvtp2d uses: inner = compute x full, outer =
-    compute + 1) and DivergenceDamping against the oracle.  Returns {name: error}."""
+    compute + 1) and DivergenceDamping against the oracle.  Returns {name: error}.
+
+    storage="f32" (a float32-storage library): metrics, column tables and every input are float32 values; XPPM / YPPM (one pass
+    from loads to stores) must equal float32(oracle) bit for bit, as must DivergenceDamping's divgd, uc and vc; its vort_b, ke and
+    delpc and Sim1Solver's outputs (intermediates in `real` storage) are held to the staged bound of _staged_f32, with the oracle's
+    response to storage noise from two draws of f32_neighbours.  `report` then receives {name: error in u = 2^-24 max |ref|, error / S}."""
     import torch
 
     from helpers import Env
@@ -550,14 +639,20 @@ def check_standalone_operators(lib, device, n, nz, exact):
     from pace_amd.fv3core.stencils.xppm import XPiecewiseParabolic
     from pace_amd.fv3core.stencils.yppm import YPiecewiseParabolic
 
+    assert storage in (None, "f32") and (storage is None) == (lib.real_bytes == 8)
     m = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(m, n, nz)
+    col = column(nz)
+    if storage:
+        m, s, col = f32_dict(m), f32_dict(s), f32_dict(col)
+    rd = f32 if storage else (lambda a: a)  # what a float32 field makes of an input
     env = Env(lib, device, m, n, nz)
     g = Grid(n, nz, m)
-    col = column(nz)
     for k in ("crx", "cry", "xfx", "yfx"):
         s[k] = np.zeros_like(s["pt"])
     dgrid_sw.fxadv(g, s["uc"], s["vc"], s["crx"], s["cry"], s["xfx"], s["yfx"], np.zeros_like(s["pt"]), np.zeros_like(s["pt"]), s["dt"])
+    for k in ("crx", "cry", "xfx", "yfx"):
+        s[k] = rd(s[k])
     errs = {}
     q, crx, cry = env.q3(s["pt"]), env.q3(s["crx"]), env.q3(s["cry"])
     for iord in (5, 6, 8):
@@ -573,28 +668,44 @@ def check_standalone_operators(lib, device, n, nz, exact):
             ref = np.zeros_like(s["pt"])
             tr.ppm_flux(s["pt"], c_np, m[name], g, axis, iord, ref, origin, domain)
             W = tuple(slice(o, o + d) for o, d in zip(origin, domain))
-            e = compare(ref[W], out.numpy()[W])
+            e = compare(rd(ref[W]), out.numpy()[W])
             errs[f"{'xy'[axis]}ppm{iord}"] = e
-            assert e == 0.0 if exact else e < 1e-14, (axis, iord, e)
+            if storage:
+                assert out.numpy().dtype == np.float32 and np.array_equal(out.numpy()[W], ref[W].astype(np.float32)), (axis, iord, e)
+            else:
+                assert e == 0.0 if exact else e < 1e-14, (axis, iord, e)
             untouched = out.numpy().copy()
             untouched[W] = 0.0
             assert not untouched.any(), "written outside origin .. origin + domain"
     # DivergenceDamping on the synthetic winds (vorticity = a smooth field; ke = another)
     f = {k: s[k].copy() for k in ("u", "v", "va", "ua", "divgd", "vc", "uc")}
     f["vort_b"], f["delpc"] = np.zeros_like(s["pt"]), np.zeros_like(s["pt"])
-    f["ke"] = 0.5 * (s["u"] ** 2 + s["v"] ** 2)
-    f["wk"] = 1.0e-5 * s["pt"] * np.cos(s["u"] * 0.1)
+    f["ke"] = rd(0.5 * (s["u"] ** 2 + s["v"] ** 2))
+    f["wk"] = rd(1.0e-5 * s["pt"] * np.cos(s["u"] * 0.1))
     qf = {k: env.q3(a) for k, a in f.items()}
+    rng = [np.random.default_rng(20240905 + d) for d in range(2)]
+
+    def divdamp(f):
+        damping.divergence_damping(g, f["u"], f["v"], f["va"], f["vort_b"], f["ua"], f["divgd"], f["vc"], f["uc"], f["delpc"], f["ke"],
+                                   f["wk"], s["dt"], nord_k=col["nord"], d2_bg_k=col["d2_divg"], dddmp=DSW_CFG["dddmp"],
+                                   d4_bg=DSW_CFG["d4_bg"], nord=DSW_CFG["nord"])
+        return f
+
+    noisy = [divdamp({k: f32_neighbours(a, r) for k, a in f.items()}) for r in rng] if storage else []
     op = DivergenceDamping(env.stencil_factory, env.qf, env.grid_data, env.damping, False, False, DSW_CFG["dddmp"], DSW_CFG["d4_bg"],
                            DSW_CFG["nord"], 0, env.kq(col["nord"]), env.kq(col["d2_divg"]))
     op(qf["u"], qf["v"], qf["va"], qf["vort_b"], qf["ua"], qf["divgd"], qf["vc"], qf["uc"], qf["delpc"], qf["ke"], qf["wk"], s["dt"])
     if device != "cpu":
         torch.cuda.synchronize()
-    damping.divergence_damping(g, f["u"], f["v"], f["va"], f["vort_b"], f["ua"], f["divgd"], f["vc"], f["uc"], f["delpc"], f["ke"],
-                               f["wk"], s["dt"], nord_k=col["nord"], d2_bg_k=col["d2_divg"], dddmp=DSW_CFG["dddmp"],
-                               d4_bg=DSW_CFG["d4_bg"], nord=DSW_CFG["nord"])
+    divdamp(f)
     B = _win(n, 0, 0, 1, 1)
     for k, W in (("vort_b", B), ("ke", B), ("delpc", B), ("divgd", B), ("uc", _win(n, 0, 0, 1, 0)), ("vc", _win(n, 0, 0, 0, 1))):
+        if storage:
+            errs["divdamp_" + k] = _staged_f32("divdamp_" + k, qf[k].numpy()[W][:, :, :nz], f[k][W][:, :, :nz],
+                                               [x[k][W][:, :, :nz] for x in noisy], report)
+            # (the nord passes run in LDS in double: the last pass's divergence, uc and vc are stored once)
+            assert k not in ("divgd", "uc", "vc") or np.array_equal(qf[k].numpy()[W][:, :, :nz], f[k][W][:, :, :nz].astype(np.float32)), k
+            continue
         e = compare(f[k][W][:, :, :nz], qf[k].numpy()[W][:, :, :nz], near_zero=1e-14 * float(np.abs(f[k][W]).max()))
         errs["divdamp_" + k] = e
         assert e == 0.0 if exact else e < 1.4e-10, (k, e)  # translate_divergencedamping.py:37
@@ -605,13 +716,15 @@ def check_standalone_operators(lib, device, n, nz, exact):
         pm[:, :, :nz] = (pem[:, :, 1:] - pem[:, :, :-1]) / (np.log(pem[:, :, 1:]) - np.log(pem[:, :, :-1]))
     pm[~np.isfinite(pm)] = 1.0e4
     pem[~np.isfinite(pem)] = 1.0e4
-    gm = 1.0 / (1.0 - s["cappa"])
+    pm, pem = rd(pm), rd(pem)
+    gm = rd(1.0 / (1.0 - s["cappa"]))
     dmass = s["delp"] * oc.RGRAV
     dmass[dmass <= 0] = 1.0  # (the allocator's extra level and unused halo cells)
+    dmass = rd(dmass)
     dz0 = np.where(s["delz"] < 0, s["delz"], -100.0)
     for n_halo in (0, 1):
         f = dict(gamma=gm.copy(), cp3=s["cappa"].copy(), pe=np.zeros_like(s["pt"]), dm=dmass.copy(), pm=pm.copy(), pem=pem.copy(),
-                 w=s["w"].copy(), dz=dz0.copy(), pt=np.where(s["pt"] > 0, s["pt"], 300.0), ws=np.zeros(s["pt"].shape[:2]) + 0.01)
+                 w=s["w"].copy(), dz=dz0.copy(), pt=np.where(s["pt"] > 0, s["pt"], 300.0), ws=rd(np.zeros(s["pt"].shape[:2]) + 0.01))
         q = {k: (env.q3(a) if a.ndim == 3 else env.q2(a)) for k, a in f.items()}
         from pace_amd.fv3core.stencils.sim1_solver import Sim1Solver
 
@@ -619,14 +732,24 @@ def check_standalone_operators(lib, device, n, nz, exact):
         op(s["dt"], q["gamma"], q["cp3"], q["pe"], q["dm"], q["pm"], q["pem"], q["w"], q["dz"], q["pt"], q["ws"])
         if device != "cpu":
             torch.cuda.synchronize()
-        vertical.sim1_solve(f["w"], f["dm"], f["gamma"], f["dz"], f["pt"], f["pm"], f["pe"], f["pem"], f["ws"], f["cp3"], s["dt"],
-                            0.05, (3 - n_halo, 3 + n + n_halo, 3 - n_halo, 3 + n + n_halo), nz)
+
+        def sim1(f):
+            vertical.sim1_solve(f["w"], f["dm"], f["gamma"], f["dz"], f["pt"], f["pm"], f["pe"], f["pem"], f["ws"], f["cp3"], s["dt"],
+                                0.05, (3 - n_halo, 3 + n + n_halo, 3 - n_halo, 3 + n + n_halo), nz)
+            return f
+
+        noisy = [sim1({k: f32_neighbours(a, r) for k, a in f.items()}) for r in rng] if storage else []
+        sim1(f)
         Wd = (slice(3 - n_halo, 3 + n + n_halo), slice(3 - n_halo, 3 + n + n_halo))
         for k, nlev in (("w", nz), ("dz", nz), ("pe", nz + 1)):
             ref, got = f[k][Wd][:, :, :nlev], q[k].numpy()[Wd][:, :, :nlev]
-            e = compare(ref, got, near_zero=1e-5 * float(np.abs(ref).max()))
-            errs[f"sim1_h{n_halo}_{k}"] = e
-            assert e < 5e-6, (n_halo, k, e)  # the reference's Riem_Solver3 bound (the solver's only Translate-level users)
+            if storage:
+                name = f"sim1_h{n_halo}_{k}"
+                errs[name] = _staged_f32(name, got, ref, [x[k][Wd][:, :, :nlev] for x in noisy], report)
+            else:
+                e = compare(ref, got, near_zero=1e-5 * float(np.abs(ref).max()))
+                errs[f"sim1_h{n_halo}_{k}"] = e
+                assert e < 5e-6, (n_halo, k, e)  # the reference's Riem_Solver3 bound (the solver's only Translate-level users)
             untouched = q[k].numpy().copy() - (np.zeros_like(f[k]) if k == "pe" else (s["w"] if k == "w" else dz0))
             untouched[Wd] = 0.0
             assert not untouched[:, :, :nlev].any(), ("written outside the compute domain + n_halo", n_halo, k)

@@ -8,6 +8,11 @@ to 6e-8 of its value each time it is stored.  Bounds (max |got - ref| / max |ref
   * one whole DynamicalCore step: 1e-5 for masses, pressures, temperatures; 1e-4 for the condensates (values ~1e-3 of the
     field's range); 2e-3 for the horizontal winds and 2e-2 for w / omga -- the algorithm amplifies 1e-13 of wind noise to
     2e-4 in one step of this zonal-flow case (tools/wind_noise_sensitivity.py), float32 rounding is a million times more.
+    For w / omga there is a second, direct reason: the column solvers' lower boundary value ws = (zs - bottom height) / dt is formed
+    from a height stored as float32 and is off the float64 value, per call, by 0.2 to 1.8 % of max |ws| at 13 x 5 and 48 x 3 and
+    by 17 to 24 % at 13 x 33, which is as good as float32 heights allow
+    (tests/test_f32_operators.py test_ws_is_ill_conditioned_in_float32_heights).
+The operators one by one, against float32(oracle) and not against a fraction of the field: tests/test_f32_operators.py.
 """
 import numpy as np
 import pytest
