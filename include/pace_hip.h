@@ -630,6 +630,34 @@ typedef struct {
 } pace_unpack_item_t;
 int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, int nitems, const double* in, void* stream);
 
+/* ---- The state into the data sections of Fortran FV3 restart files (NetCDF-3: dense, big-endian), with FMS's per-variable sums:
+ * the inverse of pace_state_unpack's XFAST items.  Up to PACE_RESTART_MAX_ITEMS windows of fields are gathered by ONE launch into
+ * one device BYTE buffer, both storage types, no atomics, no host synchronisation.  items: HOST array of nitems items.
+ *   output element e = i + ni * (j + nj * k) of an item = field(i0 + i, j0 + j, k0 + k), x fastest: the file's (z, y, x) C order,
+ *   which is the storage's own; the row padding is dropped.  The value is widened to double (exact), for PACE_RESTART_BE_F32 then
+ *   narrowed by a plain cast (round to nearest even, overflow to +-inf), and written BIG-endian at out + out_offset + e * size.
+ *   sums[m] = the wrapping (mod 2^64) sum over item m's elements of the bit pattern of the value as written, before the swap:
+ *   64 bits for BE_F64, the 32 bits zero-extended for BE_F32.  Per-workgroup partials, then a combine: integer addition commutes,
+ *   so the result does not depend on the order workgroups run in.
+ * float64 library -> BE_F64 moves bits: -0.0, denormals, +-inf and NaN payloads arrive unchanged.  out == NULL: sums only;
+ * sums == NULL: pack only.  Nothing outside a window is read; nothing outside an item's ni * nj * nk elements is written.
+ * workspace: at least pace_restart_pack_workspace_bytes(geom, items, nitems) bytes of device memory (0 for arguments that
+ * pace_restart_pack refuses); it holds nothing between calls, need not be cleared and may be NULL where sums is.
+ * PACE_ERR_ARG: nitems < 1 or > PACE_RESTART_MAX_ITEMS, a kind other than WINDOW3D and PLANE, an unknown out_type, a window that
+ * is empty or outside the storage (n + 7, n + 7, nk + 1), a NULL field, an out_offset that is negative or no multiple of the
+ * output element's size, out and sums both NULL, sums without workspace. */
+#define PACE_RESTART_MAX_ITEMS 32
+enum { PACE_RESTART_BE_F64 = 0, PACE_RESTART_BE_F32 = 1 };
+typedef struct {
+  const pace_real_t* field;   /* element (0,0,0) of the storage; for PLANE: of a 2-D field or of ONE level's plane */
+  int32_t kind;               /* PACE_DIAG_WINDOW3D | PACE_DIAG_PLANE */
+  int32_t i0, j0, k0, ni, nj, nk;   /* window in the storage; PLANE: k0 = 0, nk = 1 */
+  int64_t out_offset;         /* BYTES into out; a multiple of the output element's size */
+} pace_restart_item_t;
+int64_t pace_restart_pack_workspace_bytes(const pace_geom_t* geom, const pace_restart_item_t* items, int nitems);
+int pace_restart_pack(const pace_geom_t* geom, const pace_restart_item_t* items, int nitems, int out_type, void* out,
+                      uint64_t* sums, void* workspace, void* stream);
+
 /* ---- The interface pressures of a state read from a Fortran restart, which holds delp only
  * (driver/pace/driver/initialization.py:422-442), ONE launch:
  *   pe(i, j, k) = ptop + sum over l < k of delp(i, j, l),  peln = log(pe),  k = 0 .. nk

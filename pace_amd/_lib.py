@@ -137,6 +137,15 @@ class UnpackItem(C.Structure):  # include/pace_hip.h pace_unpack_item_t
                 ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("in_step", C.c_int32), ("in_offset", C.c_int64)]
 
 
+RESTART_MAX_ITEMS = 32  # include/pace_hip.h PACE_RESTART_MAX_ITEMS
+RESTART_BE_F64, RESTART_BE_F32 = 0, 1  # include/pace_hip.h PACE_RESTART_*
+
+
+class RestartItem(C.Structure):  # include/pace_hip.h pace_restart_item_t
+    _fields_ = [("field", c_dp), ("kind", C.c_int32), ("i0", C.c_int32), ("j0", C.c_int32), ("k0", C.c_int32),
+                ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("out_offset", C.c_int64)]
+
+
 CKPT_MAX_ITEMS = 32  # include/pace_hip.h PACE_CKPT_MAX_ITEMS
 
 
@@ -246,6 +255,8 @@ _PROTOS = {
     "pace_state_extrema": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_int), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_diag_pack": (C.c_int, [_P(Geom), _P(DiagItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pace_state_unpack": (C.c_int, [_P(Geom), _P(UnpackItem), C.c_int, c_dp, C.c_void_p]),
+    "pace_restart_pack_workspace_bytes": (C.c_int64, [_P(Geom), _P(RestartItem), C.c_int]),
+    "pace_restart_pack": (C.c_int, [_P(Geom), _P(RestartItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pace_pe_peln_from_delp": (C.c_int, [_P(Geom), c_dp, C.c_double, c_dp, c_dp, C.c_void_p]),
     "pace_ckpt_accumulate": (C.c_int, [_P(CkptItem), C.c_int, C.c_int, C.c_void_p]),
     "pace_ckpt_thresholds_workspace_bytes": (C.c_int64, [_P(CkptItem), C.c_int]),

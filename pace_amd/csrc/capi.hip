@@ -707,6 +707,36 @@ int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, 
   return launch_state_unpack(make_geo(geom), items, nitems, in, S(stream));
 }
 
+static int restart_check(const pace_geom_t* geom, const pace_restart_item_t* items, int nitems) {
+  if (!items || nitems < 1 || nitems > PACE_RESTART_MAX_ITEMS) return PACE_ERR_ARG;
+  const int ni = geom->n + 7, nlev = geom->nk + 1;
+  for (int m = 0; m < nitems; ++m) {
+    const pace_restart_item_t& it = items[m];
+    if (it.kind != PACE_DIAG_WINDOW3D && it.kind != PACE_DIAG_PLANE) return PACE_ERR_ARG;
+    if (!it.field) return PACE_ERR_ARG;
+    if (it.i0 < 0 || it.ni < 1 || it.ni > ni - it.i0 || it.j0 < 0 || it.nj < 1 || it.nj > ni - it.j0) return PACE_ERR_ARG;
+    if (it.kind == PACE_DIAG_PLANE ? (it.k0 != 0 || it.nk != 1) : (it.k0 < 0 || it.nk < 1 || it.nk > nlev - it.k0)) return PACE_ERR_ARG;
+  }
+  return PACE_OK;
+}
+
+int64_t pace_restart_pack_workspace_bytes(const pace_geom_t* geom, const pace_restart_item_t* items, int nitems) {
+  if (!geom || geom_check(geom) != PACE_OK || restart_check(geom, items, nitems) != PACE_OK) return 0;
+  return (int64_t)restart_pack_workspace_bytes(items, nitems);
+}
+
+int pace_restart_pack(const pace_geom_t* geom, const pace_restart_item_t* items, int nitems, int out_type, void* out,
+                      uint64_t* sums, void* workspace, void* stream) {
+  NEED(geom && items && (out || sums) && (!sums || workspace));
+  if (out_type != PACE_RESTART_BE_F64 && out_type != PACE_RESTART_BE_F32) return PACE_ERR_ARG;
+  if (restart_check(geom, items, nitems) != PACE_OK) return PACE_ERR_ARG;
+  const int esize = out_type == PACE_RESTART_BE_F64 ? 8 : 4;
+  for (int m = 0; m < nitems; ++m)
+    if (items[m].out_offset < 0 || items[m].out_offset % esize != 0) return PACE_ERR_ARG;
+  if (out && (uintptr_t)out % esize != 0) return PACE_ERR_ARG;
+  return launch_restart_pack(make_geo(geom), items, nitems, out_type, out, sums, workspace, S(stream));
+}
+
 int pace_pe_peln_from_delp(const pace_geom_t* geom, const real* delp, double ptop, real* pe, real* peln, void* stream) {
   NEED(geom && delp && pe && peln);
   return launch_pe_peln_from_delp(make_geo(geom), delp, ptop, pe, peln, S(stream));

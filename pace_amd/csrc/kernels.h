@@ -283,6 +283,10 @@ int launch_state_extrema(const Geo& g, const real* const* fields, const int* com
 int launch_diag_pack(const Geo& g, const pace_diag_item_t* items, int nitems, int out_is_double, void* out, hipStream_t st);
 // k_state.hip
 int launch_state_unpack(const Geo& g, const pace_unpack_item_t* items, int nitems, const double* in, hipStream_t st);
+// k_restart.hip
+size_t restart_pack_workspace_bytes(const pace_restart_item_t* items, int nitems);
+int launch_restart_pack(const Geo& g, const pace_restart_item_t* items, int nitems, int out_type, void* out, uint64_t* sums,
+                        void* workspace, hipStream_t st);
 int launch_pe_peln_from_delp(const Geo& g, const real* delp, double ptop, real* pe, real* peln, hipStream_t st);
 // k_ckpt.hip
 long ckpt_thresholds_blocks(const pace_ckpt_item_t* items, int nitems);

@@ -6,6 +6,7 @@ from .config import (  # noqa: F401
     BaroclinicInit,
     CreatesCommSelector,
     DriverConfig,
+    FortranRestartConfig,
     FortranRestartInit,
     GeneratedGridConfig,
     GridInitializerSelector,

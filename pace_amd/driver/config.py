@@ -13,12 +13,19 @@ What is accepted, refused and ignored:
   comm_config.type      null (null_comm), torch; mpi, write, read: NotImplementedError.  Absent: null, rank 0 of 6 -- the
                         reference's default is mpi, which does not exist here
   pair_debug            NotImplementedError when true
-  restart_config        NotImplementedError when it enables output (save_restart, intermediate_restart)
+  restart_config        NotImplementedError when it enables output (save_restart, intermediate_restart): pace's own restart
+                        format is not written
+  fortran_restart_config  (not in the reference) save_restart, intermediate_restart, path: the state in the FORTRAN model's
+                        restart format at the end of the run (<path>) and after the listed steps (<path>_<step>), each with a
+                        restart.yaml that resumes from it (Driver.write_fortran_restart)
+  initialization.config.verify_checksums  (fortran_restart; not in the reference) hold what was read against the files' checksums
+  initialization.config.surface_winds     (fortran_restart; not in the reference) u_srf / v_srf into the lowest level of ua / va
   diagnostics_config    output_format npz with a path: written (driver/diagnostics.py); zarr, netcdf: parsed and kept, nothing is
                         written (the Driver warns once)
   performance_config    parsed and kept; nothing is written
   stencil_config.compilation_config.backend  kept as `requested_backend`; the backend is always hip:gfx950
 """
+import copy
 import ctypes as C
 import dataclasses
 import functools
@@ -102,6 +109,9 @@ class FortranRestartInit:
     and fv_srf_wnd files, the time of its coupler.res."""
 
     path: str = "."
+    verify_checksums: bool = False  # hold the state against the files' tile_checksum / checksum attributes (util/restart.py)
+    # u_srf / v_srf into the lowest level of ua / va, where Driver.write_fortran_restart took them from (its restart.yaml says so)
+    surface_winds: bool = False
 
     @property
     def start_time(self) -> datetime:
@@ -113,10 +123,19 @@ class FortranRestartInit:
             raise ValueError(f"no coupler.res found at {self.path}")
         return get_current_date_from_coupler_res(os.path.join(self.path, coupler_files[0]))
 
+    @property
+    def model_start_time(self) -> Optional[datetime]:
+        """The model start time coupler.res records beside the current time (a restart written from this run carries it on)."""
+        from ..util.restart import get_start_date_from_coupler_res
+
+        coupler_files = sorted(name for name in os.listdir(self.path) if name.endswith("coupler.res"))
+        return get_start_date_from_coupler_res(os.path.join(self.path, coupler_files[0])) if coupler_files else None
+
     def get_driver_state(self, quantity_factory, communicator, damping_coefficients, driver_grid_data, grid_data) -> DriverState:
         from ..fv3core.initialization.dycore_state import DycoreState
 
-        dycore_state = DycoreState.from_fortran_restart(quantity_factory=quantity_factory, communicator=communicator, path=self.path)
+        dycore_state = DycoreState.from_fortran_restart(quantity_factory=quantity_factory, communicator=communicator, path=self.path,
+                                                        verify_checksums=self.verify_checksums, surface_winds=self.surface_winds)
         state = DriverState(dycore_state=dycore_state,
                             physics_state=PhysicsState.init_zeros(quantity_factory=quantity_factory, active_packages=["microphysics"]),
                             tendency_state=TendencyState.init_zeros(quantity_factory=quantity_factory), grid_data=grid_data,
@@ -335,6 +354,29 @@ class RestartConfig:
         return config if isinstance(config, cls) else _strict(cls, "restart_config", dict(config or {}))
 
 
+@dataclasses.dataclass()
+class FortranRestartConfig:
+    """Restart files in the Fortran model's format (pace_amd.util.write_restart): the final state to `path`, the state after
+    step s of intermediate_restart (1-based, as the reference's RESTART_{step}) to `path`_s."""
+
+    save_restart: bool = False
+    intermediate_restart: List[int] = dataclasses.field(default_factory=list)
+    path: str = "RESTART"
+
+    @classmethod
+    def from_dict(cls, config) -> "FortranRestartConfig":
+        return config if isinstance(config, cls) else _strict(cls, "fortran_restart_config", dict(config or {}))
+
+
+def _plain(value):
+    """What yaml.safe_dump takes: tuples as lists, all the way down."""
+    if isinstance(value, dict):
+        return {key: _plain(v) for key, v in value.items()}
+    if isinstance(value, (list, tuple)):
+        return [_plain(v) for v in value]
+    return value
+
+
 def _stencil_config(config) -> StencilConfig:
     """The reference's stencil_config section: compilation_config's flags are kept, its backend (a GT4Py one in every reference
     file) is remembered as `requested_backend` and otherwise ignored; dace_config is dropped."""
@@ -391,6 +433,8 @@ class DriverConfig:
         output_frequency: number of model timesteps between diagnostic timesteps,
             defaults to every timestep
         safety_check_frequency: number of model timesteps between checks of the state, None or 0 for never
+        restart_config: the reference's own restart format: refused when it enables output
+        fortran_restart_config: restart files in the Fortran model's format (not in the reference)
     """
 
     stencil_config: StencilConfig
@@ -413,6 +457,7 @@ class DriverConfig:
     dycore_only: bool = False
     disable_step_physics: bool = False
     restart_config: RestartConfig = dataclasses.field(default_factory=RestartConfig)
+    fortran_restart_config: FortranRestartConfig = dataclasses.field(default_factory=FortranRestartConfig)
     pair_debug: bool = False
     output_initial_state: bool = False
     output_frequency: int = 1
@@ -458,9 +503,26 @@ class DriverConfig:
                                                     damping_coefficients=damping_coefficients, driver_grid_data=driver_grid_data,
                                                     grid_data=grid_data)
 
+    source = None  # the mapping from_dict was given (plain data), from which restart_dict makes a restart.yaml
+
+    def restart_dict(self, directory: str) -> Dict[str, Any]:
+        """This run's configuration as a mapping that starts from the Fortran restart in `directory`: initialization and
+        grid_config.config.restart_path point there; everything else is what from_dict was given."""
+        if self.source is None:
+            raise ValueError("a restart.yaml is made of the mapping DriverConfig.from_dict was given; this configuration has none")
+        d = _plain(self.source)
+        directory = os.path.abspath(directory)
+        d["initialization"] = {"type": "fortran_restart", "config": {"path": directory, "surface_winds": True}}
+        grid = dict(d.get("grid_config") or {})
+        grid.setdefault("type", "generated")
+        grid["config"] = {**dict(grid.get("config") or {}), "restart_path": directory}
+        d["grid_config"] = grid
+        return d
+
     @classmethod
     def from_dict(cls, kwargs: Dict[str, Any]) -> "DriverConfig":
         kwargs = dict(kwargs)
+        source = copy.deepcopy(kwargs)
         fields = {f.name: f for f in dataclasses.fields(cls)}
         for key in kwargs:
             if key not in fields:
@@ -504,10 +566,12 @@ class DriverConfig:
             kwargs["grid_config"] = GridInitializerSelector.from_dict(kwargs["grid_config"])
         kwargs["stencil_config"] = _stencil_config(kwargs["stencil_config"])
         for key, kind in (("diagnostics_config", DiagnosticsConfig), ("performance_config", PerformanceConfig),
-                          ("restart_config", RestartConfig)):
+                          ("restart_config", RestartConfig), ("fortran_restart_config", FortranRestartConfig)):
             if key in kwargs:
                 kwargs[key] = kind.from_dict(kwargs[key])
-        return cls(**kwargs)
+        config = cls(**kwargs)
+        config.source = source
+        return config
 
     @classmethod
     def from_yaml(cls, path: str) -> "DriverConfig":

@@ -8,12 +8,15 @@ A step is the reference's (driver.py:618-640): DynamicalCore.step_dynamics, Dyco
 each a class of its own that can also be called by hand; the driver only strings them together, advances the time and, every
 safety_check_frequency steps, checks the state (SafetyChecker: one launch pair and one transfer) and, every output_frequency
 steps, stores the diagnostics (MonitorDiagnostics: one pack launch and one transfer).  What the reference's constructor does
-for DaCe, build modes, restarts and the performance collector's files is not here.
+for DaCe, build modes, its own restart format and the performance collector's files is not here.  Restart files are written in
+the FORTRAN model's format (fortran_restart_config, write_fortran_restart: one pack launch and one transfer), which
+initialization.type fortran_restart reads back.
 
 One deliberate departure: the reference's constructor registers its four variables with SafetyChecker.register_variable, which
 raises on a second registration, so two reference Drivers cannot exist in one process.  Six of these do (one per tile on
 threads): the constructor registers each of the four only if it is absent, under a lock.  register_variable itself keeps raising.
 """
+import os
 import threading
 import warnings
 
@@ -141,6 +144,29 @@ class Driver:
         if self.config.safety_check_frequency and ((step + 1) % self.config.safety_check_frequency) == 0:
             with self.performance_collector.total_timer.clock("safety_check"):
                 self.safety_checker.check_state(self.state.dycore_state)
+        restart = self.config.fortran_restart_config
+        if (step + 1) in restart.intermediate_restart:
+            self.write_fortran_restart(f"{restart.path}_{step + 1}")
+
+    def write_fortran_restart(self, path: str):
+        """The state as restart files of the Fortran model in `path` (DycoreState.to_fortran_restart: one pace_restart_pack
+        launch, one device-to-host copy), with the current time in coupler.res; rank 0 adds restart.yaml, this run's
+        configuration with initialization and grid_config.config.restart_path pointing at `path`, so that
+        DriverConfig.from_yaml(<path>/restart.yaml) resumes."""
+        with self.performance_collector.total_timer.clock("restart"):
+            # (a run that itself began from a Fortran restart carries that file's model start time on)
+            start = getattr(self.config.initialization.config, "model_start_time", None) or self._start_time
+            self.state.dycore_state.to_fortran_restart(communicator=self.communicator, path=path, time=self.time,
+                                                       start_time=start, grid_data=self.state.grid_data)
+            if self.comm.Get_rank() == 0:
+                if self.config.source is None:
+                    warnings.warn(f"{path}: no restart.yaml is written, the configuration was not made by DriverConfig.from_dict",
+                                  UserWarning, stacklevel=2)
+                else:
+                    import yaml
+
+                    with open(os.path.join(path, "restart.yaml"), "w") as f:
+                        yaml.safe_dump(self.config.restart_dict(path), f, sort_keys=False)
 
     def _critical_path_step_all(self, steps_count: int, timer: Timer, dt: float):
         """Start of code path where performance is critical."""
@@ -161,6 +187,8 @@ class Driver:
         with self.performance_collector.total_timer.clock("total"):
             self._critical_path_step_all(steps_count=self.config.n_timesteps(), timer=self.performance_collector.timestep_timer,
                                          dt=self.config.timestep.total_seconds())
+        if self.config.fortran_restart_config.save_restart:
+            self.write_fortran_restart(self.config.fortran_restart_config.path)
 
     def sypd(self) -> float:
         """Simulated years per day of wall time, as the reference reports it (performance/report.py:116-129): dt_atmos over the

@@ -79,13 +79,41 @@ class DycoreState:
         return state
 
     @classmethod
-    def from_fortran_restart(cls, *, quantity_factory, communicator, path: str):
+    def from_fortran_restart(cls, *, quantity_factory, communicator, path: str, verify_checksums: bool = False,
+                             surface_winds: bool = False):
         """dycore_state.py:361-427: zeros, then the compute domains of the fifteen fields a Fortran restart holds, through
         pace_amd.util.open_restart -- one staging buffer, one host-to-device copy, one pace_state_unpack launch.  Halos and every
-        other field (ua, va, pe, peln, pk, pkz, ps, q_con, ...) stay zero, as in the reference."""
-        from ...util.restart import open_restart
+        other field (ua, va, pe, peln, pk, pkz, ps, q_con, ...) stay zero, as in the reference.  Two additions for restarts
+        written by to_fortran_restart: sgs_tke goes to qsgs_tke where the files have it (the Fortran model's need not), and with
+        surface_winds u_srf / v_srf go back where to_fortran_restart took them from, the lowest level of ua / va."""
+        from ...util.restart import LevelOf, open_restart
 
         new = cls.init_zeros(quantity_factory=quantity_factory)
-        open_restart(dirname=path, communicator=communicator, only_names=list(FORTRAN_RESTART_FIELDS.values()),
-                     to_state={name: getattr(new, field) for field, name in FORTRAN_RESTART_FIELDS.items()})
+        to_state = {name: getattr(new, field) for field, name in FORTRAN_RESTART_FIELDS.items()}
+        to_state["turbulent_kinetic_energy"] = new.qsgs_tke
+        if surface_winds:
+            lowest = new.ua.extent[2] - 1
+            to_state["eastward_wind_at_surface"] = LevelOf(new.ua, lowest)
+            to_state["northward_wind_at_surface"] = LevelOf(new.va, lowest)
+        open_restart(dirname=path, communicator=communicator, only_names=list(to_state), to_state=to_state,
+                     verify_checksums=verify_checksums, missing_ok=["turbulent_kinetic_energy"])
         return new
+
+    def to_fortran_restart(self, *, communicator, path: str, time, start_time=None, grid_data=None, label: str = "",
+                           file_dtype=None):
+        """The inverse of from_fortran_restart, in the Fortran model's format (the reference's DriverState.save_state leaves
+        this as a commented-out starter, driver/pace/driver/state.py:118-145): the fifteen fields of FORTRAN_RESTART_FIELDS, qsgs_tke
+        as sgs_tke, and the lowest level of ua / va as u_srf / v_srf, through pace_amd.util.write_restart -- one
+        pace_restart_pack launch, one device-to-host copy.  grid_data: its ak / bk go to fv_core.res.nc (rank 0)."""
+        import numpy as np
+
+        from ...util.restart import LevelOf, write_restart
+
+        from_state = {name: getattr(self, field) for field, name in FORTRAN_RESTART_FIELDS.items()}
+        from_state["turbulent_kinetic_energy"] = self.qsgs_tke
+        lowest = self.ua.extent[2] - 1
+        from_state["eastward_wind_at_surface"] = LevelOf(self.ua, lowest)
+        from_state["northward_wind_at_surface"] = LevelOf(self.va, lowest)
+        ak, bk = (None, None) if grid_data is None else (np.asarray(grid_data.ak), np.asarray(grid_data.bk))
+        write_restart(path, communicator, from_state, time=time, start_time=start_time, label=label, ak=ak, bk=bk,
+                      file_dtype=np.float64 if file_dtype is None else file_dtype)

@@ -6,5 +6,5 @@ from .partitioner import CubedSpherePartitioner, RingPartitioner, TilePartitione
 from ._timing import KernelTimes, NullTimer, Timer  # noqa: F401,E402
 from .checkpointer import (Checkpointer, InsufficientTrialsError, NullCheckpointer, SavepointThresholds, SnapshotCheckpointer,  # noqa: F401,E402
                            Threshold, ThresholdCalibrationCheckpointer, ValidationCheckpointer)
-from .restart import open_restart  # noqa: F401,E402
+from .restart import LevelOf, open_restart, write_restart  # noqa: F401,E402
 from . import testing  # noqa: F401,E402

@@ -63,6 +63,17 @@ class TorchDistComm:
         self._dist.all_reduce(t, op=self._dist.ReduceOp.MIN, group=self._group)
         return float(t.item())
 
+    def allreduce_sum_u64(self, values):
+        """The wrapping (mod 2^64) sum over the ranks of each of `values`: an int64 SUM, which wraps the same way."""
+        import numpy as np
+
+        a = np.ascontiguousarray(values, dtype=np.uint64)
+        t = torch.from_numpy(a.view(np.int64).copy())
+        if self._dist.get_backend(self._group) == "nccl":
+            t = t.cuda()
+        self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self._group)
+        return t.cpu().numpy().view(np.uint64)
+
 
 class NullComm:
     """util/pace/util/null_comm.py:15-80: the rank of a communicator that has no peers -- what it "receives" is a fill value
@@ -93,6 +104,10 @@ class NullComm:
 
     def allreduce_min(self, value: float) -> float:
         return value
+
+    def allreduce_sum_u64(self, values):
+        """None: a rank alone cannot know the sum over the globe."""
+        return None
 
 
 class LoopbackComm(NullComm):
@@ -128,6 +143,10 @@ class _World:
         self.arrived = 0
         self.generation = 0
         self.failed = False
+        self.reduce_arrived = 0
+        self.reduce_generation = 0
+        self.reduce_sum = None
+        self.reduce_result = None
 
 
 class ThreadComm:
@@ -159,6 +178,25 @@ class ThreadComm:
                 w.cond.notify_all()
             else:
                 self._wait(lambda: w.generation != gen, "barrier")
+
+    def allreduce_sum_u64(self, values):
+        """The wrapping (mod 2^64) sum over the tiles of each of `values`, through the world object."""
+        import numpy as np
+
+        a = np.array(values, dtype=np.uint64)
+        w = self._world
+        with w.cond:
+            gen = w.reduce_generation
+            w.reduce_sum = a if w.reduce_arrived == 0 else w.reduce_sum + a  # (unsigned array addition wraps)
+            w.reduce_arrived += 1
+            if w.reduce_arrived == w.n:
+                # (the next reduction cannot complete, and replace the result, before every tile has left this one)
+                w.reduce_result, w.reduce_arrived = w.reduce_sum, 0
+                w.reduce_generation += 1
+                w.cond.notify_all()
+            else:
+                self._wait(lambda: w.reduce_generation != gen, "allreduce_sum_u64")
+            return w.reduce_result.copy()
 
     def exchange(self, sends, recvs, tag=0):
         w = self._world

@@ -1,6 +1,7 @@
 """Run the model from one of the reference's driver configuration files: pace_amd.driver.Driver, its step_all, one JSON line.
 
     python tools/driver_run.py CONFIG.yaml [--steps N] [--device D] [--cpu-emulation] [--diagnostics DIR]
+                               [--write-fortran-restart DIR]
 
 runs ONE rank (tile 0) with the `null` communicator -- its halos receive zeros, so this exercises the loop, not the weather --
 and, launched under torch.distributed.run as tools/dycore_run.py is,
@@ -10,7 +11,9 @@ and, launched under torch.distributed.run as tools/dycore_run.py is,
 
 the six tiles of the cubed sphere, one process per tile (RCCL on GPUs, gloo with --cpu-emulation).  --steps replaces the
 file's run length.  --diagnostics DIR writes the file's diagnostics into DIR as per-tile numpy archives (it replaces
-diagnostics_config.path and sets output_format: npz; pace_amd.driver.NpzMonitor describes the files).  Rank 0 prints: workload, steps, ms per step (mean of the main loop's clock, the slowest rank), SYPD
+diagnostics_config.path and sets output_format: npz; pace_amd.driver.NpzMonitor describes the files).
+--write-fortran-restart DIR writes the final state into DIR as restart files of the Fortran model (Driver.write_fortran_restart)
+with a restart.yaml, from which `python tools/driver_run.py DIR/restart.yaml` resumes.  Rank 0 prints: workload, steps, ms per step (mean of the main loop's clock, the slowest rank), SYPD
 (Driver.sypd()), and the time of the safety check per call with its verdict: the checks the file asks for inside the loop
 (safety_check_frequency) and, after the run, three timed calls on the final state whose verdict is reported, not raised (a lone
 tile behind zero halos need not stay within the bounds).
@@ -35,6 +38,8 @@ def main():
     ap.add_argument("--cpu-emulation", action="store_true", help="the CPU emulation library (and gloo): a logic check, not a timing")
     ap.add_argument("--diagnostics", metavar="DIR", default=None,
                     help="write the file's diagnostics into DIR (diagnostics_config.path = DIR, output_format = npz)")
+    ap.add_argument("--write-fortran-restart", metavar="DIR", default=None,
+                    help="write the final state into DIR in the Fortran model's restart format, with a restart.yaml that resumes from it")
     args = ap.parse_args()
     import yaml
 
@@ -72,9 +77,12 @@ def main():
         config.seconds = int(round(args.steps * config.dt_atmos))
         if config.n_timesteps() != args.steps:
             raise SystemExit(f"--steps {args.steps} is no whole number of seconds at dt_atmos {config.dt_atmos}")
+        config.source["seconds"] = config.seconds  # (a restart.yaml of this run runs as long as this run)
     lib = _lib.Library(os.path.join(ROOT, "tests", "emu", "libpace_emu.so")) if args.cpu_emulation else _lib.load()
     driver = Driver(config, lib=lib, device=device)
     driver.step_all()
+    if args.write_fortran_restart is not None:
+        driver.write_fortran_restart(args.write_fortran_restart)
     if device != "cpu":
         torch.cuda.synchronize()
     steps = config.n_timesteps()

@@ -10,6 +10,9 @@
                                                     split into host staging, H2D, unpack launch, pack launch and D2H
     python tools/kbench.py --only checkpointer      a calibration call and a validation call with the sixteen fields of D_SW-In
                                                     against a torch restatement and against "to the host and numpy", the same way
+    python tools/kbench.py --only restart_pack      write_restart of a state's fifteen 3-D fields and three planes (launch,
+                                                    device-to-host copy, file writes) against a torch / numpy restatement, the
+                                                    same way, with the split into launch, transfer and write
 """
 import argparse
 import os
@@ -47,6 +50,9 @@ def main():
     n, nz = args.n, args.nz
     if args.only == "geos_wrapper":  # (its own state: nothing of the set-up below)
         geos_wrapper_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "restart_pack":  # (its own fields)
+        restart_pack_bench(lib, n, nz, args.reps)
         return
     if args.only == "checkpointer":  # (its own fields)
         checkpointer_bench(lib, n, nz, args.reps)
@@ -485,6 +491,131 @@ def diag_pack_bench(lib, env, s, n, nz, reps):
           f"{np.median(dev):.1f} us each = {(read_mb + out_mb) * 1e6 / (np.median(dev) * 1e-6) / 1e9:.0f} GB/s of read + write)")
     print(f"  torch restatement (slice, contiguous, float32, cpu per variable)   {ref:9.1f} us per step   (min {min(times['torch']):.1f})")
     print(f"  ratio torch / hip {ref / hip:.2f}")
+
+
+def restart_pack_bench(lib, n, nz, reps):
+    """pace_amd.util.write_restart on fifteen 3-D variables and three planes of a C<n> x <nz> tile -- ONE pace_restart_pack
+    launch, ONE device-to-host copy, three file.write calls of slices of the pinned buffer (into a directory of /dev/shm where
+    there is one: no disk in the figure) -- against the same work restated with torch and numpy: per variable the slice of the
+    compute domain, .contiguous() (the storage's own order: the row padding is dropped), .cpu(), then numpy's
+    astype('>f8') and the uint64 sum of the bit patterns, written with file.write.  Both end with the files written; the two
+    alternate, timed with the host clock from an idle device; medians and minima.  Then the HIP path's parts: the launch alone
+    (device events around back-to-back launches), the transfer alone, the writes alone."""
+    import datetime
+    import shutil
+    import tempfile
+    import time
+
+    from pace_amd.util import CubedSphereCommunicator, LevelOf, NullComm, QuantityFactory, SubtileGridSizer, restart
+
+    sizer = SubtileGridSizer.from_tile_params(nx_tile=n, ny_tile=n, nz=nz, n_halo=3, extra_dim_lengths={}, layout=(1, 1))
+    qf = QuantityFactory(sizer, device="cuda", dtype=torch.float32 if lib.real_bytes == 4 else torch.float64)
+    communicator = CubedSphereCommunicator(NullComm(0, 6), device="cuda", lib=lib)
+    rng = np.random.default_rng(0)
+    names = [name for name, entry in restart.RESTART_PROPERTIES.items() if len(entry["dims"]) == 3 and entry["restart_name"] not in ("ua", "va")]
+    assert len(names) == 15
+    state = {}
+    for name in names:
+        q = qf.zeros(restart.RESTART_PROPERTIES[name]["dims"][::-1], "")
+        q.set(rng.uniform(-50.0, 50.0, q.shape))
+        state[name] = q
+    state["surface_geopotential"] = qf.zeros(["x", "y"], "")
+    state["surface_geopotential"].set(rng.uniform(0.0, 1e4, state["surface_geopotential"].shape))
+    wind = state["vertical_wind"]
+    state["eastward_wind_at_surface"], state["northward_wind_at_surface"] = LevelOf(wind, nz - 1), LevelOf(wind, nz - 2)
+    base = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    when = datetime.datetime(2016, 8, 1)
+
+    def window(value):
+        q, level = (value.quantity, value.level) if isinstance(value, LevelOf) else (value, None)
+        t = q._base[tuple(slice(o, o + e) for o, e in zip(q.origin[::-1], q.extent[::-1]))] if level is None else \
+            q._base[level, q.origin[1]:q.origin[1] + q.extent[1], q.origin[0]:q.origin[0] + q.extent[0]]
+        return t  # [k][j][i]: the file's order
+
+    def hip_step():
+        restart.write_restart(os.path.join(base, "hip"), communicator, state, time=when)
+
+    def torch_step():
+        os.makedirs(os.path.join(base, "torch"), exist_ok=True)
+        sums = {}
+        with open(os.path.join(base, "torch", "data.bin"), "wb") as f:
+            for name, value in state.items():
+                host = window(value).contiguous().cpu().numpy()
+                sums[name] = host.astype("=f8").view(np.uint64).sum(dtype=np.uint64)
+                f.write(host.astype(">f8").data)
+        return sums
+
+    try:
+        want = torch_step()
+        hip_step()
+        # the same bytes and the same sums: every file's variables against the restatement's
+        import scipy.io
+
+        for kind in restart.RESTART_NAMES:
+            with scipy.io.netcdf_file(os.path.join(base, "hip", f"{kind}.tile1.nc"), "r", mmap=False) as nc:
+                for name, value in state.items():
+                    variable = nc.variables.get(restart.RESTART_PROPERTIES[name]["restart_name"])
+                    if variable is None:
+                        continue
+                    assert np.array_equal(np.array(variable[0]).view(np.uint64), window(value).cpu().numpy().astype(">f8").view(np.uint64)), name
+                    assert variable.tile_checksum.decode() == restart.checksum_text(want[name]), name
+        paths = {"hip": hip_step, "torch": torch_step}
+        times = {k: [] for k in paths}
+        for k, fn in paths.items():  # warm-up: code objects, the pinned buffer, torch's copy kernels
+            for _ in range(3):
+                fn()
+        for _ in range(reps):
+            for k, fn in paths.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                times[k].append((time.perf_counter() - t0) * 1e3)
+        # the parts of the HIP path: the launch ...
+        geom = restart._geometry([v.quantity if isinstance(v, LevelOf) else v for v in state.values()])
+        entries = [(v.quantity, v.level) if isinstance(v, LevelOf) else (v, None) for v in state.values()]
+        windows = restart._windows_of(entries, lib.real_bytes)
+        sizes = [w[5] * w[6] * w[7] * 8 for w in windows]
+        offsets = [int(x) for x in np.concatenate(([0], np.cumsum(sizes)[:-1]))]
+        total = sum(sizes)
+        packed = torch.empty(total // 8 + len(windows), dtype=torch.int64, device="cuda")
+        host = torch.empty(total // 8 + len(windows), dtype=torch.int64, pin_memory=True)
+        stream = communicator.stream()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        dev, copy_ms, write_ms, burst = [], [], [], 5
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(burst):
+                keep = restart._pack(lib, geom, windows, offsets, 0, packed.data_ptr(), packed.data_ptr() + total, "cuda", stream)
+            e1.record()
+            torch.cuda.synchronize()
+            del keep
+            dev.append(e0.elapsed_time(e1) / burst)
+            t0 = time.perf_counter()
+            restart._to_host(packed, host)  # ... the transfer ...
+            copy_ms.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            data = memoryview(host.numpy()).cast("B")
+            with open(os.path.join(base, "hip", "data.bin"), "wb") as f:  # ... and the writes
+                f.write(data[:total])
+            write_ms.append((time.perf_counter() - t0) * 1e3)
+        read_mb = sum(sizes) / 8 * lib.real_bytes / 1e6
+        out_mb = total / 1e6
+        hip, ref = float(np.median(times["hip"])), float(np.median(times["torch"]))
+        launch = float(np.median(dev))
+        print(f"restart_pack C{n} x {nz}, {len(windows)} variables (15 3-D, 3 planes), {read_mb:.1f} MB read, {out_mb:.1f} MB of "
+              f"big-endian float64 to the host and into files under {base}; medians of {reps} alternating runs")
+        print(f"  write_restart (pace_restart_pack, one transfer, file.write of the pinned buffer)   {hip:9.2f} ms per call   "
+              f"(min {min(times['hip']):.2f})")
+        print(f"    launch  {launch:8.3f} ms (min {min(dev):.3f}; {burst} back to back in device events) = "
+              f"{(read_mb + out_mb) / launch:6.0f} GB/s of read + write")
+        print(f"    transfer {np.median(copy_ms):7.3f} ms (min {min(copy_ms):.3f}) = {out_mb / np.median(copy_ms):5.1f} GB/s to pinned memory")
+        print(f"    write   {np.median(write_ms):8.3f} ms (min {min(write_ms):.3f}) = {out_mb / np.median(write_ms):5.1f} GB/s, one file.write of all of it")
+        print(f"  torch / numpy restatement (slice, contiguous, cpu, astype('>f8'), uint64 sum, file.write per variable)   {ref:9.2f} ms "
+              f"per call   (min {min(times['torch']):.2f})")
+        print(f"  ratio torch / hip {ref / hip:.2f}")
+    finally:
+        shutil.rmtree(base, ignore_errors=True)
 
 
 def checkpointer_bench(lib, n, nz, reps):
