@@ -800,6 +800,25 @@ typedef struct {
 int pace_halo_pack(const pace_geom_t* geom, const pace_halo_desc_t* descs, int ndesc, void* stream);
 int pace_halo_unpack(const pace_geom_t* geom, const pace_halo_desc_t* descs, int ndesc, void* stream);
 
+/* ---- Halo update of tiles that share a device, without a message: one launch moves every strip of every field of every tile.
+ * Entry t writes, for 0 <= a < na, 0 <= b < nb, 0 <= k < nk,
+ *   dst[(ri0 + a, rj0 + b, k)] = sign * src[(i0 + a*di_a + b*di_b, j0 + a*dj_a + b*dj_b, k)]
+ * -- the destination half is the receiver's strip of pace_halo_unpack, the source half the sender's strip of pace_halo_pack
+ * (rotation, vector component swap and sign folded into the map).  All fields share `geom`.  dst / src are DEVICE pointers and
+ * so is `table`: it holds hundreds of entries (6 tiles x 4 edges x fields), which the kernel reads in place, one per workgroup
+ * row.  PACE_HALO_XFER_B_FAST: consecutive lanes walk b, not a (the host sets it where the longer unit-stride run lies along b).
+ * The entries cannot be checked here: whoever builds the table guarantees that every strip lies inside its field's storage and
+ * that no destination overlaps a source.  n == 0: nothing to do. */
+#define PACE_HALO_XFER_B_FAST 1
+typedef struct {
+  pace_real_t* dst;
+  const pace_real_t* src;
+  int32_t ri0, rj0, na, nb, nk, flags;
+  int32_t i0, j0, di_a, dj_a, di_b, dj_b;
+  double sign;
+} pace_halo_xfer_t;
+int pace_halo_cube(const pace_geom_t* geom, const pace_halo_xfer_t* table_on_device, int n, void* stream);
+
 const char* pace_version(void);
 /* sizeof(pace_real_t) of this build: 8 (libpace_hip.so) or 4 (libpace_hip_f32.so). */
 int pace_real_bytes(void);

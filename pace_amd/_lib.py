@@ -74,6 +74,18 @@ class HaloDesc(C.Structure):
     ]
 
 
+HALO_XFER_B_FAST = 1  # include/pace_hip.h PACE_HALO_XFER_B_FAST
+
+
+class HaloXfer(C.Structure):  # include/pace_hip.h pace_halo_xfer_t
+    _fields_ = [
+        ("dst", c_dp), ("src", c_dp),
+        ("ri0", C.c_int32), ("rj0", C.c_int32), ("na", C.c_int32), ("nb", C.c_int32), ("nk", C.c_int32), ("flags", C.c_int32),
+        ("i0", C.c_int32), ("j0", C.c_int32), ("di_a", C.c_int32), ("dj_a", C.c_int32), ("di_b", C.c_int32), ("dj_b", C.c_int32),
+        ("sign", C.c_double),
+    ]
+
+
 SAT_ADJUST_TABLE_DOUBLES = 4 * 2622  # include/pace_hip.h PACE_SAT_ADJUST_TABLE_DOUBLES
 
 
@@ -268,6 +280,7 @@ _PROTOS = {
                                C.c_void_p]),
     "pace_halo_pack": (C.c_int, [_P(Geom), _P(HaloDesc), C.c_int, C.c_void_p]),
     "pace_halo_unpack": (C.c_int, [_P(Geom), _P(HaloDesc), C.c_int, C.c_void_p]),
+    "pace_halo_cube": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -823,6 +823,13 @@ int pace_halo_unpack(const pace_geom_t* geom, const pace_halo_desc_t* descs, int
   return launch_halo_copy(make_geo(geom), descs, ndesc, 1, S(stream));
 }
 
+int pace_halo_cube(const pace_geom_t* geom, const pace_halo_xfer_t* table_on_device, int n, void* stream) {
+  NEED(geom && n >= 0);
+  if (n == 0) return PACE_OK;
+  if (!table_on_device) return PACE_ERR_ARG;
+  return launch_halo_cube(make_geo(geom), table_on_device, n, S(stream));
+}
+
 int pace_stencil(const pace_geom_t* geom, const pace_metrics_t* met, int id, void* const* fields, int nfields, const double* scalars,
                  int nscalars, const int* origin, const int* domain, void* stream) {
   NEED(geom && met && fields && origin && domain && nfields >= 1 && nfields <= 16 && nscalars >= 0 && (nscalars == 0 || scalars));

@@ -50,3 +50,39 @@ int launch_halo_copy(const Geo& g, const pace_halo_desc_t* descs, int ndesc, int
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }
+
+// The halo update of tiles that share a device (pace_halo_cube): no message, no staging buffer -- a workgroup row reads the
+// sender's field through the strip's affine map and writes the receiver's halo.  One launch for every strip of every field of
+// every tile: blockIdx.y = entry of the table, blockIdx.x = chunk of the strip.  The table lies in device memory (hundreds of
+// entries: no by-value batch holds them); an entry is the same for the whole workgroup, so it is fetched by scalar loads (the
+// pointer is const __restrict__: nothing the kernel writes can alias it) and costs the lanes nothing.
+// Strips are 1..3 points across: the host names the direction of the longer unit-stride run (on either side) and consecutive
+// lanes walk it (PACE_HALO_XFER_B_FAST), so a wave touches runs of whole rows instead of 64 different ones.
+__global__ void __launch_bounds__(256) k_halo_cube(Geo g, const pace_halo_xfer_t* __restrict__ table) {
+  const pace_halo_xfer_t d = table[blockIdx.y];
+  const unsigned total = (unsigned)d.na * (unsigned)d.nb * (unsigned)d.nk;
+  const bool b_fast = (d.flags & PACE_HALO_XFER_B_FAST) != 0;
+  const unsigned nf = (unsigned)(b_fast ? d.nb : d.na), ns = (unsigned)(b_fast ? d.na : d.nb);
+  for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += gridDim.x * 256u) {
+    const unsigned r = e / nf;
+    const int f = (int)(e - r * nf), k = (int)(r / ns), s = (int)(r - (unsigned)k * ns);
+    const int a = b_fast ? s : f, b = b_fast ? f : s;
+    const real v = d.src[IDX3(g, d.i0 + a * d.di_a + b * d.di_b, d.j0 + a * d.dj_a + b * d.dj_b, k)];
+    d.dst[IDX3(g, d.ri0 + a, d.rj0 + b, k)] = (real)(d.sign * v);
+  }
+}
+
+int launch_halo_cube(const Geo& g, const pace_halo_xfer_t* table_on_device, int n, hipStream_t st) {
+  // the largest strip a field of this geometry can hold bounds the 32-bit element counter of the kernel
+  const long most = (long)g.ni * g.nj * (g.nk + 1);
+  if (most >= (1L << 31)) return PACE_ERR_UNSUPPORTED;
+  // chunks for a three-point strip along a whole edge; longer strips take more turns of the kernel's loop
+  long bx = (3L * (g.n + 1) * (g.nk + 1) + 255) / 256;
+  if (bx > 1024) bx = 1024;
+  for (int base = 0; base < n; base += 65535) {  // (gridDim.y)
+    const int rows = n - base < 65535 ? n - base : 65535;
+    hipLaunchKernelGGL(k_halo_cube, dim3((unsigned)bx, (unsigned)rows), dim3(256), 0, st, g, table_on_device + base);
+  }
+  PACE_CHECK_LAUNCH();
+  return PACE_OK;
+}

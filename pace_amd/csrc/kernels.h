@@ -218,6 +218,7 @@ int launch_diffusive_heating(const Geo& g, const real* delp, const real* delz, c
                              const real* heat_source, real* pt, double delt_time_factor, int nlev, hipStream_t st);
 // k_halo.hip
 int launch_halo_copy(const Geo& g, const pace_halo_desc_t* descs, int ndesc, int unpack, hipStream_t st);
+int launch_halo_cube(const Geo& g, const pace_halo_xfer_t* table_on_device, int n, hipStream_t st);
 // k_tracer.hip
 int launch_tracer_flux_compute(const Geo& g, const Met& m, const real* cx, const real* cy, real* xfx, real* yfx,
                                hipStream_t st);

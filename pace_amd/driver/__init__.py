@@ -5,6 +5,7 @@
 from .config import (  # noqa: F401
     BaroclinicInit,
     CreatesCommSelector,
+    CubeCommConfig,
     DriverConfig,
     FortranRestartConfig,
     FortranRestartInit,
@@ -26,6 +27,6 @@ from .diagnostics import (  # noqa: F401
     WindowPacker,
     ZSelect,
 )
-from .driver import Driver  # noqa: F401
+from .driver import Driver, run_cube_driver  # noqa: F401
 from .safety_checks import SafetyChecker, VariableBounds  # noqa: F401
 from .state import DriverState, TendencyState  # noqa: F401

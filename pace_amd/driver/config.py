@@ -10,7 +10,7 @@ What is accepted, refused and ignored:
   grid_config.type      generated (the gnomonic grid of pace_amd.util.gridgen, not stretched; config.restart_path: ak / bk and
                         what derives from them come from <restart_path>/fv_core.res.nc); serialbox: NotImplementedError
   layout                (1, 1)
-  comm_config.type      null (null_comm), torch; mpi, write, read: NotImplementedError.  Absent: null, rank 0 of 6 -- the
+  comm_config.type      null (null_comm), torch, cube (run_cube_driver); mpi, write, read: NotImplementedError.  Absent: null, rank 0 of 6 -- the
                         reference's default is mpi, which does not exist here
   pair_debug            NotImplementedError when true
   restart_config        NotImplementedError when it enables output (save_restart, intermediate_restart): pace's own restart
@@ -296,7 +296,20 @@ class TorchCommConfig:
         pass
 
 
-_COMMS = {"null": NullCommConfig, "null_comm": NullCommConfig, "torch": TorchCommConfig}
+@dataclasses.dataclass
+class CubeCommConfig:
+    """The whole cubed sphere in one process on one device: six Drivers on six tile threads (pace_amd.driver.run_cube_driver,
+    pace_amd.util.run_cube).  No rank of such a run can be made alone, so a lone Driver cannot create its communicator."""
+
+    def get_comm(self):
+        raise ValueError("comm_config.type 'cube' runs six tiles in one process: run the configuration with "
+                         "pace_amd.driver.run_cube_driver(config), which gives every Driver its rank")
+
+    def cleanup(self, comm):
+        pass
+
+
+_COMMS = {"null": NullCommConfig, "null_comm": NullCommConfig, "torch": TorchCommConfig, "cube": CubeCommConfig}
 
 
 @dataclasses.dataclass
@@ -317,7 +330,8 @@ class CreatesCommSelector:
         kind = _selector_type("comm_config", config, ("type", "config"), default="null")
         if kind in ("mpi", "write", "read"):
             raise NotImplementedError(f"comm_config.type {kind!r}: pace_amd.driver communicates through 'torch' (torch.distributed, "
-                                      "one process per tile) or runs one rank alone with 'null'")
+                                      "one process per tile), 'cube' (six tiles in one process on one device) or runs one rank "
+                                      "alone with 'null'")
         if kind not in _COMMS:
             raise ValueError(f"comm_config.type {kind!r} is none of {sorted(_COMMS)}")
         return cls(type=kind, config=_strict(_COMMS[kind], "comm_config.config", dict(config.get("config") or {})))

@@ -204,3 +204,33 @@ class Driver:
         self.diagnostics.store_grid(grid_data=self.state.grid_data)
         self.diagnostics.cleanup()
         self.comm_config.cleanup(self.comm)
+
+
+def run_cube_driver(config: DriverConfig, steps=None, device=None, lib=None, snapshot=False):
+    """Run a configuration as the whole globe on one device (comm_config.type: cube): six Drivers on the six tile threads of
+    pace_amd.util.run_cube, whose halo updates are one kernel launch each for the whole cube.  Every Driver gets a copy of the
+    configuration, runs step_all (`steps` replaces the file's run length) and cleans up, exactly as one of six processes
+    would; diagnostics, the fortran_restart initialisation with verify_checksums and write_fortran_restart work per tile.
+    snapshot: the halo updates keep the reference's contract (a field may be rewritten after start()) at ThreadComm's cost.
+    Returns the six Drivers in tile order."""
+    import copy
+
+    from ..util import run_cube
+
+    if steps is not None:
+        config = copy.deepcopy(config)
+        config.days = config.hours = config.minutes = 0
+        config.seconds = int(round(steps * config.dt_atmos))
+        config.__dict__.pop("total_time", None)  # (a cached property of the run length it had)
+        if config.n_timesteps() != steps:
+            raise ValueError(f"steps={steps} is no whole number of seconds at dt_atmos {config.dt_atmos}")
+        if config.source is not None:
+            config.source.update(days=0, hours=0, minutes=0, seconds=config.seconds)
+
+    def program(comm):
+        driver = Driver(copy.deepcopy(config), comm=comm, lib=lib, device=device)
+        driver.step_all()
+        driver.cleanup()
+        return driver
+
+    return run_cube(program, snapshot=snapshot)

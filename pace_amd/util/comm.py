@@ -10,6 +10,9 @@ over device tensors:
   keeps launching kernels until ``wait``.
 * ``ThreadComm``     -- several tiles inside one process (one Python thread per tile, e.g. all six tiles of a small
   cubed sphere on a single 288 GB device).  A send enqueues a device-side copy; a receive copies it out.
+* ``DeviceCubeComm`` -- ``ThreadComm`` for the whole cubed sphere on one device (``run_cube``): the six ranks of a halo update
+  meet in a rendezvous, and the last one to arrive launches ONE kernel that reads every neighbour's field and writes every
+  halo (``pace_halo_cube``, pace_amd/util/halo.py).  No message, no buffer.
 """
 import threading
 from collections import defaultdict, deque
@@ -147,6 +150,10 @@ class _World:
         self.reduce_generation = 0
         self.reduce_sum = None
         self.reduce_result = None
+        # DeviceCubeComm's rendezvous of the halo updates: (tag, generation) -> {rank: what it posted}, and -> number of ranks
+        # that have still to wait() for a launch that has been issued
+        self.halo_posts = {}
+        self.halo_issued = {}
 
 
 class ThreadComm:
@@ -216,8 +223,62 @@ class ThreadComm:
         return Request(fin)
 
 
+class DeviceCubeComm(ThreadComm):
+    """A rank of the whole cubed sphere on one device.  Everything of ThreadComm is inherited; on top of it the ranks of one
+    halo update (same tag, same generation: the n-th update of that tag on every rank) meet here.  ``snapshot``: the ranks
+    behave exactly as ThreadComm's (pack at start(), buffers, unpack at wait()), which keeps the reference's contract that a
+    field may be rewritten after start()."""
+
+    def __init__(self, world: _World, rank: int, snapshot: bool = False):
+        super().__init__(world, rank)
+        self.snapshot = bool(snapshot)
+        self._halo_generation = defaultdict(int)  # tag -> updates this rank has started under it
+
+    def halo_post(self, tag, payload):
+        """Post this rank's part of the next update under `tag`.  Returns (ticket, posts): posts is None unless this rank is
+        the last of the world to post -- then it is {rank: payload} of all of them, and the caller launches the update and
+        reports it with halo_issue(ticket)."""
+        w = self._world
+        with w.cond:
+            ticket = (tag, self._halo_generation[tag])
+            self._halo_generation[tag] += 1
+            posts = w.halo_posts.setdefault(ticket, {})
+            posts[self._rank] = payload
+            if len(posts) < w.n:
+                return ticket, None
+            del w.halo_posts[ticket]
+            return ticket, posts
+
+    def halo_issue(self, ticket):
+        w = self._world
+        with w.cond:
+            w.halo_issued[ticket] = w.n
+            w.cond.notify_all()
+
+    def halo_wait(self, ticket):
+        """Block (yielding the run token, as ThreadComm._wait does) until the launch of `ticket` has been issued."""
+        w = self._world
+        with w.cond:
+            self._wait(lambda: ticket in w.halo_issued, f"halo update {ticket}")
+            w.halo_issued[ticket] -= 1
+            if w.halo_issued[ticket] == 0:
+                del w.halo_issued[ticket]
+
+
 def run_tiles(n, fn):
     """Run ``fn(comm)`` for n tiles on n threads of this process; returns their results in tile order."""
+    return _run_world(n, fn, ThreadComm)
+
+
+def run_cube(fn, snapshot=False):
+    """Run ``fn(comm)`` for the six tiles of the cubed sphere on six threads of this process, all on the current device, with
+    DeviceCubeComm ranks: a halo update is one kernel launch for the whole cube.  Between start() and wait() of an update a rank
+    must not write the fields it handed over, nor rely on their halos (the data moves when the LAST tile has started); a caller
+    that cannot keep that passes snapshot=True.  Returns the results in tile order."""
+    return _run_world(6, fn, lambda world, r: DeviceCubeComm(world, r, snapshot=snapshot))
+
+
+def _run_world(n, fn, make_comm):
     world = _World(n)
     results, errors = [None] * n, []
     # the current device is a per-thread setting: hand the caller's on to the tile threads (a rank of a multi-GPU run owns
@@ -238,7 +299,7 @@ def run_tiles(n, fn):
             torch.cuda.set_device(device)
         with world.cond:  # the run token (see _World)
             try:
-                results[r] = fn(ThreadComm(world, r))
+                results[r] = fn(make_comm(world, r))
             except BaseException as e:  # noqa: BLE001
                 import traceback
 

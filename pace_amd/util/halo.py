@@ -11,9 +11,15 @@ through mpi4py.  Here every strip is described once, at construction, by an affi
 orientation (derived below by pushing index grids through the same slice-and-rotate steps, then checked to be
 exactly affine); one HIP launch packs every strip of every field of the updater (the rotation happens in the pack),
 one grouped RCCL send/recv moves the four messages, one launch unpacks.  Nothing synchronises the device.
+
+Six tiles that share a device (``DeviceCubeComm``, ``run_cube``) need no message at all: the send strip of one tile and the
+receive strip of its neighbour are the two halves of one table entry, and ONE launch of ``pace_halo_cube`` -- issued by the
+last tile to start the update -- reads every neighbour's field and writes every halo of the cube (the fused path below).
 """
+import collections
 import ctypes as C
 import dataclasses
+import itertools
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -21,6 +27,7 @@ import torch
 
 from .. import _lib
 from . import constants as c
+from .comm import Request
 from .partitioner import EDGES, CubedSpherePartitioner, facing_edge, tile_neighbour
 
 WEST, EAST, NORTH, SOUTH = c.WEST, c.EAST, c.NORTH, c.SOUTH
@@ -191,6 +198,138 @@ class _Messages:
         return self._desc_cache[ptrs]
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the fused path: the whole cube on one device, one launch per update
+# ---------------------------------------------------------------------------------------------------------------
+CUBE_TABLE_CACHE = 8  # device tables kept per updater group: ping-pong storage swaps give a handful of pointer variants
+_serial = itertools.count()
+
+
+def _fused(comm):
+    """Does this transport offer the rendezvous of DeviceCubeComm, and is it not in snapshot mode?"""
+    return hasattr(comm, "halo_post") and not getattr(comm, "snapshot", False)
+
+
+_Post = collections.namedtuple("_Post", "updater ptrs stream")
+
+
+def _xfer_of(dst_ptr, src_ptr, rs, ss):
+    """One table entry from a receive strip and the matching send strip of the peer.  The kernel addresses the destination as
+    (ri0 + a, rj0 + b): a receive strip that runs along j with its index a (the east column of the interface
+    synchronisation) is entered with a and b exchanged."""
+    if (rs.na, rs.nb, rs.nk) != (ss.na, ss.nb, ss.nk):
+        raise ValueError(f"halo strips do not match: receiver {(rs.na, rs.nb, rs.nk)}, sender {(ss.na, ss.nb, ss.nk)}")
+    along_a = (rs.na == 1 or (rs.di_a, rs.dj_a) == (1, 0)) and (rs.nb == 1 or (rs.di_b, rs.dj_b) == (0, 1))
+    across = (rs.na == 1 or (rs.di_a, rs.dj_a) == (0, 1)) and (rs.nb == 1 or (rs.di_b, rs.dj_b) == (1, 0))
+    x = _lib.HaloXfer()
+    x.dst, x.src, x.ri0, x.rj0, x.nk, x.sign = dst_ptr, src_ptr, rs.i0, rs.j0, rs.nk, ss.sign
+    x.i0, x.j0 = ss.i0, ss.j0
+    if along_a:
+        x.na, x.nb = rs.na, rs.nb
+        x.di_a, x.dj_a, x.di_b, x.dj_b = ss.di_a, ss.dj_a, ss.di_b, ss.dj_b
+    elif across:
+        x.na, x.nb = rs.nb, rs.na
+        x.di_a, x.dj_a, x.di_b, x.dj_b = ss.di_b, ss.dj_b, ss.di_a, ss.dj_a
+    else:
+        raise ValueError("a receive strip must be a rectangle of the field's own index space")
+    # lane order: the destination's unit-stride run is along a (na points); the source's is along b where the tiles are
+    # rotated against each other (nb points) -- the longer one goes to consecutive lanes
+    x.flags = _lib.HALO_XFER_B_FAST if (abs(x.di_b) == 1 and x.dj_b == 0 and x.nb > x.na) else 0
+    return x
+
+
+def _src_box(x):
+    i = [x.i0 + a * x.di_a + b * x.di_b for a in (0, x.na - 1) for b in (0, x.nb - 1)]
+    j = [x.j0 + a * x.dj_a + b * x.dj_b for a in (0, x.na - 1) for b in (0, x.nb - 1)]
+    return min(i), max(i), min(j), max(j)
+
+
+def check_cube_table(geom, entries):
+    """The host checks of a pace_halo_cube table, once per table and before any launch: every strip lies inside its field's
+    storage ((n + 7)^2 points, nk + 1 levels), and no destination strip overlaps a source strip of the same field (the kernel
+    reads and writes in one pass: such a table would depend on the order of the workgroups).  Raises ValueError."""
+    ni = geom.n + 7
+    reads = collections.defaultdict(list)
+    for t, x in enumerate(entries):
+        if not x.dst or not x.src or x.na < 1 or x.nb < 1 or x.nk < 1 or x.nk > geom.nk + 1:
+            raise ValueError(f"halo table entry {t}: null field or extents {(x.na, x.nb, x.nk)} outside the storage")
+        i0, i1, j0, j1 = _src_box(x)
+        if min(i0, j0, x.ri0, x.rj0) < 0 or max(i1, j1, x.ri0 + x.na - 1, x.rj0 + x.nb - 1) >= ni:
+            raise ValueError(f"halo table entry {t}: a strip lies outside the field's storage of {ni} x {ni} points")
+        reads[x.src].append((i0, i1, j0, j1, t))
+    for t, x in enumerate(entries):
+        for i0, i1, j0, j1, u in reads.get(x.dst, ()):
+            if x.ri0 <= i1 and i0 <= x.ri0 + x.na - 1 and x.rj0 <= j1 and j0 <= x.rj0 + x.nb - 1:
+                raise ValueError(f"halo table entry {t} writes what entry {u} reads from the same field")
+
+
+def _upload_table(arr, device):
+    """The table on the device: through a pinned staging array on the launch stream (no synchronisation).  Returns the tensors
+    to keep alive with the table (device copy first)."""
+    nbytes = C.sizeof(arr)
+    if device.type == "cpu":
+        dev = torch.empty(nbytes // 8, dtype=torch.int64)  # (an entry is a whole number of 8-byte units)
+        C.memmove(dev.data_ptr(), arr, nbytes)
+        return (dev,)
+    stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    C.memmove(stage.data_ptr(), arr, nbytes)
+    dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    dev.copy_(stage, non_blocking=True)
+    return dev, stage
+
+
+def _build_cube_table(updaters, ptrs):
+    """The whole cube's table: every receive strip of every rank paired with the matching send strip of its peer (the strips of
+    a message are in the same order on both sides, as pack and unpack need them)."""
+    geom = updaters[0]._geom
+    for u in updaters[1:]:
+        if (u._geom.n, u._geom.nk, u._geom.sj, u._geom.sk) != (geom.n, geom.nk, geom.sj, geom.sk):
+            raise ValueError("the tiles of a halo update differ in geometry")
+    entries = []
+    for r, up in enumerate(updaters):
+        for peer, rstrips in up._msgs.recv.items():
+            sstrips = updaters[peer]._msgs.send[r]
+            if len(rstrips) != len(sstrips):
+                raise ValueError(f"tile {r} expects {len(rstrips)} strips from tile {peer}, which sends {len(sstrips)}")
+            entries += [_xfer_of(ptrs[r][rs.field], ptrs[peer][ss.field], rs, ss) for rs, ss in zip(rstrips, sstrips)]
+    check_cube_table(geom, entries)
+    arr = (_lib.HaloXfer * max(len(entries), 1))(*entries)
+    return arr, len(entries)
+
+
+def _launch_cube(cube, posts):
+    """What the last rank to start an update does: the table of this combination of storages (cached on the device), one launch."""
+    order = sorted(posts)
+    updaters = [posts[r].updater for r in order]
+    if len(set(posts[r].stream for r in order)) != 1:
+        raise RuntimeError("the tiles of a fused halo update started it on different streams "
+                           f"({[posts[r].stream for r in order]}): the one launch is ordered behind one stream only")
+    ptrs = tuple(posts[r].ptrs for r in order)
+    key = (tuple(u._serial for u in updaters), ptrs)
+    cache = updaters[0]._cube_tables
+    hit = cache.get(key)
+    if hit is None:
+        arr, n = _build_cube_table(updaters, ptrs)
+        hit = cache[key] = (_upload_table(arr, cube.device), n)
+        if len(cache) > CUBE_TABLE_CACHE:
+            cache.popitem(last=False)
+    else:
+        cache.move_to_end(key)
+    keep, n = hit
+    cube.lib.call("pace_halo_cube", C.byref(updaters[0]._geom), C.c_void_p(keep[0].data_ptr()), n, cube.stream())
+
+
+def _fused_start(updater, ptrs):
+    """Post this rank's fields; the sixth rank to post launches.  Returns the ticket wait() asks for."""
+    cube = updater._cube
+    stream = cube.stream()
+    ticket, posts = cube.comm.halo_post(updater._tag, _Post(updater, ptrs, stream.value if stream is not None else None))
+    if posts is not None:
+        _launch_cube(cube, posts)
+        cube.comm.halo_issue(ticket)
+    return ticket
+
+
 class HaloUpdater:
     """halo_updater.py:29-303.  Built once per group of fields, reused every substep."""
 
@@ -199,6 +338,8 @@ class HaloUpdater:
         self._cube = communicator
         self._tag = tag
         self._inflight = None
+        self._serial = next(_serial)
+        self._cube_tables = collections.OrderedDict()  # (the fused path: rank 0's updater holds the group's device tables)
         specs_x, specs_y = list(specs_x), list(specs_y or [])
         vector = len(specs_y) > 0
         if vector and len(specs_x) != len(specs_y):
@@ -262,8 +403,12 @@ class HaloUpdater:
         if len(qs) != self._n_x + self._n_y:
             raise ValueError(f"updater was built for {self._n_x}+{self._n_y} quantities, got {len(qs)}")
         ptrs = tuple(q.ptr for q in qs)
-        pack, npack, unpack, nunpack = self._msgs.descriptors(ptrs)
         cube = self._cube
+        if _fused(cube.comm):  # nothing is launched here unless this is the last tile to start
+            ticket = _fused_start(self, ptrs)
+            self._inflight = (Request(lambda: cube.comm.halo_wait(ticket)), None, 0, [(q, getattr(q, "generation", 0)) for q in qs])
+            return
+        pack, npack, unpack, nunpack = self._msgs.descriptors(ptrs)
         cube.lib.call("pace_halo_pack", C.byref(self._geom), pack, npack, cube.stream())
         req = cube.comm.exchange([(b, p) for p, b in self._msgs.sendbuf.items()], [(b, p) for p, b in self._msgs.recvbuf.items()],
                                  tag=self._tag)
@@ -278,7 +423,8 @@ class HaloUpdater:
                 raise RuntimeError("the storage of a Quantity was swapped (Quantity.swap_storage) between start() and wait() of its "
                                    "halo update: the received halo would be written to the buffer it no longer owns")
         req.wait()
-        self._cube.lib.call("pace_halo_unpack", C.byref(self._geom), unpack, nunpack, self._cube.stream())
+        if unpack is not None:  # (the fused path: the launch that req waited for has written the halos)
+            self._cube.lib.call("pace_halo_unpack", C.byref(self._geom), unpack, nunpack, self._cube.stream())
         self._inflight = None
 
     def update(self, quantities_x: List, quantities_y: Optional[List] = None):
@@ -317,9 +463,14 @@ class VectorInterfaceHaloUpdater:
         msgs.recv[from_e].append(_Strip(1, o + n, o, 0, 1, 0, 0, n, 1, nk, 1.0))
         msgs.finalize()
         self._msgs = msgs
+        self._serial = next(_serial)
+        self._cube_tables = collections.OrderedDict()
 
     def update(self, x_quantity, y_quantity):
         cube = self._cube
+        if _fused(cube.comm):
+            cube.comm.halo_wait(_fused_start(self, (x_quantity.ptr, y_quantity.ptr)))
+            return
         pack, npack, unpack, nunpack = self._msgs.descriptors((x_quantity.ptr, y_quantity.ptr))
         cube.lib.call("pace_halo_pack", C.byref(self._geom), pack, npack, cube.stream())
         req = cube.comm.exchange([(b, p) for p, b in self._msgs.sendbuf.items()], [(b, p) for p, b in self._msgs.recvbuf.items()],

@@ -1,7 +1,7 @@
 """Run the model from one of the reference's driver configuration files: pace_amd.driver.Driver, its step_all, one JSON line.
 
     python tools/driver_run.py CONFIG.yaml [--steps N] [--device D] [--cpu-emulation] [--diagnostics DIR]
-                               [--write-fortran-restart DIR]
+                               [--write-fortran-restart DIR] [--cube]
 
 runs ONE rank (tile 0) with the `null` communicator -- its halos receive zeros, so this exercises the loop, not the weather --
 and, launched under torch.distributed.run as tools/dycore_run.py is,
@@ -9,7 +9,10 @@ and, launched under torch.distributed.run as tools/dycore_run.py is,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 6 --master-addr 127.0.0.1 --master-port 29511 \\
         tools/driver_run.py CONFIG.yaml [--steps N] [--cpu-emulation]
 
-the six tiles of the cubed sphere, one process per tile (RCCL on GPUs, gloo with --cpu-emulation).  --steps replaces the
+the six tiles of the cubed sphere, one process per tile (RCCL on GPUs, gloo with --cpu-emulation).  A lone process whose file
+says `comm_config: {type: cube}`, or which is given --cube, runs the six tiles itself on ONE device
+(pace_amd.driver.run_cube_driver: every halo update is one kernel launch for the whole cube) and prints the same line.
+--steps replaces the
 file's run length.  --diagnostics DIR writes the file's diagnostics into DIR as per-tile numpy archives (it replaces
 diagnostics_config.path and sets output_format: npz; pace_amd.driver.NpzMonitor describes the files).
 --write-fortran-restart DIR writes the final state into DIR as restart files of the Fortran model (Driver.write_fortran_restart)
@@ -19,6 +22,7 @@ with a restart.yaml, from which `python tools/driver_run.py DIR/restart.yaml` re
 tile behind zero halos need not stay within the bounds).
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -40,6 +44,7 @@ def main():
                     help="write the file's diagnostics into DIR (diagnostics_config.path = DIR, output_format = npz)")
     ap.add_argument("--write-fortran-restart", metavar="DIR", default=None,
                     help="write the final state into DIR in the Fortran model's restart format, with a restart.yaml that resumes from it")
+    ap.add_argument("--cube", action="store_true", help="a lone process: run all six tiles on the one device (comm_config.type: cube)")
     args = ap.parse_args()
     import yaml
 
@@ -50,7 +55,13 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     with open(args.config) as f:
         settings = yaml.safe_load(f)
-    if world == 1:
+    cube = world == 1 and (args.cube or (settings.get("comm_config") or {}).get("type") == "cube")
+    if args.cube and world != 1:
+        raise SystemExit("--cube runs the six tiles in ONE process: start it without a launcher")
+    if cube:
+        settings["comm_config"] = {"type": "cube"}
+        device = "cpu" if args.cpu_emulation else (args.device or "cuda:0")
+    elif world == 1:
         settings["comm_config"] = {"type": "null", "config": {"rank": 0, "total_ranks": 6}}
         device = "cpu" if args.cpu_emulation else (args.device or "cuda:0")
     elif world == 6:
@@ -79,15 +90,31 @@ def main():
             raise SystemExit(f"--steps {args.steps} is no whole number of seconds at dt_atmos {config.dt_atmos}")
         config.source["seconds"] = config.seconds  # (a restart.yaml of this run runs as long as this run)
     lib = _lib.Library(os.path.join(ROOT, "tests", "emu", "libpace_emu.so")) if args.cpu_emulation else _lib.load()
-    driver = Driver(config, lib=lib, device=device)
-    driver.step_all()
-    if args.write_fortran_restart is not None:
-        driver.write_fortran_restart(args.write_fortran_restart)
+    if cube:
+        from pace_amd.util import run_cube
+
+        def tile(comm):  # (run_cube_driver's program, with the restart written before the clean-up)
+            d = Driver(copy.deepcopy(config), comm=comm, lib=lib, device=device)
+            d.step_all()
+            if args.write_fortran_restart is not None:
+                d.write_fortran_restart(args.write_fortran_restart)
+            d.cleanup()
+            return d
+
+        drivers = run_cube(tile)
+        driver = drivers[0]
+    else:
+        drivers = [Driver(config, lib=lib, device=device)]
+        driver = drivers[0]
+        driver.step_all()
+        if args.write_fortran_restart is not None:
+            driver.write_fortran_restart(args.write_fortran_restart)
     if device != "cpu":
         torch.cuda.synchronize()
     steps = config.n_timesteps()
     loop, total = driver.performance_collector.timestep_timer, driver.performance_collector.total_timer
-    ms_per_step = 1e3 * loop.times.get("mainloop", 0.0) / max(1, loop.hits.get("mainloop", 0))
+    ms_per_step = max(1e3 * d.performance_collector.timestep_timer.times.get("mainloop", 0.0)
+                      / max(1, d.performance_collector.timestep_timer.hits.get("mainloop", 0)) for d in drivers)
     checks = total.hits.get("safety_check", 0)
     verdict, check_times = "within bounds", []
     for _ in range(3):
@@ -99,6 +126,8 @@ def main():
         check_times.append(1e3 * (time.perf_counter() - t0))
     check_ms = sorted(check_times)[1]
     sypd = driver.sypd()
+    if cube:
+        sypd = config.dt_atmos / (ms_per_step * 1e-3) / 365.0 if ms_per_step > 0 else sypd
     if world == 6:
         t = torch.tensor([ms_per_step], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -110,12 +139,14 @@ def main():
         print(json.dumps({
             "workload": f"Driver.step_all, C{config.nx_tile}x{config.nz}L, {what}, n_split={config.dycore_config.n_split}, "
                         f"k_split={config.dycore_config.k_split}, dt_atmos={config.dt_atmos:g} s, "
-                        + ("six tiles, one process per tile" if world == 6 else "ONE tile, null communicator (zero halos)"),
+                        + ("six tiles, one process per tile" if world == 6 else
+                           "six tiles in one process on one device" if cube else "ONE tile, null communicator (zero halos)"),
             "n_gpus": 0 if args.cpu_emulation else world, "steps": steps, "ms_per_step": ms_per_step, "sypd": sypd,
             "safety_checks_in_loop": checks, "safety_check_ms_per_call": check_ms, "safety_check": verdict,
             "nan_fraction_pt": float((pt != pt).mean()),
-            "transport": "CPU emulation" if args.cpu_emulation else ("RCCL" if world == 6 else "none")}))
-    driver.cleanup()
+            "transport": "CPU emulation" if args.cpu_emulation else ("RCCL" if world == 6 else "pace_halo_cube" if cube else "none")}))
+    if not cube:
+        driver.cleanup()
     if world == 6:
         dist.barrier()
         dist.destroy_process_group()

@@ -56,6 +56,9 @@ def main():
                     help="fv_sg_adj = 600: the reference driver's end of a dycore-only step runs after each step -- DycoreToPhysics (the "
                          "dry convective adjustment, reported as dry_conv_adjust), then UpdateAtmosphereState (fill_gfs_delp and "
                          "ApplyPhysicsToDycore with its halo updates, reported as update_atmos_state)")
+    ap.add_argument("--comm", default="thread", choices=("thread", "cube"),
+                    help="six tiles: ThreadComm (pack, device-side copies, unpack per tile) or DeviceCubeComm (run_cube: one "
+                         "pace_halo_cube launch per halo update for the whole cube)")
     args = ap.parse_args()
     if os.environ.get("PACE_BENCH_TRACE"):
         import faulthandler
@@ -67,7 +70,7 @@ def main():
     from pace_amd.fv3core import DynamicalCoreConfig
     from pace_amd.fv3core.initialization.dycore_state import DycoreState
     from pace_amd.fv3core.stencils.fv_dynamics import DynamicalCore
-    from pace_amd.util import CubedSphereCommunicator, LoopbackComm, constants as c, run_tiles
+    from pace_amd.util import CubedSphereCommunicator, LoopbackComm, constants as c, run_cube, run_tiles
 
     lib = _lib.load(args.precision)
     n, nz = args.n, args.nz
@@ -143,10 +146,10 @@ def main():
         print(f"wall per step: {1e3 * wall:9.2f} ms   ({cells * args.n_split / wall / 1e9:5.2f} G cell-updates/s counting the "
               f"acoustic substeps; the timers synchronise the device at every section boundary)")
     else:
-        run_tiles(6, program)
+        run_cube(program) if args.comm == "cube" else run_tiles(6, program)
         wall = max(r[0] for r in results.values()) / args.steps
         cells = 6 * n * n * nz
-        print(f"C{n} x {nz}L, six tiles on one device, n_split = {args.n_split}, k_split = 1, do_sat_adj = {args.sat_adj}, "
+        print(f"C{n} x {nz}L, six tiles on one device (--comm {args.comm}), n_split = {args.n_split}, k_split = 1, do_sat_adj = {args.sat_adj}, "
               f"{args.steps} steps")
         print(f"wall per step (six tiles): {1e3 * wall:9.2f} ms   = {1e3 * wall / 6:7.2f} ms per tile   "
               f"({cells * args.n_split / wall / 1e9:5.2f} G cell-updates/s counting the acoustic substeps)")

@@ -5,7 +5,7 @@ util/pace/util/halo_updater.py:217-303) is timed on the host -- CPU time of the 
 the other five threads holding the interpreter) and wall time -- per updater, next to the wall time of the loop body.
 What this does NOT show: the host cost of RCCL's grouped send / receive (TorchDistComm.exchange), which needs one process per GPU.
 
-    python tools/halo_host_cost.py [--n 96] [--n_split 4]
+    python tools/halo_host_cost.py [--n 96] [--n_split 4] [--comm {thread,cube}]
 """
 import argparse
 import collections
@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--n", type=int, default=96)
     ap.add_argument("--nz", type=int, default=79)
     ap.add_argument("--n_split", type=int, default=4)
+    ap.add_argument("--comm", default="thread", choices=("thread", "cube"),
+                    help="ThreadComm (pack, copies, unpack per tile) or DeviceCubeComm (one pace_halo_cube launch per update for the cube)")
     a = ap.parse_args()
     import torch
 
@@ -32,7 +34,7 @@ def main():
     from pace_amd import _lib
     from pace_amd.fv3core.initialization.dycore_state import DycoreState
     from pace_amd.fv3core.stencils.dyn_core import AcousticDynamics
-    from pace_amd.util import CubedSphereCommunicator, run_tiles
+    from pace_amd.util import CubedSphereCommunicator, run_cube, run_tiles
     from pace_amd.util import halo as halo_mod
 
     lib = _lib.load()
@@ -90,9 +92,9 @@ def main():
         walls[rank] = time.perf_counter() - t0
         return None
 
-    run_tiles(6, tile)
+    run_cube(tile) if a.comm == "cube" else run_tiles(6, tile)
     wall = max(walls.values())
-    print(f"C{n} x {nz}, six tiles on one device, n_split = {n_split}: loop body {1e3 * wall / n_split:.3f} ms wall per substep (six tiles sharing the device)")
+    print(f"C{n} x {nz}, six tiles on one device (--comm {a.comm}), n_split = {n_split}: loop body {1e3 * wall / n_split:.3f} ms wall per substep (six tiles sharing the device)")
     print(f"{'updater':22s} {'calls':>6s} {'start cpu us':>13s} {'start wall us':>14s} {'wait cpu us':>12s} {'wait wall us':>13s}")
     tot_cpu = 0.0
     for k in sorted({k for k, _ in acc}):

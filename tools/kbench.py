@@ -13,6 +13,10 @@
     python tools/kbench.py --only restart_pack      write_restart of a state's fifteen 3-D fields and three planes (launch,
                                                     device-to-host copy, file writes) against a torch / numpy restatement, the
                                                     same way, with the split into launch, transfer and write
+    python tools/kbench.py --only halo_cube         the seven halo-updater groups of an acoustic substep for six tiles on this
+                                                    device: the fused path (run_cube: one pace_halo_cube launch per update for
+                                                    the whole cube) against the snapshot path (ThreadComm's pack, copies,
+                                                    unpack), alternating, medians, with the library calls per update
 """
 import argparse
 import os
@@ -53,6 +57,9 @@ def main():
         return
     if args.only == "restart_pack":  # (its own fields)
         restart_pack_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "halo_cube":  # (its own fields, six tiles)
+        halo_cube_bench(lib, n, nz, args.reps)
         return
     if args.only == "checkpointer":  # (its own fields)
         checkpointer_bench(lib, n, nz, args.reps)
@@ -616,6 +623,91 @@ def restart_pack_bench(lib, n, nz, reps):
         print(f"  ratio torch / hip {ref / hip:.2f}")
     finally:
         shutil.rmtree(base, ignore_errors=True)
+
+
+def halo_cube_bench(lib, n, nz, reps, rounds=3):
+    """The updater groups of one acoustic substep (dyn_core.py: w, divgd, uc / vc, delp / pt / q_con, zh, pkc, u / v) on six
+    tiles of this device, every tile updating all seven one after the other.  Host clock of tile 0 around `reps` such
+    sequences, the device drained at both ends, so the time holds the launches AND the copies; the fused and the snapshot
+    path alternate `rounds` times and the medians over all sequences are reported, with the library calls and tensor copies
+    counted on one sequence."""
+    import collections
+    import time
+
+    from pace_amd.util import CubedSphereCommunicator, QuantityFactory, SubtileGridSizer, run_cube
+    from pace_amd.util import comm as comm_mod
+
+    X, Y, Z, XI, YI, ZI = "x", "y", "z", "x_interface", "y_interface", "z_interface"
+    groups = (("w", [[X, Y, Z]], None, 3), ("divgd", [[XI, YI, Z]], None, 3), ("uc__vc", [[XI, Y, Z]], [[X, YI, Z]], 3),
+              ("delp__pt__q_con", [[X, Y, Z]] * 3, None, 3), ("zh", [[X, Y, ZI]], None, 3), ("pkc", [[X, Y, ZI]], None, 2),
+              ("u__v", [[X, YI, Z]], [[XI, Y, Z]], 3))
+    calls = collections.Counter()
+    real_call = type(lib).call
+
+    class Counting:
+        def __getattr__(self, name):
+            return getattr(lib, name)
+
+        def call(self, name, *a):
+            calls[name] += 1
+            return real_call(lib, name, *a)
+
+    counting = Counting()
+    times = {False: [], True: []}
+    counted = {}
+
+    def program(snapshot):
+        def run(comm):
+            sizer = SubtileGridSizer.from_tile_params(nx_tile=n, ny_tile=n, nz=nz, n_halo=3, extra_dim_lengths={}, layout=(1, 1))
+            qf = QuantityFactory(sizer, device="cuda", dtype=torch.float32 if lib.real_bytes == 4 else torch.float64)
+            cube = CubedSphereCommunicator(comm, device="cuda", lib=counting)
+            work = []
+            for _, dx, dy, pts in groups:
+                xs, ys = [qf.ones(d, "") for d in dx], [qf.ones(d, "") for d in (dy or [])]
+                sx = [qf.get_quantity_halo_spec(d, n_halo=pts) for d in dx]
+                if dy is None:
+                    work.append((cube.get_scalar_halo_updater(sx), xs, None))
+                else:
+                    work.append((cube.get_vector_halo_updater(sx, [qf.get_quantity_halo_spec(d, n_halo=pts) for d in dy]), xs, ys))
+
+            def sequence():
+                for up, xs, ys in work:
+                    up.update(xs, ys)
+
+            sequence()  # warm-up: tables built and uploaded
+            torch.cuda.synchronize()
+            comm.barrier()
+            if comm.Get_rank() == 0:
+                calls.clear()
+            comm.barrier()
+            sequence()
+            comm.barrier()
+            if comm.Get_rank() == 0:
+                counted[snapshot] = dict(calls)
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                comm.barrier()
+                t0 = time.perf_counter()
+                sequence()
+                comm.barrier()
+                torch.cuda.synchronize()
+                if comm.Get_rank() == 0:
+                    times[snapshot].append(time.perf_counter() - t0)
+        return run
+
+    for _ in range(rounds):
+        for snapshot in (False, True):
+            run_cube(program(snapshot), snapshot=snapshot)
+    nup = len(groups)
+    print(f"halo updates of one acoustic substep, six C{n} x {nz} tiles on one device, {nup} updater groups, "
+          f"{rounds} x {reps} sequences per path, alternating; host clock, device drained")
+    for snapshot, label in ((False, "fused (pace_halo_cube)"), (True, "snapshot (ThreadComm) ")):
+        t = np.array(times[snapshot]) * 1e6
+        per = {k: v / nup for k, v in counted[snapshot].items()}
+        copies = "" if not snapshot else "  + clone / copy_ per message: 24 + 24 per update"
+        print(f"  {label}: median {np.median(t) / nup:8.1f} us per update of the whole cube (min {t.min() / nup:8.1f}, max {t.max() / nup:8.1f}); "
+              f"library calls per update: {per}{copies}")
+    print(f"  ratio snapshot / fused: {np.median(times[True]) / np.median(times[False]):.2f}")
 
 
 def checkpointer_bench(lib, n, nz, reps):
