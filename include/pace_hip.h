@@ -819,6 +819,36 @@ typedef struct {
 } pace_halo_xfer_t;
 int pace_halo_cube(const pace_geom_t* geom, const pace_halo_xfer_t* table_on_device, int n, void* stream);
 
+/* ---- Gather and scatter across the cube (util/pace/util/communicator.py:111-329): windows of any number of fields of any of the
+ * six tiles' storages of one geometry, moved between the fields and ONE dense device buffer by ONE launch, both storage types,
+ * no atomics, no workspace, no host synchronisation.  The dense side of an item is (x, y, z) in C order, z fastest, at
+ * dense + offset (the axis order of the reference's arrays and of pace_diag_pack); dense_type names its element type.
+ *   pace_cube_gather    dense[offset + (i * nj + j) * nk + k] = (dense type) field(i0 + i, j0 + j, k0 + k)
+ *   pace_cube_scatter   field(i0 + i, j0 + j, k0 + k) = (pace_real_t) dense[offset + (i * nj + j) * nk + k]
+ * and for a PACE_DIAG_PLANE item the same with k0 = 0, nk = 1; its field points at element (0, 0) of a 2-D field or of ONE level
+ * of a 3-D one.  The conversion is a plain cast (round to nearest even, overflow to +-inf); where the types agree (the float64
+ * library with PACE_DENSE_F64, the float32 library with PACE_DENSE_F32) bits move unchanged: -0.0, NaN payloads, denormals.
+ * Nothing outside a window is read or written on the field side, nothing outside an item's ni * nj * nk elements on the dense side.
+ * table_on_device is DEVICE memory, read in place: n items, and right behind them int32_t first[n + 1], the prefix sums of the
+ * items' tile counts (first[0] = 0, first[n] = all tiles), where an item has
+ *   ceil(ni / 64) * ceil(nk / 32) * nj tiles (WINDOW3D),   ceil(ni / 64) * ceil(nj / 32) tiles (PLANE).
+ * The entry point refuses only what it can see -- n < 1 or n > PACE_CUBE_MAX_ITEMS, an unknown dense_type, a NULL pointer
+ * (PACE_ERR_ARG).  The entries cannot be checked here: whoever builds the table guarantees that every window is non-empty and
+ * inside the storage (n + 7, n + 7, nk + 1), that no field is NULL, no offset negative, that the prefix table is the one above and
+ * first[n] < 2^31, and for scatter that no two items overlap on one field (pace_amd/util/gather.py check_cube_items). */
+#define PACE_CUBE_MAX_ITEMS 4096
+enum { PACE_DENSE_F64 = 0, PACE_DENSE_F32 = 1 };
+typedef struct {            /* one window of one field of one tile */
+  void*   field;            /* element (0,0,0) of the storage (2-D field or one level's plane for a PLANE item) */
+  int32_t kind;             /* PACE_DIAG_WINDOW3D | PACE_DIAG_PLANE */
+  int32_t i0, j0, k0, ni, nj, nk;
+  int64_t offset;           /* in elements of the dense buffer */
+} pace_cube_item_t;
+int pace_cube_gather(const pace_geom_t* geom, const pace_cube_item_t* table_on_device, int n, int dense_type, void* dense,
+                     void* stream);
+int pace_cube_scatter(const pace_geom_t* geom, const pace_cube_item_t* table_on_device, int n, int dense_type, const void* dense,
+                      void* stream);
+
 const char* pace_version(void);
 /* sizeof(pace_real_t) of this build: 8 (libpace_hip.so) or 4 (libpace_hip_f32.so). */
 int pace_real_bytes(void);

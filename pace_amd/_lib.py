@@ -149,6 +149,15 @@ class UnpackItem(C.Structure):  # include/pace_hip.h pace_unpack_item_t
                 ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("in_step", C.c_int32), ("in_offset", C.c_int64)]
 
 
+CUBE_MAX_ITEMS = 4096  # include/pace_hip.h PACE_CUBE_MAX_ITEMS
+DENSE_F64, DENSE_F32 = 0, 1  # include/pace_hip.h PACE_DENSE_*
+
+
+class CubeItem(C.Structure):  # include/pace_hip.h pace_cube_item_t
+    _fields_ = [("field", c_dp), ("kind", C.c_int32), ("i0", C.c_int32), ("j0", C.c_int32), ("k0", C.c_int32),
+                ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("offset", C.c_int64)]
+
+
 RESTART_MAX_ITEMS = 32  # include/pace_hip.h PACE_RESTART_MAX_ITEMS
 RESTART_BE_F64, RESTART_BE_F32 = 0, 1  # include/pace_hip.h PACE_RESTART_*
 
@@ -281,6 +290,8 @@ _PROTOS = {
     "pace_halo_pack": (C.c_int, [_P(Geom), _P(HaloDesc), C.c_int, C.c_void_p]),
     "pace_halo_unpack": (C.c_int, [_P(Geom), _P(HaloDesc), C.c_int, C.c_void_p]),
     "pace_halo_cube": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_void_p]),
+    "pace_cube_gather": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pace_cube_scatter": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -830,6 +830,24 @@ int pace_halo_cube(const pace_geom_t* geom, const pace_halo_xfer_t* table_on_dev
   return launch_halo_cube(make_geo(geom), table_on_device, n, S(stream));
 }
 
+static int cube_xfer(const pace_geom_t* geom, const pace_cube_item_t* table_on_device, int n, int dense_type, void* dense, int scatter,
+                     void* stream) {
+  NEED(geom && table_on_device && dense);
+  if (n < 1 || n > PACE_CUBE_MAX_ITEMS) return PACE_ERR_ARG;
+  if (dense_type != PACE_DENSE_F64 && dense_type != PACE_DENSE_F32) return PACE_ERR_ARG;
+  return launch_cube_xfer(make_geo(geom), table_on_device, n, dense_type == PACE_DENSE_F64, dense, scatter, S(stream));
+}
+
+int pace_cube_gather(const pace_geom_t* geom, const pace_cube_item_t* table_on_device, int n, int dense_type, void* dense,
+                     void* stream) {
+  return cube_xfer(geom, table_on_device, n, dense_type, dense, 0, stream);
+}
+
+int pace_cube_scatter(const pace_geom_t* geom, const pace_cube_item_t* table_on_device, int n, int dense_type, const void* dense,
+                      void* stream) {
+  return cube_xfer(geom, table_on_device, n, dense_type, (void*)dense, 1, stream);
+}
+
 int pace_stencil(const pace_geom_t* geom, const pace_metrics_t* met, int id, void* const* fields, int nfields, const double* scalars,
                  int nscalars, const int* origin, const int* domain, void* stream) {
   NEED(geom && met && fields && origin && domain && nfields >= 1 && nfields <= 16 && nscalars >= 0 && (nscalars == 0 || scalars));

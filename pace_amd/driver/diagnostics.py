@@ -9,7 +9,14 @@ synchronisation of the stream.  The monitor gets host-resident Quantities that a
 (NpzMonitor: a memcpy into its time-chunk arrays), and they are overwritten by the next store.
 
 Files are written by NpzMonitor, the reference's NetCDFMonitor without its file format (neither xarray, zarr nor netCDF4 is
-required): `output_format: npz` is this project's extension.  With `zarr` and `netcdf` nothing is written, as before.
+required): `output_format: npz` is this project's extension.
+
+Where one communicator holds the whole cubed sphere (`comm_config.type: cube`, run_cube_driver: DeviceCubeComm ranks) the globe
+is written as a whole: a store is ONE pace_cube_gather launch for all six tiles and every requested variable
+(CubedSphereCommunicator.gather_state) and one transfer, the column integrals still go through each rank's pace_diag_pack and
+are joined on the host, and rank 0 alone writes -- one file per time chunk with a tile axis of 6, as npz (NpzMonitor) or as
+NetCDF-3 (`output_format: netcdf`, pace_amd.util.NetCDFMonitor).  Per-rank communicators (one process per tile, a lone tile)
+keep their per-tile npz files with a tile axis of 1, and `netcdf` writes nothing there; `zarr` writes nothing anywhere.
 """
 import abc
 import ctypes as C
@@ -103,6 +110,10 @@ class DiagnosticsConfig:
     def writes_files(self) -> bool:
         return self.path is not None and self.output_format == "npz"
 
+    def writes_files_for(self, communicator) -> bool:
+        """... with this communicator: `netcdf` is written where the communicator holds the whole cube."""
+        return self.writes_files or (self.path is not None and self.output_format == "netcdf" and whole_cube(communicator))
+
     def diagnostics_factory(self, communicator, lib=None) -> Diagnostics:
         """
         Create a diagnostics object.
@@ -112,13 +123,18 @@ class DiagnosticsConfig:
                 files; nothing is gathered)
             lib: the kernel library the state's fields belong to (default: the product library)
         """
-        if not self.writes_files:
+        if not self.writes_files_for(communicator):
             return NullDiagnostics()
         os.makedirs(self.path, exist_ok=True)
-        monitor = NpzMonitor(self.path, tile=communicator.partitioner.tile_index(communicator.rank),
-                             time_chunk_size=self.time_chunk_size)
+        if self.output_format == "netcdf":
+            from ..util.monitor import NetCDFMonitor
+
+            monitor = NetCDFMonitor(self.path, communicator, time_chunk_size=self.time_chunk_size)
+        else:
+            monitor = NpzMonitor(self.path, tile=communicator.partitioner.tile_index(communicator.rank),
+                                 time_chunk_size=self.time_chunk_size)
         return MonitorDiagnostics(monitor=monitor, names=self.names, derived_names=self.derived_names, z_select=self.z_select,
-                                  lib=lib)
+                                  lib=lib, communicator=communicator if whole_cube(communicator) else None)
 
     @classmethod
     def from_dict(cls, config) -> "DiagnosticsConfig":
@@ -129,6 +145,11 @@ class DiagnosticsConfig:
         out = _strict(cls, "diagnostics_config", dict(config or {}))
         out.z_select = [z if isinstance(z, ZSelect) else _strict(ZSelect, "diagnostics_config.z_select", z) for z in out.z_select]
         return out
+
+
+def whole_cube(communicator) -> bool:
+    """Does this communicator's transport hold all six tiles on one device (DeviceCubeComm: run_cube, run_cube_driver)?"""
+    return hasattr(getattr(communicator, "comm", None), "halo_post")
 
 
 class NullDiagnostics(Diagnostics):
@@ -248,7 +269,7 @@ class WindowPacker:
 class MonitorDiagnostics(Diagnostics, WindowPacker):
     """Diagnostics that save to a sympl-style Monitor."""
 
-    def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None):
+    def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None, communicator=None):
         """
         Args:
             monitor: a sympl-style Monitor object
@@ -256,7 +277,10 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
             derived_names: list of names of derived diagnostics to save
             z_select: the levels to save of variables of the dycore state
             lib: the library the state's fields belong to (default: the product library, loaded at the first store)
+            communicator: a communicator that holds the whole cube (run_cube): every store is gathered over it and only its
+                root hands the monitor anything -- quantities that lead with TILE_DIM.  None: this rank's tile alone
         """
+        self.communicator = communicator
         self.names = names
         self.derived_names = derived_names
         self.z_select = z_select
@@ -305,9 +329,41 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
         return requests
 
     # ---- the reference's interface ------------------------------------------------------------------------------------------------
+    def _gather(self, requests, packed, transfer_type):
+        """The whole cube's arrays of a step, in the requests' order: the windows and planes by ONE pace_cube_gather launch and
+        one transfer for all six tiles (gather_state), the column integrals -- which every rank has packed itself: `packed` --
+        stacked on the host.  {name: Quantity leading with TILE_DIM} on the root, None elsewhere."""
+        from ..util.gather import Window
+
+        cube = self.communicator
+        windows = {r.name: Window(r.field, r.kind, r.level, r.window, r.dims, r.units) for r in requests
+                   if r.kind != _lib.DIAG_COLUMN_INTEGRAL}
+        gathered = cube.gather_state(windows, transfer_type=transfer_type) if windows else ({} if cube.rank == c.ROOT_RANK else None)
+        mine = {name: q.data.numpy().copy() for name, q in packed.items()}
+        if mine:
+            stacked = cube.comm.rendezvous(("diagnostics", "columns"), mine,
+                                           lambda posts: {name: np.stack([posts[r][name] for r in sorted(posts)]) for name in mine})
+        if gathered is None:
+            return None
+        out = {}
+        for r in requests:
+            if r.name in gathered:
+                out[r.name] = gathered[r.name]
+            else:
+                out[r.name] = Quantity(stacked[r.name], dims=(c.TILE_DIM,) + r.dims, units=r.units)
+        return out
+
     def store(self, time: Union[datetime, timedelta], state):
         monitor_state = {"time": time}
-        monitor_state.update(self.pack(self._requests(state)))
+        requests = self._requests(state)
+        if self.communicator is None:
+            monitor_state.update(self.pack(requests))
+        else:
+            columns = self.pack([r for r in requests if r.kind == _lib.DIAG_COLUMN_INTEGRAL])
+            gathered = self._gather(requests, columns, np.float32)
+            if gathered is None:
+                return
+            monitor_state.update(gathered)
         self.monitor.store(monitor_state)
 
     def store_grid(self, grid_data):
@@ -317,6 +373,9 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
                 "lon_agrid": (c.X_DIM, c.Y_DIM), "lat_agrid": (c.X_DIM, c.Y_DIM)}
         names = ("lat", "lon", "lon_agrid", "lat_agrid")
         values = {name: getattr(grid_data, name) for name in names}
+        if self.communicator is not None:
+            self._store_grid_of_the_cube(names, values, dims)
+            return
         packed = self.pack([self._whole(name, v) for name, v in values.items() if hasattr(v, "dims")], out_is_double=True)
         for name in names:
             if name in packed:
@@ -328,8 +387,33 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
             data = torch.from_numpy(np.ascontiguousarray(a[cut, cut]))
             self.monitor.store_constant({name: Quantity(data, dims=dims[name], units="radians")})
 
+    def _store_grid_of_the_cube(self, names, values, dims):
+        """The same four constants of all six tiles, gathered to the root as the reference's NetCDFMonitor gathers them: device
+        Quantities by one pace_cube_gather launch, what GridData keeps on the host by stacking the ranks' cuts."""
+        cube = self.communicator
+        on_device = [self._whole(name, v) for name, v in values.items() if hasattr(v, "dims")]
+        gathered = self._gather(on_device, {}, np.float64) if on_device else None
+        cuts = {}
+        for name in names:
+            if not hasattr(values[name], "dims"):
+                a = np.asarray(values[name], dtype=np.float64)
+                n, extra = a.shape[0] - 2 * c.N_HALO_DEFAULT - 1, int(dims[name][0] == c.X_INTERFACE_DIM)
+                cut = slice(c.N_HALO_DEFAULT, c.N_HALO_DEFAULT + n + extra)
+                cuts[name] = a[cut, cut]
+        if cuts:
+            stacked = cube.comm.rendezvous(("diagnostics", "grid"), cuts,
+                                           lambda posts: {name: np.stack([posts[r][name] for r in sorted(posts)]) for name in cuts})
+        if cube.rank != c.ROOT_RANK:
+            return
+        for name in names:
+            if name in cuts:
+                self.monitor.store_constant({name: Quantity(stacked[name], dims=(c.TILE_DIM,) + dims[name], units="radians")})
+            else:
+                self.monitor.store_constant({name: gathered[name]})
+
     def cleanup(self):
-        self.monitor.cleanup()
+        if self.communicator is None or self.communicator.rank == c.ROOT_RANK:
+            self.monitor.cleanup()
 
 
 # ---- the monitor ------------------------------------------------------------------------------------------------------------------
@@ -345,14 +429,16 @@ class _TimeChunkedVariable:
 
     def __init__(self, initial, time_chunk_size: int):
         first = _host_array(initial)
-        self._data = np.zeros((time_chunk_size, 1) + first.shape, dtype=first.dtype)
-        self._data[0, 0, ...] = first
-        self.dims = tuple(initial.dims)
+        self._global = tuple(initial.dims[:1]) == (c.TILE_DIM,)  # (the whole cube: the tile axis comes with the data)
+        self._data = np.zeros((time_chunk_size,) + (() if self._global else (1,)) + first.shape, dtype=first.dtype)
+        self._data[0].reshape(first.shape)[...] = first
+        self.dims = tuple(initial.dims[1:]) if self._global else tuple(initial.dims)
         self.units = initial.units
         self._i_time = 1
 
     def append(self, quantity):
-        self._data[self._i_time, 0, ...] = _host_array(quantity, self.dims)
+        a = _host_array(quantity) if self._global else _host_array(quantity, self.dims)
+        self._data[self._i_time].reshape(a.shape)[...] = a
         self._i_time += 1
 
     @property
@@ -433,8 +519,11 @@ class NpzMonitor:
 
     def store_constant(self, state: Dict[str, Quantity]) -> None:
         for name, quantity in state.items():
-            self._write(self.CONSTANT_FILENAME_FORMAT.format(name=name, tile=self._tile), {name: _host_array(quantity)[None]},
-                        {name: {"dims": ["tile"] + list(quantity.dims), "units": quantity.units}})
+            a, dims = _host_array(quantity), list(quantity.dims)
+            if dims[:1] != [c.TILE_DIM]:
+                a, dims = a[None], ["tile"] + dims
+            self._write(self.CONSTANT_FILENAME_FORMAT.format(name=name, tile=self._tile), {name: a},
+                        {name: {"dims": dims, "units": quantity.units}})
 
     def cleanup(self):
         self.flush()

@@ -124,7 +124,7 @@ class Driver:
         if self.comm.Get_rank() != 0:
             return
         ignored = []
-        if self.config.diagnostics_config.path is not None and not self.config.diagnostics_config.writes_files:
+        if self.config.diagnostics_config.path is not None and not self.config.diagnostics_config.writes_files_for(self.communicator):
             ignored.append(f"diagnostics_config (path {self.config.diagnostics_config.path!r}): no diagnostics are written, "
                            "output_initial_state and output_frequency have no effect")
         requested = getattr(self.config.stencil_config, "requested_backend", None)

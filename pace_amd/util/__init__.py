@@ -7,4 +7,6 @@ from ._timing import KernelTimes, NullTimer, Timer  # noqa: F401,E402
 from .checkpointer import (Checkpointer, InsufficientTrialsError, NullCheckpointer, SavepointThresholds, SnapshotCheckpointer,  # noqa: F401,E402
                            Threshold, ThresholdCalibrationCheckpointer, ValidationCheckpointer)
 from .restart import LevelOf, open_restart, write_restart  # noqa: F401,E402
+from .gather import Window, check_cube_items  # noqa: F401,E402
+from .monitor import NetCDFMonitor  # noqa: F401,E402
 from . import testing  # noqa: F401,E402

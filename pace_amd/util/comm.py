@@ -13,6 +13,9 @@ over device tensors:
 * ``DeviceCubeComm`` -- ``ThreadComm`` for the whole cubed sphere on one device (``run_cube``): the six ranks of a halo update
   meet in a rendezvous, and the last one to arrive launches ONE kernel that reads every neighbour's field and writes every
   halo (``pace_halo_cube``, pace_amd/util/halo.py).  No message, no buffer.
+
+``ThreadComm.rendezvous`` is the collective behind gather and scatter (pace_amd/util/gather.py): every rank posts, the last one
+to arrive acts for all of them -- under ``DeviceCubeComm`` with ONE ``pace_cube_gather`` / ``pace_cube_scatter`` launch.
 """
 import threading
 from collections import defaultdict, deque
@@ -154,12 +157,16 @@ class _World:
         # that have still to wait() for a launch that has been issued
         self.halo_posts = {}
         self.halo_issued = {}
+        # ThreadComm.rendezvous: (tag, generation) -> {rank: payload}, and -> [result, ranks that have still to take it]
+        self.meet_posts = {}
+        self.meet_results = {}
 
 
 class ThreadComm:
     def __init__(self, world: _World, rank: int):
         self._world = world
         self._rank = rank
+        self._meet_generation = defaultdict(int)  # tag -> rendezvous this rank has joined under it
 
     def Get_rank(self):
         return self._rank
@@ -204,6 +211,29 @@ class ThreadComm:
             else:
                 self._wait(lambda: w.reduce_generation != gen, "allreduce_sum_u64")
             return w.reduce_result.copy()
+
+    def rendezvous(self, tag, payload, last):
+        """The collective of gather and scatter (pace_amd/util/gather.py): every rank posts `payload` under `tag`; the last one
+        to arrive runs ``last({rank: payload})`` -- for DeviceCubeComm that is the one launch for the whole cube -- and every
+        rank returns what it returned.  The n-th call under a tag on one rank meets the n-th on the others."""
+        w = self._world
+        with w.cond:
+            gen = self._meet_generation[tag]
+            self._meet_generation[tag] += 1
+            ticket = (tag, gen)
+            posts = w.meet_posts.setdefault(ticket, {})
+            posts[self._rank] = payload
+            if len(posts) == w.n:
+                del w.meet_posts[ticket]
+                w.meet_results[ticket] = [last(posts), w.n]
+                w.cond.notify_all()
+            else:
+                self._wait(lambda: ticket in w.meet_results, f"rendezvous {ticket}")
+            entry = w.meet_results[ticket]
+            entry[1] -= 1
+            if entry[1] == 0:
+                del w.meet_results[ticket]
+            return entry[0]
 
     def exchange(self, sends, recvs, tag=0):
         w = self._world

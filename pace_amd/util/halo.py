@@ -28,6 +28,7 @@ import torch
 from .. import _lib
 from . import constants as c
 from .comm import Request
+from .gather import GatherScatter
 from .partitioner import EDGES, CubedSpherePartitioner, facing_edge, tile_neighbour
 
 WEST, EAST, NORTH, SOUTH = c.WEST, c.EAST, c.NORTH, c.SOUTH
@@ -483,8 +484,9 @@ class _TileView:
     rank = 0
 
 
-class CubedSphereCommunicator:
-    """communicator.py:680-760 for a (1, 1) layout: rank == tile index."""
+class CubedSphereCommunicator(GatherScatter):
+    """communicator.py:680-760 for a (1, 1) layout: rank == tile index.  gather, gather_state, scatter and scatter_state
+    (communicator.py:111-329) are GatherScatter's (pace_amd/util/gather.py)."""
 
     def __init__(self, comm, partitioner: Optional[CubedSpherePartitioner] = None, device=None, lib=None, force_cpu=False,
                  timer=None):

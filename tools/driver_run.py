@@ -1,7 +1,7 @@
 """Run the model from one of the reference's driver configuration files: pace_amd.driver.Driver, its step_all, one JSON line.
 
     python tools/driver_run.py CONFIG.yaml [--steps N] [--device D] [--cpu-emulation] [--diagnostics DIR]
-                               [--write-fortran-restart DIR] [--cube]
+                               [--diagnostics-format npz|netcdf] [--write-fortran-restart DIR] [--cube]
 
 runs ONE rank (tile 0) with the `null` communicator -- its halos receive zeros, so this exercises the loop, not the weather --
 and, launched under torch.distributed.run as tools/dycore_run.py is,
@@ -14,7 +14,9 @@ says `comm_config: {type: cube}`, or which is given --cube, runs the six tiles i
 (pace_amd.driver.run_cube_driver: every halo update is one kernel launch for the whole cube) and prints the same line.
 --steps replaces the
 file's run length.  --diagnostics DIR writes the file's diagnostics into DIR as per-tile numpy archives (it replaces
-diagnostics_config.path and sets output_format: npz; pace_amd.driver.NpzMonitor describes the files).
+diagnostics_config.path and sets output_format: npz; pace_amd.driver.NpzMonitor describes the files).  With --cube the globe is
+gathered (one pace_cube_gather launch per store) and rank 0 writes one file per time chunk with a tile axis of 6, as npz or,
+with --diagnostics-format netcdf, as NetCDF-3 (pace_amd.util.NetCDFMonitor).
 --write-fortran-restart DIR writes the final state into DIR as restart files of the Fortran model (Driver.write_fortran_restart)
 with a restart.yaml, from which `python tools/driver_run.py DIR/restart.yaml` resumes.  Rank 0 prints: workload, steps, ms per step (mean of the main loop's clock, the slowest rank), SYPD
 (Driver.sypd()), and the time of the safety check per call with its verdict: the checks the file asks for inside the loop
@@ -44,6 +46,8 @@ def main():
                     help="write the file's diagnostics into DIR (diagnostics_config.path = DIR, output_format = npz)")
     ap.add_argument("--write-fortran-restart", metavar="DIR", default=None,
                     help="write the final state into DIR in the Fortran model's restart format, with a restart.yaml that resumes from it")
+    ap.add_argument("--diagnostics-format", choices=("npz", "netcdf"), default="npz",
+                    help="with --diagnostics: numpy archives, or (with --cube) NetCDF-3 files of the whole globe")
     ap.add_argument("--cube", action="store_true", help="a lone process: run all six tiles on the one device (comm_config.type: cube)")
     args = ap.parse_args()
     import yaml
@@ -82,7 +86,10 @@ def main():
     if args.steps is not None:
         settings.update(days=0, hours=0, minutes=0, seconds=0)
     if args.diagnostics is not None:
-        settings["diagnostics_config"] = dict(settings.get("diagnostics_config") or {}, path=args.diagnostics, output_format="npz")
+        if args.diagnostics_format == "netcdf" and not cube:
+            raise SystemExit("--diagnostics-format netcdf is written for the whole cube only: add --cube")
+        settings["diagnostics_config"] = dict(settings.get("diagnostics_config") or {}, path=args.diagnostics,
+                                              output_format=args.diagnostics_format)
     config = DriverConfig.from_dict(settings)
     if args.steps is not None:
         config.seconds = int(round(args.steps * config.dt_atmos))

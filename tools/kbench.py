@@ -13,6 +13,9 @@
     python tools/kbench.py --only restart_pack      write_restart of a state's fifteen 3-D fields and three planes (launch,
                                                     device-to-host copy, file writes) against a torch / numpy restatement, the
                                                     same way, with the split into launch, transfer and write
+    python tools/kbench.py --only cube_gather       one output step (fourteen variables as float32 on the host) of six C96 and six
+                                                    C192 tiles on this device: one pace_cube_gather launch and one transfer
+                                                    against six pace_diag_pack passes, one per tile, with a transfer each
     python tools/kbench.py --only halo_cube         the seven halo-updater groups of an acoustic substep for six tiles on this
                                                     device: the fused path (run_cube: one pace_halo_cube launch per update for
                                                     the whole cube) against the snapshot path (ThreadComm's pack, copies,
@@ -60,6 +63,10 @@ def main():
         return
     if args.only == "halo_cube":  # (its own fields, six tiles)
         halo_cube_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "cube_gather":  # (its own fields, six tiles, C96 and C192)
+        for size in (96, 192):
+            cube_gather_bench(lib, size, nz, args.reps)
         return
     if args.only == "checkpointer":  # (its own fields)
         checkpointer_bench(lib, n, nz, args.reps)
@@ -708,6 +715,94 @@ def halo_cube_bench(lib, n, nz, reps, rounds=3):
         print(f"  {label}: median {np.median(t) / nup:8.1f} us per update of the whole cube (min {t.min() / nup:8.1f}, max {t.max() / nup:8.1f}); "
               f"library calls per update: {per}{copies}")
     print(f"  ratio snapshot / fused: {np.median(times[True]) / np.median(times[False]):.2f}")
+
+
+def cube_gather_bench(lib, n, nz, reps, device="cuda"):
+    """One output step of the whole cube: fourteen variables (the twelve 3-D fields of the example configuration's diagnostics,
+    u and v staggered, a level of pt and a 2-D field) of six tiles on this device, as float32 on the host.
+
+    fused     ONE pace_cube_gather launch for all six tiles and all variables (84 items), one transfer of the dense buffer to
+              pinned memory, one synchronisation -- what MonitorDiagnostics does under run_cube_driver;
+    per tile  six WindowPacker passes, one per tile: a pace_diag_pack launch, a transfer and a synchronisation each -- what six
+              per-tile MonitorDiagnostics do.
+    Host clock from an idle device to the end of the last synchronisation; the two alternate, medians are reported.  The
+    split: the launches alone (enqueued, then one synchronisation) and the transfers alone (of the buffers they filled)."""
+    import time
+
+    from pace_amd.driver.diagnostics import MonitorDiagnostics, WindowPacker, _Request
+    from pace_amd.util import CubedSphereCommunicator, NullComm, QuantityFactory, SubtileGridSizer
+    from pace_amd.util.gather import Window, _Layout, _meta_of
+    from pace_amd import _lib as L
+
+    X, Y, Z, XI, YI = "x", "y", "z", "x_interface", "y_interface"
+    real = torch.float32 if lib.real_bytes == 4 else torch.float64
+    qf = QuantityFactory(SubtileGridSizer(n, n, nz), device, real)
+    names3 = [("u", [X, YI, Z]), ("v", [XI, Y, Z])] + [(k, [X, Y, Z]) for k in ("ua", "va", "pt", "delp", "qvapor", "qliquid", "qice",
+                                                                                "qrain", "qsnow", "qgraupel")]
+    tiles = []
+    for t in range(6):
+        fields = {name: qf.ones(dims, "") for name, dims in names3}
+        fields["phis"] = qf.ones([X, Y], "")
+        requests = [MonitorDiagnostics._whole(name, q) for name, q in fields.items()]
+        pt = fields["pt"]
+        requests.append(_Request("pt_z65", L.DIAG_PLANE, pt, None, min(65, nz - 1), tuple(pt.origin[:2]) + (0,) + tuple(pt.extent[:2]) + (1,),
+                                 (X, Y), ""))
+        tiles.append(requests)
+    assert len(tiles[0]) == 14
+    packers = [WindowPacker(lib) for _ in range(6)]
+    cube = CubedSphereCommunicator(NullComm(0, 6), device=device, lib=lib)
+    windows = {t: [Window(r.field, r.kind, r.level, r.window, r.dims, r.units) for r in tiles[t]] for t in range(6)}
+    layout = _Layout([_meta_of(r.name, w) for r, w in zip(tiles[0], windows[0])], 6)
+    dense, host = cube._gs_buffer(layout.total, torch.float32)
+
+    def sync():
+        if device == "cuda":
+            torch.cuda.synchronize()
+
+    def fused(launch=True, transfer=True):
+        if launch:
+            cube._gs_launch(False, windows, layout, dense)
+        if transfer:
+            host.copy_(dense, non_blocking=True)
+        sync()
+
+    def per_tile(launch=True, transfer=True):
+        if launch and transfer:
+            for t in range(6):
+                packers[t].pack(tiles[t])
+            return
+        for t in range(6):
+            packer = packers[t]
+            geom, offsets, packed, phost = packer._plan(tiles[t], False)
+            if launch:
+                saved, packer._to_host = packer._to_host, lambda *a: None
+                try:
+                    packer.pack(tiles[t])
+                finally:
+                    packer._to_host = saved
+            if transfer:
+                phost.copy_(packed, non_blocking=True)
+        sync()
+
+    fused(), per_tile()  # warm-up: table and plans built, buffers allocated and pinned
+    parts = {"step": (True, True), "launches": (True, False), "transfer": (False, True)}
+    times = {(path, part): [] for path in ("fused", "per tile") for part in parts}
+    for _ in range(reps):
+        for part, (launch, transfer) in parts.items():
+            for path, fn in (("fused", fused), ("per tile", per_tile)):
+                sync()
+                t0 = time.perf_counter()
+                fn(launch, transfer)
+                times[path, part].append(time.perf_counter() - t0)
+    mib = layout.total * 4 / 2 ** 20
+    print(f"one output step of six C{n} x {nz} tiles, fourteen variables, {mib:.0f} MiB of float32 to the host; {reps} repetitions, "
+          "alternating; host clock, idle device to the last synchronisation; medians")
+    for path, what in (("fused", "1 pace_cube_gather, 1 transfer "), ("per tile", "6 pace_diag_pack, 6 transfers")):
+        med = {part: float(np.median(times[path, part])) * 1e6 for part in parts}
+        print(f"  {path:8s} ({what}): step {med['step']:9.1f} us   launches alone {med['launches']:8.1f} us   "
+              f"transfers alone {med['transfer']:9.1f} us ({mib / 1024 / (med['transfer'] * 1e-6):5.1f} GiB/s)")
+    print(f"  ratio per tile / fused: step {np.median(times['per tile', 'step']) / np.median(times['fused', 'step']):.2f}, "
+          f"launches {np.median(times['per tile', 'launches']) / np.median(times['fused', 'launches']):.2f}")
 
 
 def checkpointer_bench(lib, n, nz, reps):
