@@ -46,6 +46,9 @@ typedef pace_metrics_t Met;
 // storage type of fields, metrics and device K-arrays (include/pace_hip.h); arithmetic is double in both builds
 typedef pace_real_t real;
 #define REAL_SHIFT (sizeof(real) == 8 ? 3 : 2)  // log2 of the element size, for the byte-offset addressing of some kernels
+struct alignas(2 * sizeof(real)) RealPair {  // two neighbouring elements as they are stored: one 16-byte (float32: 8-byte) load
+  real x, y;
+};
 
 // Kernel arguments read in place.  A kernel whose argument list is a table of pointers larger than the scalar register file (102
 // SGPRs) gets all of it loaded in its prologue, spilled into lanes of vector registers and read back with v_readlane in front of

@@ -67,9 +67,7 @@ constexpr int RB = (int)sizeof(real);  // bytes per stored element (8; 4 in the 
 struct alignas(16) D2 {
   double x, y;
 };
-struct alignas(2 * sizeof(real)) RealPair {  // two neighbouring elements as they are stored: one 16-byte (float32: 8-byte) load
-  real x, y;
-};
+// (RealPair, two neighbouring elements as they are stored: common.h)
 
 struct FvtLds {
   double pad0[P];     // (the damping runs read one row above / below a plane without clamping)

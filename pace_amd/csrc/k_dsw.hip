@@ -170,6 +170,8 @@ kinetic_energy_point(const Geo& g, const Met& m, const real* __restrict__ uc, co
   ke[c] = kev;
 }
 
+// (The point form: every point loads what it reads itself.  The launcher takes it with PACE_KE_TILED=0 and where there is no interior
+// region; otherwise k_ke_vorticity_tiled below, whose interior threads share their loads between neighbouring points.)
 // The kinetic energy and the relative vorticity in ONE launch, as two kinds of workgroups (round 6): a level's kinetic-energy blocks and,
 // behind them in the same level's share of the launch, the 64 x 4 patches of its vorticity.  Nothing is shared per point (x02: the
 // vorticity inside the kinetic-energy point function was slower); what is shared is the launch -- no drain / fill between the two -- and
@@ -223,6 +225,175 @@ k_ke_vorticity(Geo g, Met m, const real* __restrict__ uc, const real* __restrict
     const int k = k0 + t;
     if (k >= g.nk) break;
     kinetic_energy_point<MORD>(g, m, uc, vc, u, v, ut, vt, ke, dt, (real*)nullptr, i, j, k, interior, true);
+  }
+}
+
+// The interior region as register tiles: a thread owns the 2 x TR block of B-grid points of columns i0 (even), i0 + 1 and
+// rows j0 .. j0 + TR - 1 and loads every value the block's kinetic energies AND relative vorticities read ONCE per level, as aligned
+// pairs (rows are 128-byte aligned): the point form issues 22 + 9 loads per point and level for 4 inputs, this 9 - 11.  The expressions are
+// those of kinetic_energy_point's interior branch and of rel_vorticity, operand by operand: the bits are the same.  ok0 / ok1: the
+// column is inside the region (an odd first column or an even last one: the pair starts one column outside / ends one outside);
+// rows past `je` (the region's height is no multiple of TR) are loaded from the storage's last row at most and not used.
+// Needs i0 >= 4 and i0 + 3 < ni (launcher: ke_tiles_fit).
+#ifndef KE_TILE_R
+#define KE_TILE_R 1  // rows of a thread's block (C192: 1 and 2 within 2 us of each other, 4 slower than the point form: DESIGN 4.3)
+#endif
+#ifndef KE_TILED_MIN_N
+// tile size from which the interior takes the tiles by itself: the smallest size measured (faster at every one, C48 ... C192:
+// profiles/ke_tiled_ab.txt); smaller tiles keep the point form (PACE_KE_TILED=1: tiles wherever there is an interior region, =0: never)
+#define KE_TILED_MIN_N 48
+#endif
+#ifndef KE_TILED_CH2_MIN_WGS
+// workgroups the tiled one-level launch must have for two levels per thread (C48: 1.2 k, a tie; C96: 2.8 k; C192: 7.9 k)
+#define KE_TILED_CH2_MIN_WGS 2048u
+#endif
+__device__ __forceinline__ void ld_pair(const real* __restrict__ p, double& a, double& b) {
+  const RealPair r = *(const RealPair*)p;
+  a = r.x;
+  b = r.y;
+}
+// the sum / product of two STORED values as the point form's expressions form them: in the storage type (float32 storage: a float
+// operation; a double that holds a stored value converts back exactly)
+__device__ __forceinline__ double add_stored(double a, double b) { return (real)a + (real)b; }
+__device__ __forceinline__ double mul_stored(double a, double b) { return (real)a * (real)b; }
+template <int MORD, int KE_CH, int TR>
+__device__ __forceinline__ void
+ke_vorticity_tile(const Geo& g, const Met& m, const real* __restrict__ uc, const real* __restrict__ vc, const real* __restrict__ u,
+                  const real* __restrict__ v, real* __restrict__ ke, double dt, real* __restrict__ vort, int i0, int j0, int je, bool ok0,
+                  bool ok1, int k0) {
+  const int sj = g.sj, jlast = g.nj - 1;
+  auto at = [&](int j) { return (long)(j < jlast ? j : jlast) * sj + i0; };  // (i0, j) in a plane, the row held inside the storage
+  // the block's metric values, held across the levels
+  double cosa[TR][2], rsina[TR][2], rdx[TR][3], rdy[TR + 1][2], ra[TR][2], dx[TR + 1][2], dy[TR][3];
+#pragma unroll
+  for (int r = 0; r < TR; ++r) {
+    const long o = at(j0 + r);
+    double skip;
+    ld_pair(m.cosa + o, cosa[r][0], cosa[r][1]);
+    ld_pair(m.rsina + o, rsina[r][0], rsina[r][1]);
+    ld_pair(m.rdx + o - 2, skip, rdx[r][0]);
+    ld_pair(m.rdx + o, rdx[r][1], rdx[r][2]);
+    ld_pair(m.rarea + o, ra[r][0], ra[r][1]);
+    ld_pair(m.dy + o, dy[r][0], dy[r][1]);
+    dy[r][2] = m.dy[o + 2];
+  }
+#pragma unroll
+  for (int r = 0; r <= TR; ++r) {
+    ld_pair(m.rdy + at(j0 - 1 + r), rdy[r][0], rdy[r][1]);
+    ld_pair(m.dx + at(j0 + r), dx[r][0], dx[r][1]);
+  }
+#pragma unroll 1  // (a level's values are dead before the next level's loads: unrolled, no faster -- profiles/ke_tiled_ab.txt)
+  for (int t = 0; t < KE_CH; ++t) {
+    const int k = k0 + t;
+    if (k >= g.nk) break;
+    const long kb = (long)k * g.sk;
+    double vv[TR + 5][2];  // v, rows j0 - 3 .. j0 + TR + 1
+    double v2[TR];         // v(i0 + 2), rows j0 .. j0 + TR - 1 (the second column's vorticity)
+    double uu[TR + 1][8];  // u, columns i0 - 4 .. i0 + 3 of rows j0 .. j0 + TR - 1; row j0 + TR: i0, i0 + 1 only (the vorticity)
+    double ucp[TR + 1][2];  // uc, rows j0 - 1 .. j0 + TR - 1
+    double vcp[TR][3];      // vc, columns i0 - 1 .. i0 + 1
+#pragma unroll
+    for (int r = 0; r < TR + 5; ++r) ld_pair(v + kb + at(j0 - 3 + r), vv[r][0], vv[r][1]);
+#pragma unroll
+    for (int r = 0; r <= TR; ++r) ld_pair(uc + kb + at(j0 - 1 + r), ucp[r][0], ucp[r][1]);
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+      const long o = kb + at(j0 + r);
+      double skip;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ld_pair(u + o - 4 + 2 * q, uu[r][2 * q], uu[r][2 * q + 1]);
+      ld_pair(vc + o - 2, skip, vcp[r][0]);
+      ld_pair(vc + o, vcp[r][1], vcp[r][2]);
+      v2[r] = v[o + 2];
+    }
+    ld_pair(u + kb + at(j0 + TR), uu[TR][4], uu[TR][5]);
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+      const int j = j0 + r;
+      if (j > je) break;
+      double kev[2], wv[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const double ub_cov = 0.5 * add_stored(ucp[r][s], ucp[r + 1][s]);
+        const double vb_cov = 0.5 * add_stored(vcp[r][s], vcp[r][s + 1]);
+        const double ub = (ub_cov - vb_cov * cosa[r][s]) * rsina[r][s];
+        const double vb = (vb_cov - ub_cov * cosa[r][s]) * rsina[r][s];
+        double q6[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) q6[e] = vv[r + e][s];
+        double cfl = (vb > 0.0) ? vb * dt * rdy[r][s] : vb * dt * rdy[r + 1][s];
+        const double adv_v = wind_flux6<MORD, false>(q6, vb, cfl, j, g.js, g.je, [](int) { return 0.0; }, false, false);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) q6[e] = uu[r][s + 1 + e];
+        cfl = (ub > 0.0) ? ub * dt * rdx[r][s] : ub * dt * rdx[r][s + 1];
+        const double adv_u = wind_flux6<MORD, false>(q6, ub, cfl, i0 + s, g.is, g.ie, [](int) { return 0.0; }, false, false);
+        kev[s] = 0.5 * dt * (ub * adv_u + vb * adv_v);
+        const double dxc = dx[r][s], dyc = dy[r][s];
+        wv[s] = (uu[r][4 + s] - mul_stored(uu[r + 1][4 + s], dx[r + 1][s]) / dxc) * (ra[r][s] * dxc) +
+                (mul_stored(s == 0 ? vv[r + 3][1] : v2[r], dy[r][s + 1]) / dyc - vv[r + 3][s]) * (ra[r][s] * dyc);
+      }
+      const long c = kb + (long)j * sj + i0;
+      if (ok0 && ok1) {
+        *(RealPair*)(ke + c) = RealPair{(real)kev[0], (real)kev[1]};
+        *(RealPair*)(vort + c) = RealPair{(real)wv[0], (real)wv[1]};
+      } else if (ok0) {
+        ke[c] = kev[0];
+        vort[c] = wv[0];
+      } else if (ok1) {
+        ke[c + 1] = kev[1];
+        vort[c + 1] = wv[1];
+      }
+    }
+  }
+}
+
+// point (i, j) of thread t of block `b` of the frame strips of S (regions 1 .. n - 1, each flattened over its blocks' 256 threads:
+// REGION_POINT's map); false: a padding thread
+__device__ __forceinline__ bool strip_point(const Regions& S, int b, int t, int& i, int& j) {
+  int reg__ = 1;
+  while (reg__ + 1 < S.n && b >= S.first[reg__ + 1]) ++reg__;
+  const int w__ = S.ie[reg__] - S.ib[reg__] + 1;
+  const int p__ = (b - S.first[reg__]) * 256 + t;
+  j = S.jb[reg__] + p__ / w__;
+  i = S.ib[reg__] + p__ % w__;
+  return j <= S.je[reg__];
+}
+
+// k_ke_vorticity with the interior region taken by ke_vorticity_tile: the blocks of a chunk of KE_CH levels are, in this order, the
+// tile blocks (the region's pairs of columns x groups of TR rows, flattened over the 256 threads: a block's rows are contiguous;
+// a thread takes the chunk's levels one after the other) and, ONE level each as in REGION_POINT_CHUNKED (the edge forms cost
+// several times the interior's per point, and looped over levels their position tests spill scalar registers), level by level:
+// the frame strips of the kinetic energy (regions 1 .. of R, the point form) and the strips of RV, the vorticity's domain
+// [0, ni - 2] x [0, nj - 2] minus the interior region, whose cells the tiles have written.
+// nbt: tile blocks; nbks: blocks of R's strips; nbs: those + the blocks of RV's strips.
+template <int MORD, int KE_CH, int TR>
+__global__ void __launch_bounds__(256)
+k_ke_vorticity_tiled(Geo g, Met m, const real* __restrict__ uc, const real* __restrict__ vc, const real* __restrict__ u,
+                     const real* __restrict__ v, const real* __restrict__ ut, const real* __restrict__ vt, real* __restrict__ ke, double dt,
+                     Regions R, Regions RV, real* __restrict__ vort, int nbt, int nbks, int nbs) {
+  const KeBlock wg__ = ke_block_of_linear((int)blockIdx.x + (int)gridDim.x * (int)blockIdx.z, (int)gridDim.x, (int)gridDim.z);
+  const int bx__ = wg__.bx, k0 = wg__.bz * KE_CH;
+  const int t__ = (int)threadIdx.y * 64 + (int)threadIdx.x;
+  if (bx__ < nbt) {
+    const int ib0 = R.ib[0] & ~1, npr = (R.ie[0] - ib0) / 2 + 1;  // pairs of columns in a row of the region
+    const int p__ = bx__ * 256 + t__;
+    const int rg = p__ / npr, i0 = ib0 + 2 * (p__ - rg * npr), j0 = R.jb[0] + rg * TR;
+    if (j0 > R.je[0]) return;
+    ke_vorticity_tile<MORD, KE_CH, TR>(g, m, uc, vc, u, v, ke, dt, vort, i0, j0, R.je[0], i0 >= R.ib[0], i0 + 1 <= R.ie[0], k0);
+    return;
+  }
+  // a frame strip, of the kinetic energy or of the vorticity: its points flattened over the block
+  const int lev__ = (bx__ - nbt) / nbs, bs__ = (bx__ - nbt) - lev__ * nbs;
+  const int k = k0 + lev__;
+  if (k >= g.nk) return;
+  int i, j;
+  if (bs__ < nbks) {
+    if (!strip_point(R, bs__ + R.first[1], t__, i, j)) return;
+    kinetic_energy_point<MORD>(g, m, uc, vc, u, v, ut, vt, ke, dt, (real*)nullptr, i, j, k, false, true);
+  } else {
+    if (!strip_point(RV, bs__ - nbks + RV.first[1], t__, i, j)) return;
+    const long c = IDX3(g, i, j, k);
+    vort[c] = rel_vorticity(g, m, u, v, c, IDX2(g, i, j));
   }
 }
 
@@ -1721,8 +1892,34 @@ struct DswCall {
     const dim3 pg = patch_grid(g, 1);
     const unsigned nbl = (unsigned)nbr + pg.x * pg.y;
     const char* ke_ch_env = getenv("PACE_KE_LEVELS");  // (read per call; a test lever: 1 or 2 levels per thread)
+    const char* tiled_env = getenv("PACE_KE_TILED");  // (read per call; first character '0': the point form, '1': tiles at any size)
+    const bool tiled = ke_tiles_fit(rke) && !(tiled_env && tiled_env[0] == '0') && ((tiled_env && tiled_env[0] == '1') || g.n >= KE_TILED_MIN_N);
+    if (tiled) {
+      // the interior as register tiles (ke_vorticity_tile); the vorticity's strips cover its domain minus the interior
+      const int npr = (rke.ie[0] - (rke.ib[0] & ~1)) / 2 + 1, nrg = (rke.je[0] - rke.jb[0] + KE_TILE_R) / KE_TILE_R;
+      const int nbt = (npr * nrg + 255) / 256, nbks = nbr - rke.first[1];
+      Regions rv{};  // (region 0 empty: strips only)
+      rv.n = 1; rv.ie[0] = -1; rv.je[0] = -1; rv.nbx0 = 1;
+      add_region(rv, 0, g.ni - 2, 0, rke.jb[0] - 1);
+      add_region(rv, 0, g.ni - 2, rke.je[0] + 1, g.nj - 2);
+      add_region(rv, 0, rke.ib[0] - 1, rke.jb[0], rke.je[0]);
+      add_region(rv, rke.ie[0] + 1, g.ni - 2, rke.jb[0], rke.je[0]);
+      const int nbs = nbks + rv.first[rv.n];  // strip blocks of a level
+      const int ch = ke_ch_env ? (ke_ch_env[0] == '2' ? 2 : 1) : ((unsigned)((nbt + nbs) * nk) >= KE_TILED_CH2_MIN_WGS ? 2 : 1);
+      const unsigned nbt_l = (unsigned)(nbt + ch * nbs);  // blocks of a chunk of levels: the strips take one level each
+#define KE_GO(MORD, CH)                                                                                                                  \
+  hipLaunchKernelGGL((k_ke_vorticity_tiled<MORD, CH, KE_TILE_R>), dim3(nbt_l, 1, (unsigned)((nk + CH - 1) / CH)), dim3(64, 4), 0, st, g, m, \
+                     f.uc, f.vc, f.u, f.v, W.ut, W.vt, W.ke, f.dt, rke, rv, W.wk, nbt, nbks, nbs)
+      if (cfg->hord_mt == 5) {
+        if (ch == 2) KE_GO(5, 2); else KE_GO(5, 1);
+      } else {
+        if (ch == 2) KE_GO(6, 2); else KE_GO(6, 1);
+      }
+#undef KE_GO
+      return wind_halo_own_launch();
+    }
     const int ke_ch = ke_ch_env ? (ke_ch_env[0] == '2' ? 2 : 1) : (nbl * (unsigned)nk >= KE_CH2_MIN_WGS ? 2 : 1);
-#define KE_GO(MORD, CH)                                                                                                                     \
+#define KE_GO(MORD, CH)                                                                                                                   \
   hipLaunchKernelGGL((k_ke_vorticity<MORD, CH>), dim3(nbl, 1, (unsigned)((nk + CH - 1) / CH)), dim3(64, 4), 0, st, g, m, f.uc, f.vc, f.u, f.v, \
                      W.ut, W.vt, W.ke, f.dt, rke, W.wk, nbr)
     if (cfg->hord_mt == 5) {
@@ -1731,10 +1928,23 @@ struct DswCall {
       if (ke_ch == 2) KE_GO(6, 2); else KE_GO(6, 1);
     }
 #undef KE_GO
+    return wind_halo_own_launch();
+  }
+  int wind_halo_own_launch() const {
     if (p.wind_halo == WIND_HALO_OWN_LAUNCH)  // over the frame of the plane
-      hipLaunchKernelGGL(k_copy_wind_halo, dim3((unsigned)((wind_halo_points(g) + 255) / 256), (unsigned)nk), dim3(256), 0, st, g, f.u, f.v,
+      hipLaunchKernelGGL(k_copy_wind_halo, dim3((unsigned)((wind_halo_points(g) + 255) / 256), (unsigned)g.nk), dim3(256), 0, st, g, f.u, f.v,
                          cfg->u_out, cfg->v_out);
     return PACE_OK;
+  }
+  // The tiles' pair loads: every plane and field 2-element aligned with even strides, the interior region not empty, and columns
+  // i0 - 4 .. i0 + 3 of every pair's first column i0 inside the storage's rows.
+  bool ke_tiles_fit(const Regions& rke) const {
+    if (rke.ie[0] < rke.ib[0] || rke.je[0] < rke.jb[0] || (rke.ib[0] & ~1) < 4 || (rke.ie[0] & ~1) + 3 >= g.ni || rke.jb[0] < 3) return false;
+    if ((g.sj & 1) || (g.sk & 1)) return false;
+    const void* ptrs[] = {f.uc, f.vc, f.u, f.v, W.ke, W.wk, m.cosa, m.rsina, m.rdx, m.rdy, m.rarea, m.dx, m.dy};
+    for (const void* q : ptrs)
+      if ((uintptr_t)q % sizeof(RealPair)) return false;
+    return true;
   }
 
   // winds A2: divergence damping, then (the split order) the vorticity transport
