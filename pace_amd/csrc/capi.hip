@@ -41,6 +41,18 @@ static bool legacy_column_solvers() {
   return pace_env_on("PACE_LEGACY_COLUMN_SOLVERS");  // (read at every call: tests switch between the two forms within one process)
 }
 
+// The window of an item of the pack kernels (pace_diag_item_t, pace_unpack_item_t, pace_restart_item_t name these fields alike):
+// a 3-D window or a plane (`columns`: or a column integral) of a field that is there, inside the storage's (n + 7)^2 points and
+// nk + 1 levels; a plane is given by its field pointer alone: k0 = 0, nk = 1.
+template <class Item>
+static bool window_ok(const pace_geom_t* geom, const Item& it, bool columns = false) {
+  const int ni = geom->n + 7, nlev = geom->nk + 1;
+  if (it.kind != PACE_DIAG_WINDOW3D && it.kind != PACE_DIAG_PLANE && !(columns && it.kind == PACE_DIAG_COLUMN_INTEGRAL)) return false;
+  if (!it.field) return false;
+  if (it.i0 < 0 || it.ni < 1 || it.ni > ni - it.i0 || it.j0 < 0 || it.nj < 1 || it.nj > ni - it.j0) return false;
+  return it.kind == PACE_DIAG_PLANE ? (it.k0 == 0 && it.nk == 1) : (it.k0 >= 0 && it.nk >= 1 && it.nk <= nlev - it.k0);
+}
+
 extern "C" {
 
 const char* pace_last_error(void) { return g_pace_err; }
@@ -680,14 +692,10 @@ int pace_diag_pack(const pace_geom_t* geom, const pace_diag_item_t* items, int n
                    void* stream) {
   NEED(geom && items && out);
   if (nitems < 1 || nitems > PACE_DIAG_MAX_ITEMS) return PACE_ERR_ARG;
-  const int ni = geom->n + 7, nlev = geom->nk + 1;
   for (int m = 0; m < nitems; ++m) {
     const pace_diag_item_t& it = items[m];
-    if (it.kind != PACE_DIAG_WINDOW3D && it.kind != PACE_DIAG_PLANE && it.kind != PACE_DIAG_COLUMN_INTEGRAL) return PACE_ERR_ARG;
-    if (!it.field || it.out_offset < 0) return PACE_ERR_ARG;
+    if (!window_ok(geom, it, true) || it.out_offset < 0) return PACE_ERR_ARG;
     if (it.kind == PACE_DIAG_COLUMN_INTEGRAL && !it.weight) return PACE_ERR_ARG;
-    if (it.i0 < 0 || it.ni < 1 || it.ni > ni - it.i0 || it.j0 < 0 || it.nj < 1 || it.nj > ni - it.j0) return PACE_ERR_ARG;
-    if (it.kind == PACE_DIAG_PLANE ? (it.k0 != 0 || it.nk != 1) : (it.k0 < 0 || it.nk < 1 || it.nk > nlev - it.k0)) return PACE_ERR_ARG;
   }
   return launch_diag_pack(make_geo(geom), items, nitems, out_is_double, out, S(stream));
 }
@@ -695,28 +703,19 @@ int pace_diag_pack(const pace_geom_t* geom, const pace_diag_item_t* items, int n
 int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, int nitems, const double* in, void* stream) {
   NEED(geom && items && in);
   if (nitems < 1 || nitems > PACE_UNPACK_MAX_ITEMS) return PACE_ERR_ARG;
-  const int ni = geom->n + 7, nlev = geom->nk + 1;
   for (int m = 0; m < nitems; ++m) {
     const pace_unpack_item_t& it = items[m];
-    if (it.kind != PACE_DIAG_WINDOW3D && it.kind != PACE_DIAG_PLANE) return PACE_ERR_ARG;
+    if (!window_ok(geom, it)) return PACE_ERR_ARG;
     if (it.order != PACE_ORDER_ZFAST && it.order != PACE_ORDER_XFAST) return PACE_ERR_ARG;
-    if (!it.field || it.in_offset < 0 || it.in_step < 1) return PACE_ERR_ARG;
-    if (it.i0 < 0 || it.ni < 1 || it.ni > ni - it.i0 || it.j0 < 0 || it.nj < 1 || it.nj > ni - it.j0) return PACE_ERR_ARG;
-    if (it.kind == PACE_DIAG_PLANE ? (it.k0 != 0 || it.nk != 1) : (it.k0 < 0 || it.nk < 1 || it.nk > nlev - it.k0)) return PACE_ERR_ARG;
+    if (it.in_offset < 0 || it.in_step < 1) return PACE_ERR_ARG;
   }
   return launch_state_unpack(make_geo(geom), items, nitems, in, S(stream));
 }
 
 static int restart_check(const pace_geom_t* geom, const pace_restart_item_t* items, int nitems) {
   if (!items || nitems < 1 || nitems > PACE_RESTART_MAX_ITEMS) return PACE_ERR_ARG;
-  const int ni = geom->n + 7, nlev = geom->nk + 1;
-  for (int m = 0; m < nitems; ++m) {
-    const pace_restart_item_t& it = items[m];
-    if (it.kind != PACE_DIAG_WINDOW3D && it.kind != PACE_DIAG_PLANE) return PACE_ERR_ARG;
-    if (!it.field) return PACE_ERR_ARG;
-    if (it.i0 < 0 || it.ni < 1 || it.ni > ni - it.i0 || it.j0 < 0 || it.nj < 1 || it.nj > ni - it.j0) return PACE_ERR_ARG;
-    if (it.kind == PACE_DIAG_PLANE ? (it.k0 != 0 || it.nk != 1) : (it.k0 < 0 || it.nk < 1 || it.nk > nlev - it.k0)) return PACE_ERR_ARG;
-  }
+  for (int m = 0; m < nitems; ++m)
+    if (!window_ok(geom, items[m])) return PACE_ERR_ARG;
   return PACE_OK;
 }
 

@@ -6,8 +6,7 @@
 // first (exact); every accumulator, expected value and result is double in both libraries.
 //
 //   k_ckpt_accumulate          1-D grid, 256 threads = 4 waves.  A workgroup takes CK_ROWS * 4 consecutive rows (j, k) of one
-//                              item, which it finds by a bisection of the prefix table of per-item workgroup counts that travels
-//                              by value with the items (workgroup-uniform: scalar loads and branches, as k_diag_pack).  A wave
+//                              item, which it finds by table_find (wgmap.h) in the table that travels by value (pack_table.h).  A wave
 //                              takes a row, lane l the points i = l, l + 64, ...: 512 B contiguous of the field and of each of
 //                              the three dense accumulators (row r of them starts at r * ni).  first: plain stores; otherwise
 //                              read-modify-write of the thread's own elements -- no atomics, and one accumulator per element
@@ -29,6 +28,7 @@
 // never read.
 #include "common.h"
 #include "kernels.h"
+#include "pack_table.h"
 
 #define CK_WAVES 4
 #define CK_ROWS 16                     // rows a wave walks (accumulate, validate)
@@ -53,22 +53,7 @@ struct CkValItem {
   int i0, j0, k0, wi, wj, wk;
 };
 template <class Item>
-struct CkTable {
-  Item item[PACE_CKPT_MAX_ITEMS];
-  int first[PACE_CKPT_MAX_ITEMS + 1];  // first workgroup of each item; first[nitems] = the grid
-  int nitems;
-};
-
-template <class Item>
-__device__ __forceinline__ int ck_find(const CkTable<Item>& tab, int b) {
-  int m = 0, hi = tab.nitems;  // first[m] <= b < first[hi]
-  while (hi - m > 1) {
-    const int mid = (m + hi) >> 1;
-    if (b >= tab.first[mid]) m = mid;
-    else hi = mid;
-  }
-  return m;
-}
+using CkTable = PackTable<Item, PACE_CKPT_MAX_ITEMS>;
 
 // ---- calibration: the fold of one trial ----------------------------------------------------------------------------------------
 // numpy's minimum / maximum (loops_minmax: (a < b || isnan(a)) ? a : b): a NaN on either side gives NaN, and stays
@@ -77,7 +62,7 @@ __device__ __forceinline__ double ck_np_max(double a, double b) { return (a > b 
 
 __global__ void __launch_bounds__(64 * CK_WAVES) k_ckpt_accumulate(CkTable<CkAccItem> tab, int first) {
   const int b = (int)blockIdx.x;
-  const int m = ck_find(tab, b);
+  const int m = table_find(tab.first, tab.nitems, b);
   const CkAccItem& it = tab.item[m];
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int r0 = ((b - tab.first[m]) * CK_WAVES + wave) * CK_ROWS;
@@ -176,7 +161,7 @@ __device__ __forceinline__ void ck_block_reduce_store(R e, double* out) {
 __global__ void __launch_bounds__(64 * CK_WAVES) k_ckpt_thresholds_partial(CkTable<CkThrItem> tab, double n_trials,
                                                                             double* __restrict__ partial) {
   const int b = (int)blockIdx.x;
-  const int m = ck_find(tab, b);
+  const int m = table_find(tab.first, tab.nitems, b);
   const CkThrItem& it = tab.item[m];
   const long e0 = (long)(b - tab.first[m]) * CK_CHUNK;
   CkThr acc = ck_identity((const CkThr*)nullptr);
@@ -195,7 +180,7 @@ __global__ void __launch_bounds__(64 * CK_WAVES) k_ckpt_thresholds_partial(CkTab
 // ---- validation ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64 * CK_WAVES) k_ckpt_validate_partial(CkTable<CkValItem> tab, double* __restrict__ partial) {
   const int b = (int)blockIdx.x;
-  const int m = ck_find(tab, b);
+  const int m = table_find(tab.first, tab.nitems, b);
   const CkValItem& it = tab.item[m];
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int r0 = ((b - tab.first[m]) * CK_WAVES + wave) * CK_ROWS;
@@ -254,6 +239,12 @@ __global__ void __launch_bounds__(64 * CK_WAVES) k_ckpt_validate_partial(CkTable
 struct CkFirst {
   int first[PACE_CKPT_MAX_ITEMS + 1];
 };
+template <class Item>
+static inline CkFirst ck_firsts(const CkTable<Item>& tab) {  // the prefix table alone, for the combine
+  CkFirst f;
+  memcpy(f.first, tab.first, sizeof(f.first));
+  return f;
+}
 
 template <class R>
 __global__ void __launch_bounds__(64) k_ckpt_combine(CkFirst tab, const double* __restrict__ partial, double* __restrict__ out) {
@@ -287,34 +278,29 @@ long ckpt_validate_blocks(const pace_ckpt_item_t* items, int nitems) {
 int launch_ckpt_accumulate(const pace_ckpt_item_t* items, int nitems, int first, hipStream_t st) {
   CkTable<CkAccItem> tab{};
   tab.nitems = nitems;
-  long blocks = 0;
   for (int m = 0; m < nitems; ++m) {
     const pace_ckpt_item_t& it = items[m];
     tab.item[m] = CkAccItem{it.field, it.mn, it.mx, it.asum, (long)it.sj, (long)it.sk, it.ni, it.nj, it.nj * it.nk, 0};
-    blocks += ck_row_blocks((long)it.nj * it.nk);
-    if (blocks > 0x7fffffffL) return PACE_ERR_UNSUPPORTED;
-    tab.first[m + 1] = (int)blocks;
   }
-  hipLaunchKernelGGL(k_ckpt_accumulate, dim3((unsigned)blocks), dim3(64 * CK_WAVES), 0, st, tab, first);
+  const int rc = pack_table_fill_first(tab, [](const CkAccItem& it) { return ck_row_blocks(it.nrows); });
+  if (rc != PACE_OK) return rc;
+  hipLaunchKernelGGL(k_ckpt_accumulate, dim3((unsigned)tab.first[nitems]), dim3(64 * CK_WAVES), 0, st, tab, first);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 }
 
 int launch_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_trials, void* workspace, double* out, hipStream_t st) {
   CkTable<CkThrItem> tab{};
-  CkFirst firsts{};
   tab.nitems = nitems;
-  long blocks = 0;
   for (int m = 0; m < nitems; ++m) {
     const pace_ckpt_item_t& it = items[m];
-    const long count = (long)it.ni * it.nj * it.nk;
-    tab.item[m] = CkThrItem{it.mn, it.mx, it.asum, count};
-    blocks += ck_chunk_blocks(count);
-    if (blocks > 0x7fffffffL) return PACE_ERR_UNSUPPORTED;
-    tab.first[m + 1] = firsts.first[m + 1] = (int)blocks;
+    tab.item[m] = CkThrItem{it.mn, it.mx, it.asum, (long)it.ni * it.nj * it.nk};
   }
+  const int rc = pack_table_fill_first(tab, [](const CkThrItem& it) { return ck_chunk_blocks(it.count); });
+  if (rc != PACE_OK) return rc;
+  const CkFirst firsts = ck_firsts(tab);
   double* partial = (double*)workspace;
-  hipLaunchKernelGGL(k_ckpt_thresholds_partial, dim3((unsigned)blocks), dim3(64 * CK_WAVES), 0, st, tab, (double)n_trials, partial);
+  hipLaunchKernelGGL(k_ckpt_thresholds_partial, dim3((unsigned)tab.first[nitems]), dim3(64 * CK_WAVES), 0, st, tab, (double)n_trials, partial);
   PACE_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_ckpt_combine<CkThr>, dim3((unsigned)nitems), dim3(64), 0, st, firsts, partial, out);
   PACE_CHECK_LAUNCH();
@@ -323,19 +309,17 @@ int launch_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_tria
 
 int launch_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspace, double* out, hipStream_t st) {
   CkTable<CkValItem> tab{};
-  CkFirst firsts{};
   tab.nitems = nitems;
-  long blocks = 0;
   for (int m = 0; m < nitems; ++m) {
     const pace_ckpt_item_t& it = items[m];
     tab.item[m] = CkValItem{it.field, it.expected, (long)it.sj, (long)it.sk, (long)it.ei, (long)it.ej, (long)it.ek, it.rtol, it.atol,
                             it.i0, it.j0, it.k0, it.wi, it.wj, it.wk};
-    blocks += ck_row_blocks((long)it.wj * it.wk);
-    if (blocks > 0x7fffffffL) return PACE_ERR_UNSUPPORTED;
-    tab.first[m + 1] = firsts.first[m + 1] = (int)blocks;
   }
+  const int rc = pack_table_fill_first(tab, [](const CkValItem& it) { return ck_row_blocks((long)it.wj * it.wk); });
+  if (rc != PACE_OK) return rc;
+  const CkFirst firsts = ck_firsts(tab);
   double* partial = (double*)workspace;
-  hipLaunchKernelGGL(k_ckpt_validate_partial, dim3((unsigned)blocks), dim3(64 * CK_WAVES), 0, st, tab, partial);
+  hipLaunchKernelGGL(k_ckpt_validate_partial, dim3((unsigned)tab.first[nitems]), dim3(64 * CK_WAVES), 0, st, tab, partial);
   PACE_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_ckpt_combine<CkVal>, dim3((unsigned)nitems), dim3(64), 0, st, firsts, partial, out);
   PACE_CHECK_LAUNCH();

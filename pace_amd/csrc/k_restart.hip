@@ -13,9 +13,8 @@
 //                      V * s - shift + V - 1.  A slot that lies wholly inside the item is ONE 16-byte store at an aligned
 //                      address; the first slot (head) and the last (tail) may hold fewer elements and store them one by one.
 //                      A workgroup takes RS_SLOTS = 4 * 256 consecutive slots (16 KiB of output), thread t the slots t,
-//                      t + 256, ...: a wave's store is 1 KiB contiguous.  It finds its item by a bisection of the prefix table
-//                      of per-item workgroup counts, which travels by value with the items (workgroup-uniform: scalar loads and
-//                      scalar branches only, as k_diag_pack).
+//                      t + 256, ...: a wave's store is 1 KiB contiguous.  It finds its item by table_find (wgmap.h) in the
+//                      table that travels by value (pack_table.h).
 //           loads      per element, no LDS stage.  The window's rows are 12 .. 391 elements and start at any element, so no
 //                      vector load is aligned; but consecutive output elements ARE consecutive addresses within a row, and a
 //                      wave's V load instructions together read the same 128 (256) consecutive elements -- whole cache lines but
@@ -35,6 +34,7 @@
 // unchanged (the value never passes through a floating-point instruction).
 #include "common.h"
 #include "kernels.h"
+#include "pack_table.h"
 
 #define RS_WAVES 4
 #define RS_UNROLL 4
@@ -48,11 +48,7 @@ struct RestartEntry {
   long out_byte;  // of the item's first element
 };
 
-struct RestartTable {
-  RestartEntry item[PACE_RESTART_MAX_ITEMS];
-  int first[PACE_RESTART_MAX_ITEMS + 1];  // first workgroup of each item; first[nitems] = the grid
-  int nitems;
-};
+typedef PackTable<RestartEntry, PACE_RESTART_MAX_ITEMS> RestartTable;
 
 struct alignas(16) RestartSlot {
   uint64_t w[2];
@@ -92,12 +88,7 @@ __global__ void __launch_bounds__(64 * RS_WAVES) k_restart_pack(Geo g, RestartTa
                                                                  uint64_t* __restrict__ partial) {
   constexpr int V = 16 / (int)sizeof(OutT);
   const int b = (int)blockIdx.x;
-  int m = 0, hi = tab.nitems;  // first[m] <= b < first[hi]
-  while (hi - m > 1) {
-    const int mid = (m + hi) >> 1;
-    if (b >= tab.first[mid]) m = mid;
-    else hi = mid;
-  }
+  const int m = table_find(tab.first, tab.nitems, b);
   const RestartEntry& it = tab.item[m];
   const real* __restrict__ q = it.field;
   const int ni = it.ni, nj = it.nj, total = it.total, shift = it.shift;
@@ -199,7 +190,6 @@ int launch_restart_pack(const Geo& g, const pace_restart_item_t* items, int nite
   const int esize = out_type == PACE_RESTART_BE_F64 ? 8 : 4, v = 16 / esize;
   RestartTable tab{};
   tab.nitems = nitems;
-  long blocks = 0;
   for (int m = 0; m < nitems; ++m) {
     const pace_restart_item_t& in = items[m];
     RestartEntry& e = tab.item[m];
@@ -208,10 +198,9 @@ int launch_restart_pack(const Geo& g, const pace_restart_item_t* items, int nite
     e.total = in.ni * in.nj * in.nk;  // (within the storage: below 2^29, geom_check)
     e.out_byte = in.out_offset;
     e.shift = out ? (int)(((uintptr_t)out + (uintptr_t)in.out_offset) % 16) / esize : 0;
-    blocks += restart_blocks(e.total, e.shift, v);
-    if (blocks > 0x7fffffffL) return PACE_ERR_UNSUPPORTED;
-    tab.first[m + 1] = (int)blocks;
   }
+  const int rc = pack_table_fill_first(tab, [v](const RestartEntry& e) { return restart_blocks(e.total, e.shift, v); });
+  if (rc != PACE_OK) return rc;
   const dim3 grid((unsigned)tab.first[nitems]), block(64 * RS_WAVES);
   uint64_t* partial = sums ? (uint64_t*)workspace : nullptr;
   if (out_type == PACE_RESTART_BE_F64)

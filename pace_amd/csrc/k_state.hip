@@ -8,22 +8,13 @@
 //                                      item and j for a plane, and never i, so the tile is transposed on its way;
 //   XFAST  e = i + ni * (j + nj * k)   Fortran order, which is the device's own: nothing to transpose.
 //
-//   k_state_unpack  1-D grid, 256 threads = 4 waves.  A workgroup takes one tile of SU_TI = 64 points in i by SU_TS = 32 points in
-//                   s (a 3-D item: at one j; so 32 levels), and finds its item by a bisection of the prefix table of per-item tile
-//                   counts, which travels by value with the items (workgroup-uniform: scalar loads and scalar branches only).  The
-//                   branch on the order is per item, hence uniform as well.
-//                   ZFAST  read    the tile's points flattened with s fastest over the 256 threads: runs of up to 32 contiguous
-//                                  doubles per i (256 B; with in_step = 7 every seventh double of a run of 1792 B), 8 points per
-//                                  thread.
-//                          LDS     tile[s][i] of the STORAGE type (narrowed before it is staged), pitch SU_PITCH = 65 elements.
-//                                  This is k_diag.hip's bank argument mirrored: here the transposed accesses are the WRITES, and
-//                                  a write's bank is (dword address) mod 32 (MI355X_MICROARCH.md, LDS).  ds_write_b32 goes in
-//                                  groups of 32 lanes: s = 0 .. 31 at one i, element address 65 * s + i, bank (s + i) mod 32 --
-//                                  32 different banks.  ds_write_b64 goes in groups of 16 lanes: s = 0 .. 15 (16 .. 31) at one i,
-//                                  dword address 130 * s + 2 * i, banks (2 * s + 2 * i) mod 32 and the one after it -- 16 different
-//                                  pairs.  A pitch of 64 would put a whole group on one bank (pair).  A tile narrower than 32
-//                                  in s (the last 15 of 79 levels) mixes two or three i in a group and takes up to 3 lanes per
-//                                  bank.  The row reads are 64 consecutive elements: conflict-free.
+//   k_state_unpack  1-D grid, 256 threads = 4 waves.  A workgroup takes one window tile (wgmap.h: 64 points in i by 32 in s) of
+//                   the item that table_find gives it; the table travels by value (pack_table.h).  The branch on the order is
+//                   per item, hence workgroup-uniform.
+//                   ZFAST  read    wt_runs_to_lds: runs of up to 32 contiguous doubles per i (256 B; with in_step = 7 every
+//                                  seventh double of a run of 1792 B).
+//                          LDS     tile[s][i] of the STORAGE type (narrowed before it is staged) at wgmap.h's pitch: here the
+//                                  transposed accesses are the writes.
 //                          write   wave w takes s = w, w + 4, ...; lane l writes i = l of that row: 64 contiguous elements.
 //                   XFAST  no LDS: wave w takes s = w, w + 4, ...; lane l reads and writes i = l: contiguous runs of up to 64
 //                          elements on both sides (in_step = 1).
@@ -44,44 +35,17 @@
 #include "common.h"
 #include "kernels.h"
 #include "lean_math.h"
+#include "pack_table.h"
 
-#define SU_TI 64
-#define SU_TS 32
-#define SU_WAVES 4
-#define SU_PITCH (SU_TI + 1)
+typedef PackTable<pace_unpack_item_t, PACE_UNPACK_MAX_ITEMS> UnpackTable;
 
-struct UnpackTable {
-  pace_unpack_item_t item[PACE_UNPACK_MAX_ITEMS];
-  int first[PACE_UNPACK_MAX_ITEMS + 1];  // first tile of each item; first[nitems] = the grid
-  int nitems;
-};
-
-// tiles of an item: s tiles fastest, then i tiles, then (3-D) the rows j
-static inline long unpack_tiles(const pace_unpack_item_t& it) {
-  const int ns = it.kind == PACE_DIAG_WINDOW3D ? it.nk : it.nj;
-  const long per_row = (long)((it.ni + SU_TI - 1) / SU_TI) * ((ns + SU_TS - 1) / SU_TS);
-  return it.kind == PACE_DIAG_WINDOW3D ? per_row * it.nj : per_row;
-}
-
-__global__ void __launch_bounds__(64 * SU_WAVES) k_state_unpack(Geo g, UnpackTable tab, const double* __restrict__ in) {
+__global__ void __launch_bounds__(64 * WT_WAVES) k_state_unpack(Geo g, UnpackTable tab, const double* __restrict__ in) {
   const int b = (int)blockIdx.x;
-  int m = 0, hi = tab.nitems;  // first[m] <= b < first[hi]
-  while (hi - m > 1) {
-    const int mid = (m + hi) >> 1;
-    if (b >= tab.first[mid]) m = mid;
-    else hi = mid;
-  }
+  const int m = table_find(tab.first, tab.nitems, b);
   const pace_unpack_item_t& it = tab.item[m];
   const bool vol = it.kind == PACE_DIAG_WINDOW3D;
-  const int ns = vol ? it.nk : it.nj;
-  const int nts = (ns + SU_TS - 1) / SU_TS, nti = (it.ni + SU_TI - 1) / SU_TI;
-  int t = b - tab.first[m];
-  const int sb = (t % nts) * SU_TS;
-  t /= nts;
-  const int ib = (t % nti) * SU_TI;
-  const int j = t / nti;  // the row of a 3-D item's tile; 0 for a plane
-  const int wi = it.ni - ib < SU_TI ? it.ni - ib : SU_TI;
-  const int ws = ns - sb < SU_TS ? ns - sb : SU_TS;
+  const WindowTile wt = window_tile_of_linear(b - tab.first[m], it.ni, it.nj, it.nk, vol, WT_TS);
+  const int sb = wt.sb, ib = wt.ib, j = wt.j, wi = wt.wi, ws = wt.ws;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const long step = it.in_step;
   const double* __restrict__ src = in + it.in_offset;
@@ -92,7 +56,7 @@ __global__ void __launch_bounds__(64 * SU_WAVES) k_state_unpack(Geo g, UnpackTab
     // source elements between s and s + 1 (a 3-D item: levels; a plane: rows), and the tile's first element
     const long sstride = vol ? (long)it.ni * it.nj : (long)it.ni;
     const long e0 = (vol ? (long)it.ni * j : 0L) + ib + lane;
-    for (int s = wave; s < ws; s += SU_WAVES) {
+    for (int s = wave; s < ws; s += WT_WAVES) {
       const real v = (real)src[(e0 + sstride * (sb + s)) * step];
       if (vol) q[IDX3(g, it.i0 + ib + lane, it.j0 + j, it.k0 + sb + s)] = v;
       else q[IDX2(g, it.i0 + ib + lane, it.j0 + sb + s)] = v;
@@ -100,18 +64,15 @@ __global__ void __launch_bounds__(64 * SU_WAVES) k_state_unpack(Geo g, UnpackTab
     return;
   }
 
-  __shared__ real tile[SU_TS * SU_PITCH];
+  __shared__ real tile[WT_TS * WT_PITCH];
   const long istride = vol ? (long)it.nj * it.nk : (long)it.nj;  // source elements between i and i + 1
   const long e0 = (vol ? (long)j * it.nk : 0L) + sb + (long)ib * istride;
-  for (int f = (int)threadIdx.x; f < wi * ws; f += 64 * SU_WAVES) {
-    const int li = f / ws, s = f - li * ws;
-    tile[s * SU_PITCH + li] = (real)src[(e0 + (long)li * istride + s) * step];
-  }
+  wt_runs_to_lds(tile, src + e0 * step, istride, step, wi, ws);
   __syncthreads();
   if (lane < wi) {
     const int i = it.i0 + ib + lane;
-    for (int s = wave; s < ws; s += SU_WAVES) {
-      const real v = tile[s * SU_PITCH + lane];
+    for (int s = wave; s < ws; s += WT_WAVES) {
+      const real v = tile[s * WT_PITCH + lane];
       if (vol) q[IDX3(g, i, it.j0 + j, it.k0 + sb + s)] = v;
       else q[IDX2(g, i, it.j0 + sb + s)] = v;
     }
@@ -121,14 +82,12 @@ __global__ void __launch_bounds__(64 * SU_WAVES) k_state_unpack(Geo g, UnpackTab
 int launch_state_unpack(const Geo& g, const pace_unpack_item_t* items, int nitems, const double* in, hipStream_t st) {
   UnpackTable tab{};
   tab.nitems = nitems;
-  long tiles = 0;
-  for (int m = 0; m < nitems; ++m) {
-    tab.item[m] = items[m];
-    tiles += unpack_tiles(items[m]);
-    if (tiles > 0x7fffffffL) return PACE_ERR_UNSUPPORTED;
-    tab.first[m + 1] = (int)tiles;
-  }
-  const dim3 grid((unsigned)tab.first[nitems]), block(64 * SU_WAVES);
+  for (int m = 0; m < nitems; ++m) tab.item[m] = items[m];
+  const int rc = pack_table_fill_first(tab, [](const pace_unpack_item_t& it) {
+    return window_tiles(it.ni, it.nj, it.nk, it.kind == PACE_DIAG_WINDOW3D, WT_TS);
+  });
+  if (rc != PACE_OK) return rc;
+  const dim3 grid((unsigned)tab.first[nitems]), block(64 * WT_WAVES);
   hipLaunchKernelGGL(k_state_unpack, grid, block, 0, st, g, tab, in);
   PACE_CHECK_LAUNCH();
   return PACE_OK;

@@ -79,3 +79,54 @@ WGMAP_FN FxBlock fxadv_block_of_workgroup(int b, int nbx_padded) {
   return FxBlock{(r & 7) * seg + (r >> 3), chunk};
 }
 WGMAP_FN bool fxadv_block_is_padding(const FxBlock& w, int nblocks) { return w.block >= nblocks; }
+
+// ---- the window tiles of the table-driven pack kernels (k_diag.hip, k_state.hip, k_gather.hip) -------------------------------
+// A window of a field ([k][j][i], i fastest) moves to or from a dense array whose fastest axis, called s, is never i: k of a 3-D
+// item (`vol`), j of a plane.  It is cut into tiles of WT_TI points in i by `ts` points in s (WT_TS; WT_TS_COLUMN for a column
+// integral, one row per wave), a 3-D item at one j per tile, numbered with the s tiles fastest, then the i tiles, then the rows j.
+// The host's tile count and the kernels' decomposition are these two functions and nothing else.
+//
+// The tile is transposed through LDS as tile[s][i] at a pitch of WT_PITCH = 65 elements (MI355X_MICROARCH.md, LDS: 64 banks of
+// 4 B; b32 goes in groups of 32 lanes, b64 in groups of 16 for writes).  The field side is rows of 64 consecutive elements:
+// conflict-free in both directions.  The dense side is s = 0 .. 31 at one i, element 65 s + i:
+//   reads (pack, gather)      ds_read_b32: bank (s + i) mod 32; ds_read_b64: 2 ((s + i) mod 32) of 64 -- 32 different banks;
+//   writes (unpack, scatter)  ds_write_b32: bank (s + i) mod 32 -- 32 different banks; ds_write_b64, s = 0 .. 15 (16 .. 31):
+//                             dword 130 s + 2 i, banks (2 s + 2 i) mod 32 and the one after it -- 16 different pairs.
+// A pitch of 64 would put a whole group on one bank (pair).  A tile narrower than 32 in s (the last 15 of 79 levels) mixes two
+// or three i in a group and takes up to 3 lanes per bank.
+#define WT_TI 64
+#define WT_TS 32
+#define WT_WAVES 4
+#define WT_TS_COLUMN WT_WAVES
+#define WT_PITCH (WT_TI + 1)
+
+WGMAP_FN long window_tiles(int ni, int nj, int nk, bool vol, int ts) {
+  const int ns = vol ? nk : nj;
+  const long per_row = (long)((ni + WT_TI - 1) / WT_TI) * ((ns + ts - 1) / ts);
+  return vol ? per_row * nj : per_row;
+}
+struct WindowTile {
+  int sb, ib;  // the tile's first point in s and in i, within the window
+  int j;       // the row of a 3-D item's tile; 0 for a plane
+  int wi, ws;  // its points in i (1 .. WT_TI) and in s (1 .. ts)
+};
+WGMAP_FN WindowTile window_tile_of_linear(int t, int ni, int nj, int nk, bool vol, int ts) {
+  const int ns = vol ? nk : nj;
+  const int nts = (ns + ts - 1) / ts, nti = (ni + WT_TI - 1) / WT_TI;
+  const int sb = (t % nts) * ts;
+  t /= nts;
+  const int ib = (t % nti) * WT_TI;
+  return WindowTile{sb, ib, t / nti, ni - ib < WT_TI ? ni - ib : WT_TI, ns - sb < ts ? ns - sb : ts};
+}
+
+// ---- the item of a workgroup: m with first[m] <= b < first[m + 1] in a prefix table first[0 .. n] of per-item counts >= 1 ------
+// (b is the same for a whole workgroup and first[] is read-only: scalar loads and scalar branches, ceil(log2 n) of them)
+WGMAP_FN int table_find(const int* first, int n, int b) {
+  int m = 0, hi = n;  // first[m] <= b < first[hi]
+  while (hi - m > 1) {
+    const int mid = (m + hi) >> 1;
+    if (b >= first[mid]) m = mid;
+    else hi = mid;
+  }
+  return m;
+}

@@ -28,7 +28,7 @@ from .. import _lib
 from . import constants as c
 from .quantity import Quantity, QuantityFactory, SubtileGridSizer
 
-CUBE_TILE_I, CUBE_TILE_S = 64, 32  # pace_amd/csrc/k_gather.hip CG_TI, CG_TS
+CUBE_TILE_I, CUBE_TILE_S = 64, 32  # pace_amd/csrc/wgmap.h WT_TI, WT_TS (tests/test_cube_gather.py holds them together)
 TABLE_CACHE = 8  # device tables kept per communicator
 _TORCH_OF = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32}
 

@@ -4,7 +4,9 @@
 // launch's pieces of work, each once -- none skipped, none repeated, none outside.  For the padded launch of the flux preparation
 // the pieces are the nblocks real blocks of every chunk: each is taken once, and the other workgroups of the launch -- exactly
 // (padded - nblocks) per chunk -- get block numbers in [nblocks, padded), whose points lie past the plane's last row, so the
-// kernel's box test returns them (k_fxadv.hip; fxadv_block_is_padding is that comparison by name, nothing more).  Prints the
+// kernel's box test returns them (k_fxadv.hip; fxadv_block_is_padding is that comparison by name, nothing more).  For the window
+// tiles of the pack kernels the pieces are the points (i, j, s) of the window: the tiles 0 .. window_tiles - 1 cover each once and
+// stay inside it.  table_find is held against a linear scan of the prefix table.  Prints the
 // first offending shape and workgroup and exits 1; prints one summary line per map and exits 0 otherwise.
 //
 //   wgmap_check            the full ranges
@@ -107,6 +109,64 @@ bool check_fx(int nblocks, int nchunks) {
   return true;
 }
 
+// ---- the pack kernels' window tiles: ni x nj x ns points (a plane: nj = 1 rows of its own, s = j), `rows` per tile in s ----
+bool check_window(int ni, int nj, int ns, bool vol, int rows) {
+  // (a plane's s axis is its nj, and its nk is 1)
+  const int wnj = vol ? nj : ns, wnk = vol ? ns : 1;
+  const long count = window_tiles(ni, wnj, wnk, vol, rows);
+  g_seen.assign((size_t)ni * (size_t)nj * (size_t)ns, 0);
+  long points = 0;
+  for (int t = 0; t < (int)count; ++t) {
+    const WindowTile w = window_tile_of_linear(t, ni, wnj, wnk, vol, rows);
+    const bool inside = w.wi >= 1 && w.wi <= WT_TI && w.ws >= 1 && w.ws <= rows && w.ib >= 0 && w.ib + w.wi <= ni && w.sb >= 0 &&
+                        w.sb + w.ws <= ns && w.j >= 0 && w.j < nj;
+    if (!inside) {
+      std::printf("window_tile_of_linear: ni %d nj %d ns %d 3-D %d rows %d: tile %d -> sb %d ib %d j %d wi %d ws %d leaves the window\n", ni,
+                  nj, ns, (int)vol, rows, t, w.sb, w.ib, w.j, w.wi, w.ws);
+      return false;
+    }
+    for (int i = w.ib; i < w.ib + w.wi; ++i)
+      for (int s = w.sb; s < w.sb + w.ws; ++s) {
+        unsigned char& seen = g_seen[(size_t)s + (size_t)ns * ((size_t)w.j + (size_t)nj * (size_t)i)];
+        if (seen) {
+          std::printf("window_tile_of_linear: ni %d nj %d ns %d 3-D %d rows %d: tile %d takes (%d, %d, %d) again\n", ni, nj, ns, (int)vol,
+                      rows, t, i, w.j, s);
+          return false;
+        }
+        seen = 1;
+        ++points;
+      }
+  }
+  if (points != (long)ni * nj * ns) {
+    std::printf("window_tiles: ni %d nj %d ns %d 3-D %d rows %d: %ld tiles hold %ld of %ld points\n", ni, nj, ns, (int)vol, rows, count,
+                points, (long)ni * nj * ns);
+    return false;
+  }
+  g_workgroups += count;
+  return true;
+}
+
+// ---- the table search: n items with counts >= 1 from a fixed generator; every b below the total against a linear scan ----
+bool check_find(int n, unsigned seed) {
+  std::vector<int> first((size_t)n + 1, 0);
+  for (int m = 0; m < n; ++m) {
+    seed = seed * 1664525u + 1013904223u;
+    const int count = 1 + (int)((seed >> 16) % ((seed >> 8) % 3 == 0 ? 40u : 3u));  // mostly 1 .. 3, a third up to 40
+    first[(size_t)m + 1] = first[(size_t)m] + count;
+  }
+  for (int b = 0; b < first[(size_t)n]; ++b) {
+    int want = 0;
+    while (first[(size_t)want + 1] <= b) ++want;
+    const int got = table_find(first.data(), n, b);
+    if (got != want) {
+      std::printf("table_find: %d items, seed %u: workgroup %d -> item %d, a linear scan gives %d\n", n, seed, b, got, want);
+      return false;
+    }
+  }
+  g_workgroups += first[(size_t)n];
+  return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -163,6 +223,21 @@ int main(int argc, char** argv) {
     for (int nchunks = 1; nchunks <= 130; nchunks += step, ++shapes)
       if (!check_fx(nblocks, nchunks)) return 1;
   std::printf("fxadv_block_of_workgroup: %lld launch shapes, every real (block, chunk) once, the rest past the last block\n", shapes);
+  // window tiles: every ni 1 .. 200 (three tiles and a partial fourth) with every ns 1 .. 100, 32 and 4 rows per tile; a plane,
+  // and a 3-D item of 1 .. 3 rows j (per j identical: three rows catch a wrong carry between ib and j)
+  shapes = 0;
+  for (int rows : {WT_TS, WT_TS_COLUMN})
+    for (int ni = 1; ni <= 200; ++ni)
+      for (int ns = 1; ns <= 100; ns += step)
+        for (int nj = 0; nj <= 3; ++nj, ++shapes)  // 0: the plane
+          if (!check_window(ni, nj == 0 ? 1 : nj, ns, nj != 0, rows)) return 1;
+  std::printf("window_tile_of_linear: %lld windows, every point once, every tile inside\n", shapes);
+  // the table search: every item count 1 .. 33 with eight tables each
+  shapes = 0;
+  for (int n = 1; n <= 33; ++n)
+    for (unsigned seed = 1; seed <= 8; ++seed, ++shapes)
+      if (!check_find(n, seed * 2654435761u + (unsigned)n)) return 1;
+  std::printf("table_find: %lld tables, every workgroup as a linear scan\n", shapes);
   std::printf("wgmap_check ok: %lld workgroups\n", g_workgroups);
   return 0;
 }

@@ -5,7 +5,8 @@ storages between the fields and one dense buffer in (x, y, z) C order.
   everywhere else): C12, C13 (13 + 1 interface points: a partial 64-wide tile) and C68 (two tiles in i, one partial); 1, 7, 33
   and 79 levels (a partial and full 32-level tiles); centred, x-, y- and z-interface windows, planes of a 2-D field and of one
   level, a window that starts in the halo, and 40 items in one call spread over the six storages; both libraries and both dense
-  types; -0.0, NaN (with a payload), inf and a denormal;
+  types; -0.0, NaN (with a payload), inf and a denormal; and the whole storages of six C68 x 79 fields, 2700 tiles for a grid
+  capped at 2048 workgroups, so that 652 workgroups take a second tile and reuse their LDS;
 * scatter after gather is the identity on the windows;
 * what the host refuses (pace_amd.util.gather.check_cube_items) and what the entry point refuses.
 
@@ -95,6 +96,8 @@ def item_list(s, many=False):
 
     n, nz = s.n, s.nz
     W, P = _lib.DIAG_WINDOW3D, _lib.DIAG_PLANE
+    if many == "whole":  # the whole storage of each 3-D field: at C68 x 79, 2 x 3 x 75 = 450 tiles each, 2700 past the grid's 2048
+        return [(f, None, W, (0, 0, 0, n + 7, n + 7, nz + 1)) for f in range(6)]
     if many:  # 40 items, past the old cap of 32 of the by-value tables: rows of two, seven per storage
         out = []
         for m in range(40):
@@ -205,6 +208,7 @@ def check_kernel(device, only=None):
                 assert kernel_case(lib, device, n, nz, dense_dtype, False, seed) == 8
             assert kernel_case(lib, device, 12, 7, dense_dtype, True, seed) == 40
             assert kernel_case(lib, device, 68, 33, dense_dtype, True, seed) == 40
+            assert kernel_case(lib, device, 68, 79, dense_dtype, "whole", seed) == 6
 
 
 def check_round_trip(device):
@@ -314,6 +318,23 @@ def test_header_and_binding_agree_on_the_entry_points():
     names = re.findall(r"(\w+)\s*[;,]", re.sub(r"/\*.*?\*/", "", body))
     assert names == [name for name, _ in _lib.CubeItem._fields_]
     assert C.sizeof(_lib.CubeItem) == 48
+    # the tile of the prefix table behind the items: the kernel's constants (csrc/wgmap.h) and their Python mirror
+    from types import SimpleNamespace
+
+    from pace_amd.util import gather
+
+    maps = open(os.path.join(ROOT, "pace_amd", "csrc", "wgmap.h")).read()
+    ti, ts = (int(re.search(rf"^#define {name} (\d+)$", maps, re.M).group(1)) for name in ("WT_TI", "WT_TS"))
+    assert (ti, ts) == (gather.CUBE_TILE_I, gather.CUBE_TILE_S) == (64, 32)
+    for n, nz in CASES + ((68, 79),):
+        for many in (False, True, "whole"):
+            for _, _, kind, (_, _, _, ni, nj, nk) in item_list(SimpleNamespace(n=n, nz=nz), many):
+                x = _lib.CubeItem()
+                x.kind, x.ni, x.nj, x.nk = kind, ni, nj, nk
+                volume = kind == _lib.DIAG_WINDOW3D
+                want = ((ni + ti - 1) // ti) * (((nk if volume else nj) + ts - 1) // ts) * (nj if volume else 1)
+                assert gather.cube_tiles(x) == want, (n, nz, many, kind, ni, nj, nk)
+    assert sum(gather.cube_tiles(SimpleNamespace(kind=_lib.DIAG_WINDOW3D, ni=75, nj=75, nk=80)) for _ in range(6)) == 2700 > 2048
 
 
 # ---- the GPU tier: each check in a child process with a time limit --------------------------------------------------------------

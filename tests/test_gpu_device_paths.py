@@ -46,7 +46,13 @@ def test_workgroup_maps_are_bijections_exhaustively(build):
       * flux preparation (k_fxadv.hip): blocks = ceil(row stride x rows / 1024): 1 at C12, 41 at C192, 153 at C384; chunks =
         ceil(nk / ch) with ch = 1 on small tiles, so up to 128 chunks (C12 x 79: 79).  Checked: every block count 1 .. 160 with
         every chunk count 1 .. 130.  What is proved there: every real (block, chunk) is taken once and the launch's other
-        workgroups, (padded - blocks) per chunk, get block numbers past the last real one, which the kernel's box test returns."""
+        workgroups, (padded - blocks) per chunk, get block numbers past the last real one, which the kernel's box test returns.
+      * the window tiles of the pack kernels (k_diag.hip, k_state.hip, k_gather.hip): 64 points in i by 32 (a column integral: 4)
+        in the dense side's fastest axis s; a storage is at most 391 points wide and 129 levels deep, and the map depends on a
+        width through ceil(ni / 64) and ni % 64 only.  Checked: every ni 1 .. 200 (three tiles and a partial fourth) with every
+        ns 1 .. 100, as a plane and as a 3-D item of 1 .. 3 rows j (per j identical), with 32 and 4 rows per tile: the tiles
+        0 .. window_tiles - 1 hold every point of the window once and none outside it.
+      * table_find against a linear scan: tables of 1 .. 33 items (the by-value tables hold 32), eight each, every workgroup."""
     plain, sanitized = build_wgmap_check()
     p = subprocess.run([plain if build == "plain" else sanitized], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
