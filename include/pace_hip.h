@@ -606,6 +606,43 @@ typedef struct {
 int pace_diag_pack(const pace_geom_t* geom, const pace_diag_item_t* items, int nitems, int out_is_double, void* out,
                    void* stream);
 
+/* ---- Pressure-level diagnostics (`p_select`; this project's extension, the reference stops at z_select): up to
+ * PACE_PLEV_MAX_ITEMS planes -- layer fields and the geometric height on up to PACE_PLEV_MAX_LEVELS pressure surfaces --
+ * interpolated linearly in log p and written to one packed device buffer by ONE launch, both storage types, no atomics, no
+ * workspace, no host synchronisation.  peln: the state's log interface pressures, nk + 1 levels of ln(Pa); log_p: HOST array of
+ * nlevels natural logs of the target pressures (the kernel has no transcendental); items: HOST array of nitems items; one
+ * horizontal window (i0, j0, ni, nj) serves all items; out: DEVICE array of float32, or of float64 where out_is_double != 0;
+ * an item's output is out[out_offset + i * nj + j], (x, y) in C order like a PACE_DIAG_PLANE.  All arithmetic is in double on
+ * the stored values (the float32 library widens first), without FMA, in exactly this order, with lp = log_p[level], nz = nk:
+ *   PACE_PLEV_LAYER   a cell-centre (x, y, z) field f; pm[k] = 0.5 * (peln[k] + peln[k + 1]);
+ *                       kb = the largest k in 1 .. nz - 2 with pm[k] <= lp, 0 if there is none
+ *                       if   not (lp > pm[0]):   f[0]
+ *                       elif lp >= pm[nz - 1]:   f[nz - 1]                                (clamped: no extrapolation)
+ *                       else: t = (lp - pm[kb]) / (pm[kb + 1] - pm[kb]);  f[kb] + (f[kb + 1] - f[kb]) * t
+ *   PACE_PLEV_HEIGHT  geometric height [m] from field = delz and surface = phis:
+ *                       zi[nz] = phis * RGRAV;  zi[k] = zi[k + 1] - delz[k], k = nz - 1 .. 0
+ *                       kb = the largest k in 1 .. nz - 1 with peln[k] <= lp, 0 if there is none
+ *                       t = (lp - peln[kb]) / (peln[kb + 1] - peln[kb]);  zi[kb] + (zi[kb + 1] - zi[kb]) * t
+ *                     (extrapolated with the top layer's slope above the model top, with the lowest layer's below the ground)
+ * The definitions are total: every comparison with a NaN is false, and a non-monotone or NaN column yields a value by these
+ * rules.  Nothing outside the window's columns is read and nothing outside an item's ni * nj output elements is written.
+ * PACE_ERR_ARG: nlevels < 1 or > PACE_PLEV_MAX_LEVELS, nitems < 1 or > PACE_PLEV_MAX_ITEMS, an unknown kind, a level outside
+ * 0 .. nlevels - 1, an item without field, a HEIGHT item without surface, geom->nk < 2, a window that is empty or outside the
+ * storage (n + 7, n + 7), a negative out_offset. */
+#define PACE_PLEV_MAX_ITEMS 32
+#define PACE_PLEV_MAX_LEVELS 8
+enum { PACE_PLEV_LAYER = 0, PACE_PLEV_HEIGHT = 1 };
+typedef struct {
+  const pace_real_t* field;   /* LAYER: the 3-D field; HEIGHT: delz */
+  const pace_real_t* surface; /* HEIGHT: phis (2-D); LAYER: NULL */
+  int32_t kind;               /* PACE_PLEV_LAYER | PACE_PLEV_HEIGHT */
+  int32_t level;              /* index into log_p[] */
+  int64_t out_offset;         /* in output elements */
+} pace_plev_item_t;
+int pace_plev_diag(const pace_geom_t* geom, const pace_real_t* peln, const double* log_p, int nlevels,
+                   const pace_plev_item_t* items, int nitems, int i0, int j0, int ni, int nj, int out_is_double, void* out,
+                   void* stream);
+
 /* ---- A host model's arrays into the state (fv3core/pace/fv3core/initialization/geos_wrapper.py:207-270): the inverse of
  * pace_diag_pack.  Up to PACE_UNPACK_MAX_ITEMS windows of fields are filled from one packed device buffer by ONE launch, both
  * storage types, no atomics, no workspace, no host synchronisation.  items: HOST array of nitems items; in: DEVICE array of

@@ -140,6 +140,14 @@ class DiagItem(C.Structure):  # include/pace_hip.h pace_diag_item_t
                 ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("out_offset", C.c_int64)]
 
 
+PLEV_MAX_ITEMS, PLEV_MAX_LEVELS = 32, 8  # include/pace_hip.h PACE_PLEV_MAX_ITEMS, PACE_PLEV_MAX_LEVELS
+PLEV_LAYER, PLEV_HEIGHT = 0, 1  # include/pace_hip.h PACE_PLEV_*
+
+
+class PlevItem(C.Structure):  # include/pace_hip.h pace_plev_item_t
+    _fields_ = [("field", c_dp), ("surface", c_dp), ("kind", C.c_int32), ("level", C.c_int32), ("out_offset", C.c_int64)]
+
+
 UNPACK_MAX_ITEMS = 32  # include/pace_hip.h PACE_UNPACK_MAX_ITEMS
 ORDER_ZFAST, ORDER_XFAST = 0, 1  # include/pace_hip.h PACE_ORDER_*
 
@@ -275,6 +283,7 @@ _PROTOS = {
     "pace_state_extrema_workspace_bytes": (C.c_int64, [_P(Geom)]),
     "pace_state_extrema": (C.c_int, [_P(Geom), _P(C.c_void_p), _P(C.c_int), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_diag_pack": (C.c_int, [_P(Geom), _P(DiagItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pace_plev_diag": (C.c_int, [_P(Geom), c_dp, _P(C.c_double), C.c_int, _P(PlevItem)] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
     "pace_state_unpack": (C.c_int, [_P(Geom), _P(UnpackItem), C.c_int, c_dp, C.c_void_p]),
     "pace_restart_pack_workspace_bytes": (C.c_int64, [_P(Geom), _P(RestartItem), C.c_int]),
     "pace_restart_pack": (C.c_int, [_P(Geom), _P(RestartItem), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -700,6 +700,21 @@ int pace_diag_pack(const pace_geom_t* geom, const pace_diag_item_t* items, int n
   return launch_diag_pack(make_geo(geom), items, nitems, out_is_double, out, S(stream));
 }
 
+int pace_plev_diag(const pace_geom_t* geom, const real* peln, const double* log_p, int nlevels, const pace_plev_item_t* items,
+                   int nitems, int i0, int j0, int ni, int nj, int out_is_double, void* out, void* stream) {
+  NEED(geom && peln && log_p && items && out);
+  if (nlevels < 1 || nlevels > PACE_PLEV_MAX_LEVELS || nitems < 1 || nitems > PACE_PLEV_MAX_ITEMS || geom->nk < 2) return PACE_ERR_ARG;
+  const int side = geom->n + 7;
+  if (i0 < 0 || ni < 1 || ni > side - i0 || j0 < 0 || nj < 1 || nj > side - j0) return PACE_ERR_ARG;
+  for (int m = 0; m < nitems; ++m) {
+    const pace_plev_item_t& it = items[m];
+    if (it.kind != PACE_PLEV_LAYER && it.kind != PACE_PLEV_HEIGHT) return PACE_ERR_ARG;
+    if (!it.field || (it.kind == PACE_PLEV_HEIGHT && !it.surface)) return PACE_ERR_ARG;
+    if (it.level < 0 || it.level >= nlevels || it.out_offset < 0) return PACE_ERR_ARG;
+  }
+  return launch_plev_diag(make_geo(geom), peln, log_p, nlevels, items, nitems, i0, j0, ni, nj, out_is_double, out, S(stream));
+}
+
 int pace_state_unpack(const pace_geom_t* geom, const pace_unpack_item_t* items, int nitems, const double* in, void* stream) {
   NEED(geom && items && in);
   if (nitems < 1 || nitems > PACE_UNPACK_MAX_ITEMS) return PACE_ERR_ARG;

@@ -282,6 +282,9 @@ int launch_state_extrema(const Geo& g, const real* const* fields, const int* com
                          double* out, hipStream_t st);
 // k_diag.hip
 int launch_diag_pack(const Geo& g, const pace_diag_item_t* items, int nitems, int out_is_double, void* out, hipStream_t st);
+// k_plev.hip
+int launch_plev_diag(const Geo& g, const real* peln, const double* log_p, int nlevels, const pace_plev_item_t* items, int nitems,
+                     int i0, int j0, int ni, int nj, int out_is_double, void* out, hipStream_t st);
 // k_gather.hip
 int launch_cube_xfer(const Geo& g, const pace_cube_item_t* table_on_device, int n, int dense_is_double, void* dense, int scatter,
                      hipStream_t st);

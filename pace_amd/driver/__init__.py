@@ -24,6 +24,7 @@ from .diagnostics import (  # noqa: F401
     MonitorDiagnostics,
     NpzMonitor,
     NullDiagnostics,
+    PSelect,
     WindowPacker,
     ZSelect,
 )

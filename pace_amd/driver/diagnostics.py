@@ -17,11 +17,17 @@ is written as a whole: a store is ONE pace_cube_gather launch for all six tiles 
 are joined on the host, and rank 0 alone writes -- one file per time chunk with a tile axis of 6, as npz (NpzMonitor) or as
 NetCDF-3 (`output_format: netcdf`, pace_amd.util.NetCDFMonitor).  Per-rank communicators (one process per tile, a lone tile)
 keep their per-tile npz files with a tile axis of 1, and `netcdf` writes nothing there; `zarr` writes nothing anywhere.
+
+Fields on pressure surfaces (`p_select`: pt_p850, height_p500, ...; this project's extension, the reference stops at z_select)
+are interpolated on the device by pace_plev_diag (pace_amd/csrc/k_plev.hip), one launch per PACE_PLEV_MAX_LEVELS pressures and
+PACE_PLEV_MAX_ITEMS planes, into the same packed buffer: a step is still one transfer and one synchronisation, and a plane is
+1 / nz of the volume a host-side interpolation would need.
 """
 import abc
 import ctypes as C
 import dataclasses
 import json
+import math
 import os
 import warnings
 from datetime import datetime, timedelta
@@ -79,6 +85,36 @@ class ZSelect:
         return output
 
 
+HEIGHT = "height"  # p_select's pseudo-name: the geometric height of the pressure surface, from phis and delz
+
+
+@dataclasses.dataclass
+class PSelect:
+    """Variables on one pressure surface [Pa], interpolated linearly in log p from the state's own peln (include/pace_hip.h,
+    pace_plev_diag): `<name>_p<pressure / 100:g>`, e.g. pt_p850, height_p500."""
+
+    pressure: float
+    names: List[str]
+
+    def __post_init__(self):
+        if not self.pressure > 0:
+            raise ValueError(f"p_select of {', '.join(self.names)}: the pressure must be positive, got {self.pressure!r} Pa")
+
+    def output_name(self, name: str) -> str:
+        return f"{name}_p{self.pressure / 100:g}"
+
+    def variable(self, state, name: str) -> Quantity:
+        """The state's cell-centre variable `name` (`height`: delz, which the height is summed from)."""
+        field = "delz" if name == HEIGHT else name
+        quantity = getattr(state, field, None) if field in getattr(state, "__dict__", {}) else None
+        if quantity is None:
+            raise ValueError(f"Invalid state variable {name} for pressure level select")
+        if tuple(quantity.dims) != (c.X_DIM, c.Y_DIM, c.Z_DIM):
+            raise ValueError(f"p_select only works for state variables with dimension (x, y, z) and for `{HEIGHT}`. \n {name} has "
+                             f"dimension {quantity.dims}")
+        return quantity
+
+
 @dataclasses.dataclass
 class DiagnosticsConfig:
     """
@@ -91,6 +127,7 @@ class DiagnosticsConfig:
         names: state variables to save as diagnostics
         derived_names: derived diagnostics to save
         z_select: save a vertical slice of a 3D state
+        p_select: save state variables, or `height`, on pressure surfaces (this project's extension)
     """
 
     path: Optional[str] = None
@@ -99,9 +136,10 @@ class DiagnosticsConfig:
     names: List[str] = dataclasses.field(default_factory=list)
     derived_names: List[str] = dataclasses.field(default_factory=list)
     z_select: List[ZSelect] = dataclasses.field(default_factory=list)
+    p_select: List[PSelect] = dataclasses.field(default_factory=list)
 
     def __post_init__(self):
-        if (len(self.names) > 0 or len(self.derived_names) > 0) and self.path is None:
+        if (len(self.names) > 0 or len(self.derived_names) > 0 or len(self.p_select) > 0) and self.path is None:
             raise ValueError("DiagnosticsConfig.path must be given to enable diagnostics")
         if self.output_format not in _OUTPUT_FORMATS:
             raise ValueError(f"output_format must be one of 'zarr', 'netcdf' or 'npz', got {self.output_format}")
@@ -134,7 +172,7 @@ class DiagnosticsConfig:
             monitor = NpzMonitor(self.path, tile=communicator.partitioner.tile_index(communicator.rank),
                                  time_chunk_size=self.time_chunk_size)
         return MonitorDiagnostics(monitor=monitor, names=self.names, derived_names=self.derived_names, z_select=self.z_select,
-                                  lib=lib, communicator=communicator if whole_cube(communicator) else None)
+                                  lib=lib, communicator=communicator if whole_cube(communicator) else None, p_select=self.p_select)
 
     @classmethod
     def from_dict(cls, config) -> "DiagnosticsConfig":
@@ -142,7 +180,11 @@ class DiagnosticsConfig:
 
         if isinstance(config, cls):
             return config
-        out = _strict(cls, "diagnostics_config", dict(config or {}))
+        config = dict(config or {})
+        # (parsed before the constructor sees them: a pressure that is no number is named as the setting it is)
+        config["p_select"] = [p if isinstance(p, PSelect) else _strict(PSelect, "diagnostics_config.p_select", p)
+                              for p in config.get("p_select") or []]
+        out = _strict(cls, "diagnostics_config", config)
         out.z_select = [z if isinstance(z, ZSelect) else _strict(ZSelect, "diagnostics_config.z_select", z) for z in out.z_select]
         return out
 
@@ -183,6 +225,39 @@ class _Request:
         ni, nj, nk = self.window[3:]
         return (ni, nj, nk) if self.kind == _lib.DIAG_WINDOW3D else (ni, nj)
 
+    @property
+    def tensors(self):
+        return [self.field.data] + ([self.weight.data] if self.weight is not None else [])
+
+    @property
+    def packed_by_rank(self):
+        """Under a whole-cube communicator: does every rank pack this itself (the windows and planes are gathered)?"""
+        return self.kind == _lib.DIAG_COLUMN_INTEGRAL
+
+
+@dataclasses.dataclass
+class _PlevRequest:
+    """One plane on a pressure surface: what pace_plev_diag is asked for and what the monitor is told about it."""
+
+    name: str
+    kind: int  # _lib.PLEV_LAYER | _lib.PLEV_HEIGHT
+    field: Quantity  # LAYER: the field; HEIGHT: delz
+    surface: Optional[Quantity]  # HEIGHT: phis
+    peln: Quantity
+    log_p: float
+    window: tuple  # (i0, j0, ni, nj)
+    dims: tuple
+    units: str
+    packed_by_rank = True
+
+    @property
+    def shape(self):
+        return tuple(self.window[2:])
+
+    @property
+    def tensors(self):
+        return [self.field.data, self.peln.data] + ([self.surface.data] if self.surface is not None else [])
+
 
 def _layout(t):
     """(n, sj, nk or None, sk or None) of a 2-D or 3-D field of the library's layout."""
@@ -195,7 +270,8 @@ def _layout(t):
 
 
 class WindowPacker:
-    """Windows of fields to the host: ONE pace_diag_pack launch per PACE_DIAG_MAX_ITEMS requests, ONE transfer of the packed
+    """Windows of fields to the host: ONE pace_diag_pack launch per PACE_DIAG_MAX_ITEMS requests, ONE pace_plev_diag launch per
+    PACE_PLEV_MAX_LEVELS pressures and PACE_PLEV_MAX_ITEMS planes on them, all into one packed buffer, ONE transfer of that
     buffer to pinned host memory and ONE synchronisation.  What MonitorDiagnostics stores with, and what
     pace_amd.fv3core.GeosDycoreWrapper hands a host model its arrays with."""
 
@@ -205,7 +281,7 @@ class WindowPacker:
         self._plans = {}  # what is asked for, where and as which type -> (geometry, offsets, device buffer, host buffer)
 
     def _plan(self, requests, out_is_double):
-        tensors = [r.field.data for r in requests] + [r.weight.data for r in requests if r.weight is not None]
+        tensors = [t for r in requests for t in r.tensors]
         layouts = [_layout(t) for t in tensors]
         n, sj = layouts[0][:2]
         levels = {(nk, sk) for _, _, nk, sk in layouts if nk is not None}
@@ -213,7 +289,7 @@ class WindowPacker:
             raise ValueError("diagnostics take fields of one layout and type on one device")
         nk, sk = levels.pop() if levels else (1, sj * (n + 7))
         device = tensors[0].device
-        key = (device, n, nk, sj, sk, bool(out_is_double), tuple((r.name, r.kind, r.window) for r in requests))
+        key = (device, n, nk, sj, sk, bool(out_is_double), tuple((r.name, type(r), r.kind, r.window, getattr(r, "log_p", None)) for r in requests))
         if key not in self._plans:
             offsets, total = [], 0
             for r in requests:
@@ -224,6 +300,34 @@ class WindowPacker:
             host = torch.empty(total, dtype=dtype, pin_memory=device.type != "cpu")
             self._plans[key] = (_lib.Geom(n, nk, sj, 0, sk), offsets, packed, host)
         return self._plans[key]
+
+    @staticmethod
+    def _plev_launches(placed):
+        """The pressure-level requests cut into launches, in their order: one log interface pressure and one window, at most
+        PACE_PLEV_MAX_LEVELS different pressures and PACE_PLEV_MAX_ITEMS planes each."""
+        launches, key, levels = [], None, set()
+        for r, offset in placed:
+            this = (r.peln.ptr, r.window)
+            if (this != key or len(launches[-1]) == _lib.PLEV_MAX_ITEMS
+                    or (r.log_p not in levels and len(levels) == _lib.PLEV_MAX_LEVELS)):
+                launches.append([])
+                key, levels = this, set()
+            levels.add(r.log_p)
+            launches[-1].append((r, offset))
+        return launches
+
+    @staticmethod
+    def _plev_arguments(geom, chunk, out_is_double, packed, stream):
+        """pace_plev_diag's arguments for one launch's requests and their places in the packed buffer."""
+        log_p = sorted({r.log_p for r, _ in chunk})
+        items = (_lib.PlevItem * len(chunk))()
+        for item, (r, offset) in zip(items, chunk):
+            item.field = r.field.ptr  # (the pointers of THIS call's storages)
+            item.surface = r.surface.ptr if r.surface is not None else None
+            item.kind, item.level, item.out_offset = r.kind, log_p.index(r.log_p), offset
+        peln, window = chunk[0][0].peln, chunk[0][0].window
+        return (C.byref(geom), peln.ptr, (C.c_double * len(log_p))(*log_p), len(log_p), items, len(chunk), *window,
+                int(bool(out_is_double)), C.c_void_p(packed.data_ptr()), stream)
 
     def _to_host(self, packed, host):
         """The step's one transfer and one synchronisation."""
@@ -247,10 +351,12 @@ class WindowPacker:
         if emu != ("emulation" in self._lib.version()):
             raise _lib.PaceError("CPU tensors go with the emulation test library, device tensors with the product library")
         stream = None if emu else C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
-        for first in range(0, len(requests), _lib.DIAG_MAX_ITEMS):
-            chunk = requests[first:first + _lib.DIAG_MAX_ITEMS]
+        placed = list(zip(requests, offsets))
+        windows = [(r, offset) for r, offset in placed if not isinstance(r, _PlevRequest)]
+        for first in range(0, len(windows), _lib.DIAG_MAX_ITEMS):
+            chunk = windows[first:first + _lib.DIAG_MAX_ITEMS]
             items = (_lib.DiagItem * len(chunk))()
-            for item, r, offset in zip(items, chunk, offsets[first:]):
+            for item, (r, offset) in zip(items, chunk):
                 item.field = r.field.ptr + r.level * geom.sk * self._lib.real_bytes  # (the pointers of THIS call's storages)
                 item.weight = r.weight.ptr if r.weight is not None else None
                 item.kind = r.kind
@@ -258,6 +364,8 @@ class WindowPacker:
                 item.out_offset = offset
             self._lib.call("pace_diag_pack", C.byref(geom), items, len(chunk), int(bool(out_is_double)),
                            C.c_void_p(packed.data_ptr()), stream)
+        for chunk in self._plev_launches([(r, offset) for r, offset in placed if isinstance(r, _PlevRequest)]):
+            self._lib.call("pace_plev_diag", *self._plev_arguments(geom, chunk, out_is_double, packed, stream))
         self._to_host(packed, host)
         out = {}
         for r, offset in zip(requests, offsets):
@@ -269,7 +377,8 @@ class WindowPacker:
 class MonitorDiagnostics(Diagnostics, WindowPacker):
     """Diagnostics that save to a sympl-style Monitor."""
 
-    def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None, communicator=None):
+    def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None, communicator=None,
+                 p_select=()):
         """
         Args:
             monitor: a sympl-style Monitor object
@@ -279,11 +388,13 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
             lib: the library the state's fields belong to (default: the product library, loaded at the first store)
             communicator: a communicator that holds the whole cube (run_cube): every store is gathered over it and only its
                 root hands the monitor anything -- quantities that lead with TILE_DIM.  None: this rank's tile alone
+            p_select: the pressure surfaces to save variables of the dycore state (or `height`) on
         """
         self.communicator = communicator
         self.names = names
         self.derived_names = derived_names
         self.z_select = z_select
+        self.p_select = list(p_select)
         self.monitor = monitor
         WindowPacker.__init__(self, lib)
 
@@ -299,8 +410,8 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
         raise ValueError(f"{name} has dimensions {quantity.dims}: diagnostics take 2-D and 3-D variables")
 
     def _requests(self, state) -> List[_Request]:
-        """The reference's order (diagnostics.py:166-178): names, derived names, level selections.  The Quantities are looked up
-        at every call: Quantity.swap_storage replaces storages during a step."""
+        """The reference's order (diagnostics.py:166-178): names, derived names, level selections; then the pressure levels.  The
+        Quantities are looked up at every call: Quantity.swap_storage replaces storages during a step."""
         requests = []
         for name in self.names:
             try:
@@ -326,18 +437,28 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
                 window = tuple(quantity.origin[:2]) + (0,) + tuple(quantity.extent[:2]) + (1,)
                 requests.append(_Request(f"{name}_z{zselect.level}", _lib.DIAG_PLANE, quantity, None, zselect.level, window,
                                          tuple(quantity.dims[:2]), quantity.units))
+        for pselect in self.p_select:
+            for name in pselect.names:
+                dycore = state.dycore_state
+                quantity = pselect.variable(dycore, name)
+                height = name == HEIGHT
+                window = tuple(quantity.origin[:2]) + tuple(quantity.extent[:2])
+                requests.append(_PlevRequest(pselect.output_name(name), _lib.PLEV_HEIGHT if height else _lib.PLEV_LAYER, quantity,
+                                             dycore.phis if height else None, dycore.peln, math.log(pselect.pressure), window,
+                                             tuple(quantity.dims[:2]), "m" if height else quantity.units))
         return requests
 
     # ---- the reference's interface ------------------------------------------------------------------------------------------------
     def _gather(self, requests, packed, transfer_type):
         """The whole cube's arrays of a step, in the requests' order: the windows and planes by ONE pace_cube_gather launch and
         one transfer for all six tiles (gather_state), the column integrals -- which every rank has packed itself: `packed` --
-        stacked on the host.  {name: Quantity leading with TILE_DIM} on the root, None elsewhere."""
+        and the planes on pressure surfaces
+        likewise -- stacked on the host.  {name: Quantity leading with TILE_DIM} on the root, None elsewhere."""
         from ..util.gather import Window
 
         cube = self.communicator
         windows = {r.name: Window(r.field, r.kind, r.level, r.window, r.dims, r.units) for r in requests
-                   if r.kind != _lib.DIAG_COLUMN_INTEGRAL}
+                   if not r.packed_by_rank}
         gathered = cube.gather_state(windows, transfer_type=transfer_type) if windows else ({} if cube.rank == c.ROOT_RANK else None)
         mine = {name: q.data.numpy().copy() for name, q in packed.items()}
         if mine:
@@ -359,7 +480,7 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
         if self.communicator is None:
             monitor_state.update(self.pack(requests))
         else:
-            columns = self.pack([r for r in requests if r.kind == _lib.DIAG_COLUMN_INTEGRAL])
+            columns = self.pack([r for r in requests if r.packed_by_rank])
             gathered = self._gather(requests, columns, np.float32)
             if gathered is None:
                 return

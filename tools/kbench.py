@@ -5,6 +5,9 @@
                                                     around whole checks, which end in their own synchronisation; medians)
     python tools/kbench.py --only diag_pack         a diagnostics step (the example file's fourteen variables) against a plain
                                                     torch restatement, the same way
+    python tools/kbench.py --only plev_diag         an output step of 16 pressure-level planes (p_select: one pace_plev_diag launch,
+                                                    one transfer) against the volumes to the host with numpy there and against
+                                                    a torch restatement on the device, the same way, with the launches alone
     python tools/kbench.py --only geos_wrapper      GeosDycoreWrapper's ingest and export (30 windows each way) against a torch
                                                     restatement (one .copy_ per window, .cpu() per output), the same way, with the
                                                     split into host staging, H2D, unpack launch, pack launch and D2H
@@ -67,6 +70,9 @@ def main():
     if args.only == "cube_gather":  # (its own fields, six tiles, C96 and C192)
         for size in (96, 192):
             cube_gather_bench(lib, size, nz, args.reps)
+        return
+    if args.only == "plev_diag":  # (its own fields)
+        plev_diag_bench(lib, n, nz, max(args.reps, 30))
         return
     if args.only == "checkpointer":  # (its own fields)
         checkpointer_bench(lib, n, nz, args.reps)
@@ -505,6 +511,164 @@ def diag_pack_bench(lib, env, s, n, nz, reps):
           f"{np.median(dev):.1f} us each = {(read_mb + out_mb) * 1e6 / (np.median(dev) * 1e-6) / 1e9:.0f} GB/s of read + write)")
     print(f"  torch restatement (slice, contiguous, float32, cpu per variable)   {ref:9.1f} us per step   (min {min(times['torch']):.1f})")
     print(f"  ratio torch / hip {ref / hip:.2f}")
+
+
+def plev_diag_bench(lib, n, nz, reps, device="cuda"):
+    """An output step of pressure-level diagnostics: pt, ua, va, w, qvapor at 850, 500 and 200 hPa and the height at 500 hPa
+    (16 planes of float32 on the host) of a C<n> x <nz> tile whose surface pressure varies 500 ... 1030 hPa, three ways:
+
+      hip     MonitorDiagnostics with p_select: ONE pace_plev_diag launch, one transfer of the 16 planes, one synchronisation;
+      volumes the only route without it: the eight volumes the interpolation needs (the five fields, delz, peln) and phis as
+              WINDOW3D / PLANE through pace_diag_pack in float64 to the host, then the numpy restatement
+              (tests/plev_reference.py) there;
+      torch   the restatement written with torch on the device (gathers along z at the brackets, the heights by a flipped
+              cumsum), then .to(float32).cpu() per plane.
+    Host clock from an idle device to the data on the host; the three alternate, medians are reported.  Then the launches
+    alone: device events around back-to-back pace_plev_diag launches, and around the torch restatement without its copies;
+    the launch's GB/s are over its algorithmic bytes: peln once, delz once, two elements per LAYER plane, the outputs."""
+    import ctypes as C
+    import math
+    import time
+    import types
+
+    import plev_reference as ref
+
+    from pace_amd.driver import MonitorDiagnostics, PSelect
+    from pace_amd.driver.diagnostics import WindowPacker
+    from pace_amd.util import QuantityFactory, SubtileGridSizer, constants as c
+
+    X, Y, Z, ZI = "x", "y", "z", "z_interface"
+    real = torch.float32 if lib.real_bytes == 4 else torch.float64
+    qf = QuantityFactory(SubtileGridSizer(n, n, nz), device, real)
+    rng = np.random.default_rng(0)
+    side = n + 7
+    ps = rng.uniform(50000.0, 103000.0, (side, side))
+    peln_h = np.log(300.0 + (ps[..., None] - 300.0) * (np.arange(nz + 1) / nz) ** 1.5)
+    layer_names = ["pt", "ua", "va", "w", "qvapor"]
+    fields = {}
+    for name in layer_names + ["delz"]:
+        q = qf.zeros([X, Y, Z], "")
+        a = rng.uniform(-50.0, 50.0, q.shape)
+        if name == "delz":
+            a[..., :nz] = -c.RDGAS * 250.0 / c.GRAV * (peln_h[..., 1:] - peln_h[..., :-1])
+        q.set(a)
+        fields[name] = q
+    fields["peln"] = qf.zeros([X, Y, ZI], "ln(Pa)")
+    fields["peln"].set(peln_h)
+    fields["phis"] = qf.zeros([X, Y], "")
+    fields["phis"].set(rng.uniform(0.0, 3.0e4, (side, side)))
+    state = types.SimpleNamespace(dycore_state=types.SimpleNamespace(**fields), physics_state=types.SimpleNamespace())
+    pressures = (85000.0, 50000.0, 20000.0)
+    p_select = [PSelect(pressures[0], list(layer_names)), PSelect(pressures[1], list(layer_names) + ["height"]),
+                PSelect(pressures[2], list(layer_names))]
+    diag = MonitorDiagnostics(None, [], [], [], lib=lib, p_select=p_select)
+    volumes = WindowPacker(lib)
+    volume_requests = [MonitorDiagnostics._whole(name, fields[name]) for name in layer_names + ["delz", "peln", "phis"]]
+
+    def hip_step():
+        return {k: v.view[:] for k, v in diag.pack(diag._requests(state)).items()}
+
+    def volumes_step():
+        host = {k: v.view[:].numpy() for k, v in volumes.pack(volume_requests, out_is_double=True).items()}
+        out = {}
+        for sel in p_select:
+            lp = math.log(sel.pressure)
+            for name in sel.names:
+                if name == "height":
+                    out[sel.output_name(name)] = ref.height(host["delz"], host["phis"], host["peln"], lp, nz).astype(np.float32)
+                else:
+                    out[sel.output_name(name)] = ref.layer(host[name], host["peln"], lp, nz).astype(np.float32)
+        return out
+
+    def take(a, k):
+        return torch.gather(a, 2, k.unsqueeze(2)).squeeze(2)
+
+    def torch_planes():
+        peln = fields["peln"].view[:].to(torch.float64)
+        pm = 0.5 * (peln[:, :, :-1] + peln[:, :, 1:])
+        zi = None
+        out = {}
+        for sel in p_select:
+            lp = math.log(sel.pressure)
+            kb = ((pm[:, :, 1:nz - 1] <= lp).sum(dim=2))  # (monotone columns: the count is the largest such k)
+            lo, hi = take(pm, kb), take(pm, kb + 1)
+            t = (lp - lo) / (hi - lo)
+            top, bottom = ~(lp > pm[:, :, 0]), lp >= pm[:, :, nz - 1]
+            for name in sel.names:
+                if name == "height":
+                    if zi is None:
+                        delz = fields["delz"].view[:].to(torch.float64)
+                        zs = (fields["phis"].view[:].to(torch.float64) * c.RGRAV).unsqueeze(2)
+                        zi = torch.cat([(zs - torch.cumsum(delz.flip(2), dim=2)).flip(2), zs], dim=2)  # (summed bottom-up)
+                    kh = (peln[:, :, 1:nz] <= lp).sum(dim=2)
+                    e_lo, e_hi = take(peln, kh), take(peln, kh + 1)
+                    z_lo, z_hi = take(zi, kh), take(zi, kh + 1)
+                    out[sel.output_name(name)] = z_lo + (z_hi - z_lo) * ((lp - e_lo) / (e_hi - e_lo))
+                else:
+                    f = fields[name].view[:].to(torch.float64)
+                    v = take(f, kb) + (take(f, kb + 1) - take(f, kb)) * t
+                    out[sel.output_name(name)] = torch.where(top, f[:, :, 0], torch.where(bottom, f[:, :, nz - 1], v))
+        return out
+
+    def torch_step():
+        return {k: v.to(torch.float32).cpu() for k, v in torch_planes().items()}
+
+    got, want, third = hip_step(), volumes_step(), torch_step()
+    assert len(got) == 16
+    for name in got:  # (the kernel and the restatement bit for bit; torch's cumsum sums in another order: the height to 1e-3 m)
+        assert np.array_equal(got[name].numpy().view(np.int32), want[name].view(np.int32)), name
+        assert torch.allclose(third[name], got[name], rtol=1e-6, atol=1e-3), name
+    paths = {"hip": hip_step, "volumes": volumes_step, "torch": torch_step}
+    times = {k: [] for k in paths}
+    for fn in paths.values():  # warm-up: code objects, the pinned buffers, torch's kernels
+        for _ in range(3):
+            fn()
+    for _ in range(reps):
+        for k, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append((time.perf_counter() - t0) * 1e6)
+    requests = diag._requests(state)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    real_to_host = diag._to_host
+    diag._to_host = lambda packed, host: None
+    geom, offsets, packed, _ = diag._plan(requests, False)
+    (chunk,) = diag._plev_launches(list(zip(requests, offsets)))
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream) if device == "cuda" else None
+    arguments = diag._plev_arguments(geom, chunk, False, packed, stream)  # (built once: the burst below is the kernel's time)
+    burst, dev, dev_torch, prep = 10, [], [], []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        diag.pack(requests)
+        prep.append((time.perf_counter() - t0) * 1e6)  # host time to build the item table and launch, nothing waited for
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(burst):
+            lib.call("pace_plev_diag", *arguments)
+        e1.record()
+        torch.cuda.synchronize()
+        dev.append(e0.elapsed_time(e1) * 1e3 / burst)
+        e0.record()
+        torch_planes()
+        e1.record()
+        torch.cuda.synchronize()
+        dev_torch.append(e0.elapsed_time(e1) * 1e3)
+    diag._to_host = real_to_host
+    columns = n * n
+    mb = columns * ((nz + 1 + nz + 1) * lib.real_bytes + 15 * 2 * lib.real_bytes + 16 * 4) / 1e6
+    volume_mb = sum(int(np.prod(r.shape)) for r in volume_requests) * 8 / 1e6
+    hip, vol, ref_t = (float(np.median(times[k])) for k in ("hip", "volumes", "torch"))
+    launch, launch_torch = float(np.median(dev)), float(np.median(dev_torch))
+    print(f"plev_diag C{n} x {nz}, 16 planes ({16 * columns * 4 / 1e6:.2f} MB of float32 to the host); medians of {reps} alternating runs")
+    print(f"  (a) p_select (1 pace_plev_diag, one transfer)              {hip:10.1f} us per step   (min {min(times['hip']):.1f}, host time to build the item table and launch {np.median(prep):.1f} us); "
+          f"the launch alone, {burst} back to back in device events: {launch:.1f} us = {mb * 1e6 / (launch * 1e-6) / 1e9:.0f} GB/s "
+          f"over {mb:.1f} MB of algorithmic bytes")
+    print(f"  (b) volumes to the host ({volume_mb:.0f} MB of float64), numpy there  {vol:10.1f} us per step   (min {min(times['volumes']):.1f})")
+    print(f"  (c) torch restatement on the device, .cpu() per plane      {ref_t:10.1f} us per step   (min {min(times['torch']):.1f}); "
+          f"its kernels alone in device events: {launch_torch:.1f} us")
+    print(f"  ratio (b) / (a) {vol / hip:.1f}   (c) / (a) {ref_t / hip:.2f}   launches alone (c) / (a) {launch_torch / launch:.1f}")
 
 
 def restart_pack_bench(lib, n, nz, reps):
