@@ -36,7 +36,7 @@ from typing import Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _launch, _lib
 from ..util import constants as c
 from ..util.quantity import Quantity
 
@@ -259,16 +259,6 @@ class _PlevRequest:
         return [self.field.data, self.peln.data] + ([self.surface.data] if self.surface is not None else [])
 
 
-def _layout(t):
-    """(n, sj, nk or None, sk or None) of a 2-D or 3-D field of the library's layout."""
-    if t.dim() not in (2, 3) or t.stride(0) != 1:
-        raise ValueError(f"field of shape {tuple(t.shape)}, strides {tuple(t.stride())}: diagnostics take 2-D and 3-D fields "
-                         "allocated with pace_amd.util.QuantityFactory")
-    if t.dim() == 2:
-        return t.shape[0] - 7, t.stride(1), None, None
-    return t.shape[0] - 7, t.stride(1), t.shape[2] - 1, t.stride(2)
-
-
 class WindowPacker:
     """Windows of fields to the host: ONE pace_diag_pack launch per PACE_DIAG_MAX_ITEMS requests, ONE pace_plev_diag launch per
     PACE_PLEV_MAX_LEVELS pressures and PACE_PLEV_MAX_ITEMS planes on them, all into one packed buffer, ONE transfer of that
@@ -282,23 +272,21 @@ class WindowPacker:
 
     def _plan(self, requests, out_is_double):
         tensors = [t for r in requests for t in r.tensors]
-        layouts = [_layout(t) for t in tensors]
-        n, sj = layouts[0][:2]
-        levels = {(nk, sk) for _, _, nk, sk in layouts if nk is not None}
-        if any(lay[:2] != (n, sj) for lay in layouts) or len(levels) > 1 or len({(t.device, t.dtype) for t in tensors}) > 1:
-            raise ValueError("diagnostics take fields of one layout and type on one device")
-        nk, sk = levels.pop() if levels else (1, sj * (n + 7))
+        differ = "diagnostics take fields of one layout and type on one device"
+        geom = _launch.geometry(
+            tensors, lambda t: f"field of shape {tuple(t.shape)}, strides {tuple(t.stride())}: diagnostics take 2-D and 3-D fields "
+                               "allocated with pace_amd.util.QuantityFactory", differ)
+        if len({(t.device, t.dtype) for t in tensors}) > 1:
+            raise ValueError(differ)
         device = tensors[0].device
-        key = (device, n, nk, sj, sk, bool(out_is_double), tuple((r.name, type(r), r.kind, r.window, getattr(r, "log_p", None)) for r in requests))
+        key = (device, geom.n, geom.nk, geom.sj, geom.sk, bool(out_is_double), tuple((r.name, type(r), r.kind, r.window, getattr(r, "log_p", None)) for r in requests))
         if key not in self._plans:
             offsets, total = [], 0
             for r in requests:
                 offsets.append(total)
                 total += int(np.prod(r.shape))
-            dtype = torch.float64 if out_is_double else torch.float32
-            packed = torch.empty(total, dtype=dtype, device=device)
-            host = torch.empty(total, dtype=dtype, pin_memory=device.type != "cpu")
-            self._plans[key] = (_lib.Geom(n, nk, sj, 0, sk), offsets, packed, host)
+            packed, host = _launch.staging(total, torch.float64 if out_is_double else torch.float32, device)
+            self._plans[key] = (geom, offsets, packed, host)
         return self._plans[key]
 
     @staticmethod
@@ -329,11 +317,8 @@ class WindowPacker:
         return (C.byref(geom), peln.ptr, (C.c_double * len(log_p))(*log_p), len(log_p), items, len(chunk), *window,
                 int(bool(out_is_double)), C.c_void_p(packed.data_ptr()), stream)
 
-    def _to_host(self, packed, host):
-        """The step's one transfer and one synchronisation."""
-        host.copy_(packed, non_blocking=True)
-        if packed.device.type != "cpu":
-            torch.cuda.current_stream(packed.device).synchronize()
+    # the step's one transfer and one synchronisation (pack calls it through this name: the one-transfer tests count it here)
+    _to_host = staticmethod(_launch.to_host)
 
     def pack(self, requests: List[_Request], out_is_double: bool = False) -> Dict[str, Quantity]:
         """name -> host-resident Quantity, C-contiguous over the request's window; views of a buffer that the next call with the
@@ -344,24 +329,16 @@ class WindowPacker:
             self._lib = _lib.load()
         geom, offsets, packed, host = self._plan(requests, out_is_double)
         tensor = requests[0].field.data
-        real = torch.float32 if self._lib.real_bytes == 4 else torch.float64
-        if tensor.dtype != real:
-            raise ValueError(f"field dtype {tensor.dtype} does not match the library's storage type {real}")
-        emu = tensor.device.type == "cpu"
-        if emu != ("emulation" in self._lib.version()):
-            raise _lib.PaceError("CPU tensors go with the emulation test library, device tensors with the product library")
-        stream = None if emu else C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
+        _launch.check_library(self._lib, tensor.device, tensor.dtype)
+        stream = _launch.stream_of(tensor.device)
         placed = list(zip(requests, offsets))
         windows = [(r, offset) for r, offset in placed if not isinstance(r, _PlevRequest)]
-        for first in range(0, len(windows), _lib.DIAG_MAX_ITEMS):
-            chunk = windows[first:first + _lib.DIAG_MAX_ITEMS]
+        for _, chunk in _launch.chunks(windows, _lib.DIAG_MAX_ITEMS):
             items = (_lib.DiagItem * len(chunk))()
             for item, (r, offset) in zip(items, chunk):
-                item.field = r.field.ptr + r.level * geom.sk * self._lib.real_bytes  # (the pointers of THIS call's storages)
+                _launch.set_window(item, _launch.window_of(r.field, r.level or None, r.window))  # (THIS call's storages)
                 item.weight = r.weight.ptr if r.weight is not None else None
-                item.kind = r.kind
-                item.i0, item.j0, item.k0, item.ni, item.nj, item.nk = r.window
-                item.out_offset = offset
+                item.kind, item.out_offset = r.kind, offset  # (the kind as asked for: a column integral is no window_of's)
             self._lib.call("pace_diag_pack", C.byref(geom), items, len(chunk), int(bool(out_is_double)),
                            C.c_void_p(packed.data_ptr()), stream)
         for chunk in self._plev_launches([(r, offset) for r, offset in placed if isinstance(r, _PlevRequest)]):
@@ -401,13 +378,10 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
     # ---- what a step asks for ---------------------------------------------------------------------------------------------------
     @staticmethod
     def _whole(name, quantity) -> _Request:
-        if len(quantity.dims) == 3:
-            return _Request(name, _lib.DIAG_WINDOW3D, quantity, None, 0, tuple(quantity.origin) + tuple(quantity.extent),
-                            tuple(quantity.dims), quantity.units)
-        if len(quantity.dims) == 2:
-            return _Request(name, _lib.DIAG_PLANE, quantity, None, 0, tuple(quantity.origin) + (0,) + tuple(quantity.extent) + (1,),
-                            tuple(quantity.dims), quantity.units)
-        raise ValueError(f"{name} has dimensions {quantity.dims}: diagnostics take 2-D and 3-D variables")
+        if len(quantity.dims) not in (2, 3):
+            raise ValueError(f"{name} has dimensions {quantity.dims}: diagnostics take 2-D and 3-D variables")
+        _, kind, *window = _launch.window_of(quantity)
+        return _Request(name, kind, quantity, None, 0, tuple(window), tuple(quantity.dims), quantity.units)
 
     def _requests(self, state) -> List[_Request]:
         """The reference's order (diagnostics.py:166-178): names, derived names, level selections; then the pressure levels.  The
@@ -434,7 +408,7 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
                 quantity = zselect.variable(state.dycore_state, name)
                 if not 0 <= zselect.level < quantity.data.shape[2]:
                     raise IndexError(f"z_select level {zselect.level} of {name}: the storage has {quantity.data.shape[2]} levels")
-                window = tuple(quantity.origin[:2]) + (0,) + tuple(quantity.extent[:2]) + (1,)
+                window = _launch.window_of(quantity, zselect.level)[2:]
                 requests.append(_Request(f"{name}_z{zselect.level}", _lib.DIAG_PLANE, quantity, None, zselect.level, window,
                                          tuple(quantity.dims[:2]), quantity.units))
         for pselect in self.p_select:

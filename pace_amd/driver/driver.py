@@ -20,7 +20,7 @@ import os
 import threading
 import warnings
 
-from .. import _lib
+from .. import _launch, _lib
 from ..fv3core import DynamicalCore
 from ..physics import Physics
 from ..stencils import update_atmos_state
@@ -60,12 +60,7 @@ class Driver:
         self.comm = comm if comm is not None else config.comm_config.get_comm()
         self.lib = lib if lib is not None else _lib.load()
         if device is None:
-            if "emulation" in self.lib.version():
-                device = "cpu"
-            else:
-                import torch
-
-                device = torch.device("cuda", torch.cuda.current_device())
+            device = _launch.default_device(self.lib)
         self.device = device
         self.performance_collector = PerformanceCollector()
         with self.performance_collector.total_timer.clock("initialization"):

@@ -16,7 +16,7 @@ from typing import ClassVar, Dict, Optional
 
 import torch
 
-from .. import _lib
+from .. import _launch, _lib
 
 
 class VariableBounds:
@@ -66,19 +66,22 @@ class SafetyChecker:
         cls.checks.clear()
 
     # ---- device side ------------------------------------------------------------------------------------------------------------
-    def _plan(self, t):
-        """The geometry of a 3-D field of the library's layout, and the workspace and result buffers kept for it."""
-        if t.dim() != 3 or t.stride(0) != 1:
-            raise ValueError(f"field of shape {tuple(t.shape)}, strides {tuple(t.stride())}: the safety check takes 3-D fields "
-                             "allocated with pace_amd.util.QuantityFactory")
-        key = (t.device, t.shape[0] - 7, t.shape[2] - 1, t.stride(1), t.stride(2))
+    def _plan(self, tensors):
+        """The geometry the 3-D fields of the library's layout share, and the workspace and result buffers kept for it."""
+        differ = "the safety check takes fields of one layout on one device"
+        geom = _launch.geometry(
+            tensors, lambda t: f"field of shape {tuple(t.shape)}, strides {tuple(t.stride())}: the safety check takes 3-D fields "
+                               "allocated with pace_amd.util.QuantityFactory", differ, ndim=(3,))
+        device = tensors[0].device
+        if any(t.device != device for t in tensors):
+            raise ValueError(differ)
+        key = (device, geom.n, geom.nk, geom.sj, geom.sk)
         if key not in self._buffers:
-            geom = _lib.Geom(key[1], key[2], key[3], 0, key[4])
             nbytes = int(self._lib.cdll.pace_state_extrema_workspace_bytes(C.byref(geom)))
             if nbytes <= 0:
                 raise _lib.PaceError(f"pace_state_extrema_workspace_bytes: invalid geometry {key[1:]}")
-            workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=t.device)
-            results = torch.empty(4 * _lib.STATE_EXTREMA_MAX_FIELDS, dtype=torch.float64, device=t.device)
+            workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+            results = torch.empty(4 * _lib.STATE_EXTREMA_MAX_FIELDS, dtype=torch.float64, device=device)
             self._buffers[key] = (geom, workspace, results)
         return key, self._buffers[key]
 
@@ -90,23 +93,16 @@ class SafetyChecker:
         tensors = [_field_tensor(f) for f in fields]
         if not tensors:
             return torch.empty((0, 4), dtype=torch.float64).numpy()
-        key, (geom, workspace, results) = self._plan(tensors[0])
-        real = torch.float32 if self._lib.real_bytes == 4 else torch.float64
-        for t in tensors:
-            if t.dtype != real:
-                raise ValueError(f"field dtype {t.dtype} does not match the library's storage type {real}")
-            if self._plan(t)[0] != key:
-                raise ValueError("the safety check takes fields of one layout on one device")
-        emu = tensors[0].device.type == "cpu"
-        if emu != ("emulation" in self._lib.version()):
-            raise _lib.PaceError("CPU tensors go with the emulation test library, device tensors with the product library")
-        stream = None if emu else C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        key, (geom, workspace, results) = self._plan(tensors)
+        device = tensors[0].device
+        for dtype in {t.dtype for t in tensors}:
+            _launch.check_library(self._lib, device, dtype)
+        stream = _launch.stream_of(device)
         m = _lib.STATE_EXTREMA_MAX_FIELDS
         if len(tensors) > m and results.numel() < 4 * len(tensors):
-            results = torch.empty(4 * len(tensors), dtype=torch.float64, device=tensors[0].device)
+            results = torch.empty(4 * len(tensors), dtype=torch.float64, device=device)
             self._buffers[key] = (geom, workspace, results)
-        for first in range(0, len(tensors), m):
-            chunk = tensors[first:first + m]
+        for first, chunk in _launch.chunks(tensors, m):
             table = (C.c_void_p * len(chunk))(*[t.data_ptr() for t in chunk])
             flags = (C.c_int * len(chunk))(*[int(bool(x)) for x in compute_domain_only[first:first + m]])
             self._lib.call("pace_state_extrema", C.byref(geom), table, flags, len(chunk), C.c_void_p(workspace.data_ptr()),

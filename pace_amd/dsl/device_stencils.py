@@ -15,6 +15,7 @@ function name (the translate tests define some stencils in their own modules).
 """
 import ctypes as C
 
+from .. import _launch
 from .stencil import register_stencil
 
 
@@ -37,12 +38,7 @@ def _geom(st):
 
 
 def _stream(st):
-    import torch
-
-    f = st._factory
-    if f.quantity_factory.device.type == "cpu":
-        return None
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return _launch.stream_of(st._factory.quantity_factory.device)
 
 
 def _window(st, origin, domain, what):

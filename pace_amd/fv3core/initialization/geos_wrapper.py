@@ -26,7 +26,7 @@ from typing import Dict
 import numpy as np
 import torch
 
-from ... import _lib
+from ... import _launch, _lib
 from ...util import CubedSphereCommunicator, Timer
 from ...util.constants import N_HALO_DEFAULT
 from .._config import DynamicalCoreConfig
@@ -107,7 +107,7 @@ class GeosDycoreWrapper:
         """
         from ...driver.diagnostics import WindowPacker  # (pace_amd.driver imports pace_amd.fv3core)
         from ...tile import setup_factories
-        from ...util.grid import DampingCoefficients, GridData, MetricTerms
+        from ...util.grid import DampingCoefficients, GridData, MetricTerms, geom_struct
         from ..stencils.fv_dynamics import DynamicalCore
 
         self.perf_collector = PerformanceCollector("GEOS wrapper", comm)
@@ -118,14 +118,12 @@ class GeosDycoreWrapper:
         if tuple(self.layout) != (1, 1):
             raise NotImplementedError(f"layout {tuple(self.layout)}: pace_amd maps one cubed-sphere tile per device, layout must be (1, 1)")
         self._lib = lib if lib is not None else _lib.load()
-        if device is None:
-            device = "cpu" if "emulation" in self._lib.version() else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = device = torch.device(device) if device is not None else _launch.default_device(self._lib)
         self.communicator = CubedSphereCommunicator(comm, device=device, lib=self._lib)
         self._n, self._nz = self.dycore_config.npx - 1, self.dycore_config.npz
         _, quantity_factory, self._grid_indexing, stencil_factory = setup_factories(
             self._lib, device, self._n, self._nz, layout=self.layout, communicator=self.communicator)
-        self._geom = _lib.Geom(self._n, self._nz, quantity_factory.row_stride, 0, quantity_factory.level_stride)
+        self._geom = geom_struct(quantity_factory)
 
         # set up the metric terms and grid data
         metric_terms = MetricTerms(quantity_factory=quantity_factory, communicator=self.communicator)
@@ -154,9 +152,8 @@ class GeosDycoreWrapper:
         for name, (_, _, window) in self._ingest.items():
             self._slots[name] = total
             total += int(np.prod(window[3:])) * (len(TRACERS) if name == "q" else 1)
-        self._staging = torch.empty(total, dtype=torch.float64, pin_memory=self.device.type != "cpu")
+        self._staged, self._staging = _launch.staging(total, torch.float64, self.device)
         self._staging_array = self._staging.numpy()
-        self._staged = torch.empty(total, dtype=torch.float64, device=self.device)
         self._packer = WindowPacker(self._lib)
         self._pool = None
         self.output_dict: Dict[str, np.ndarray] = {}
@@ -167,9 +164,8 @@ class GeosDycoreWrapper:
         flat = self._staging_array[self._slots[name]:self._slots[name] + int(np.prod(shape))]
         return flat.reshape(shape[::-1]).T if f_order else flat.reshape(shape)
 
-    def _to_device(self, staging, staged):
-        """The call's one host-to-device copy (on the current stream: the unpack launch follows it there)."""
-        staged.copy_(staging, non_blocking=True)
+    # the call's one host-to-device copy (the call goes through this name: the one-transfer test counts it here)
+    _to_device = staticmethod(_launch.to_device)
 
     def _stage(self, copies):
         """The host copies of a call, (slot, window of the argument) each: one np.copyto per argument, spread over
@@ -202,16 +198,14 @@ class GeosDycoreWrapper:
                 fields = [(getattr(state, name), offset, 1)]
             for field, in_offset, in_step in fields:
                 item = items[m]
-                item.field = field.ptr  # (the pointer of THIS call's storage: the step swaps storages)
-                item.kind = _lib.DIAG_WINDOW3D if len(shape) > 2 else _lib.DIAG_PLANE
+                _launch.set_window(item, _launch.window_of(field, window=window))  # (THIS call's storage: the step swaps storages)
                 item.order = _lib.ORDER_XFAST if f_order else _lib.ORDER_ZFAST
-                item.i0, item.j0, item.k0, item.ni, item.nj, item.nk = window
                 item.in_step, item.in_offset = in_step, in_offset
                 m += 1
         self._stage(copies)
         self._to_device(self._staging, self._staged)
-        stream = None if self.device.type == "cpu" else C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib.call("pace_state_unpack", C.byref(self._geom), items, m, C.c_void_p(self._staged.data_ptr()), stream)
+        self._lib.call("pace_state_unpack", C.byref(self._geom), items, m, C.c_void_p(self._staged.data_ptr()),
+                       _launch.stream_of(self.device))
         return state
 
     # ---- out -------------------------------------------------------------------------------------------------------------------

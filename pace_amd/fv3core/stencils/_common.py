@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ... import _lib
+from ... import _launch, _lib
 from ...util.grid import geom_struct
 
 
@@ -42,16 +42,12 @@ class Operator:
                                  f"{quantity_factory.real}: load the matching build (pace_amd._lib.load(precision=...))")
         self._grid_data = grid_data
         self._met = grid_data.c_struct() if grid_data is not None else None
-        self._emu = quantity_factory.device.type == "cpu"
-        if self._emu and "emulation" not in self.lib.version():
-            raise _lib.PaceError("CPU tensors can only be used with the emulation test library")
-        if (not self._emu) and "emulation" in self.lib.version():
-            raise _lib.PaceError("the emulation test library cannot run on device tensors")
+        self._device = quantity_factory.device
+        self._emu = self._device.type == "cpu"
+        _launch.check_library(self.lib, self._device)
 
     def stream(self):
-        if self._emu:
-            return None
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _launch.stream_of(self._device)
 
     def call(self, name, *args):
         self.lib.call(name, C.byref(self._geom), *args)

@@ -197,7 +197,7 @@ class DGridShallowWaterLagrangianDynamics(Operator):
         if self._side is None:
             self._side = torch.cuda.Stream(device=self._workspace.device)
             self._ev_prep, self._ev_scalars, self._done = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
-        main, side = torch.cuda.current_stream(), self._side
+        main, side = torch.cuda.current_stream(self._device), self._side
         side_ptr = C.c_void_p(side.cuda_stream)
         # Measured at C192 x 79: running winds A (mask 4) concurrently with the scalar transport (mask 2) gains nothing -- both
         # saturate the SIMDs -- while the winds next to the bandwidth-shaped column solver do (-10 % per substep).
@@ -228,5 +228,5 @@ class DGridShallowWaterLagrangianDynamics(Operator):
     def join(self):
         """Make the calling stream wait for an overlapped wind update (no-op otherwise)."""
         if self._pending:
-            torch.cuda.current_stream().wait_event(self._done)
+            torch.cuda.current_stream(self._device).wait_event(self._done)
             self._pending = False

@@ -71,13 +71,12 @@ def setup_factories(lib, device, n, nz, layout=(1, 1), stencil_config=None, comm
     """The sizer, quantity factory, grid indexing and stencil factory of one C<n> x <nz> tile on `device` for `lib` (whose
     storage type the fields follow: float64 for libpace_hip.so, float32 for the _f32 build) -- what the reference's driver does
     in _setup_factories (driver/pace/driver/driver.py:705-745).  Shared by Env and pace_amd.driver.Driver."""
-    import torch
-
+    from . import _launch
     from .dsl import CompilationConfig, GridIndexing, StencilConfig, StencilFactory
     from .util import QuantityFactory, SubtileGridSizer
 
     sizer = SubtileGridSizer.from_tile_params(nx_tile=n, ny_tile=n, nz=nz, n_halo=3, extra_dim_lengths={}, layout=layout)
-    qf = QuantityFactory(sizer, device=device, dtype=torch.float32 if lib.real_bytes == 4 else torch.float64)
+    qf = QuantityFactory(sizer, device=device, dtype=_launch.real_of(lib))
     grid_indexing = GridIndexing.from_sizer_and_communicator(sizer, communicator)
     if stencil_config is None:
         stencil_config = StencilConfig(compilation_config=CompilationConfig())

@@ -1,12 +1,10 @@
 """What the device checkpointers share: the library and the device as Driver takes them, and a variable -- a Quantity (a
 transpose view, a 2-D field, a float32 field), a tensor or a numpy array -- described to the kernels as a base pointer,
 extents (ni, nj, nk) in STORAGE order and strides (1, sj, sk)."""
-import ctypes as C
-
 import numpy as np
 import torch
 
-from ... import _lib
+from ... import _launch, _lib
 
 
 class DeviceSide:
@@ -25,16 +23,15 @@ class DeviceSide:
     @property
     def device(self):
         if self._device is None:
-            emu = "emulation" in self.lib.version()
-            self._device = torch.device("cpu") if emu else torch.device("cuda", torch.cuda.current_device())
+            self._device = _launch.default_device(self.lib)
         return self._device
 
     @property
     def real(self):
-        return torch.float32 if self.lib.real_bytes == 4 else torch.float64
+        return _launch.real_of(self.lib)
 
     def stream(self):
-        return None if self.device.type == "cpu" else C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _launch.stream_of(self.device)
 
     def describe(self, name, array):
         """A Variable for what a checkpoint call handed over.  numpy arrays are uploaded (as the library's storage type);
@@ -49,8 +46,7 @@ class DeviceSide:
             if not t.dtype.is_floating_point:
                 raise TypeError(f"{name}: a checkpointed variable holds floats, not {t.dtype}")
             raise TypeError(f"{name}: dtype {t.dtype} does not match the library's storage type {self.real}")
-        if t.device.type != self.device.type:
-            raise _lib.PaceError(f"{name}: CPU tensors go with the emulation test library, device tensors with the product library")
+        _launch.check_library(self.lib, t.device, name=name)
         if t.dim() < 1 or t.dim() > 3:
             raise ValueError(f"{name}: variables have one to three axes, not {t.dim()}")
         var = Variable.of(name, t)

@@ -17,7 +17,7 @@ from typing import Dict, List
 
 import torch
 
-from ... import _lib
+from ... import _launch, _lib
 from ._device import DeviceSide
 from .base import Checkpointer
 
@@ -119,8 +119,7 @@ class ThresholdCalibrationCheckpointer(Checkpointer, DeviceSide):
             (fresh if acc.folds == 0 else again).append((var, acc))
             acc.folds += 1
         for group, first in ((fresh, 1), (again, 0)):
-            for start in range(0, len(group), _lib.CKPT_MAX_ITEMS):
-                chunk = group[start:start + _lib.CKPT_MAX_ITEMS]
+            for _, chunk in _launch.chunks(group, _lib.CKPT_MAX_ITEMS):
                 items = (_lib.CkptItem * len(chunk))()
                 for item, (var, acc) in zip(items, chunk):
                     var.fill(item)
@@ -179,8 +178,7 @@ class ThresholdCalibrationCheckpointer(Checkpointer, DeviceSide):
             return []
         out = torch.empty(4 * len(accs), dtype=torch.float64, device=self.device)
         chunks = []
-        for start in range(0, len(accs), _lib.CKPT_MAX_ITEMS):
-            chunk = accs[start:start + _lib.CKPT_MAX_ITEMS]
+        for start, chunk in _launch.chunks(accs, _lib.CKPT_MAX_ITEMS):
             items = (_lib.CkptItem * len(chunk))()
             for item, acc in zip(items, chunk):
                 item.ni, item.nj, item.nk = acc.extents

@@ -21,7 +21,7 @@ from typing import MutableMapping
 import numpy as np
 import torch
 
-from ... import _lib
+from ... import _launch, _lib
 from ._device import DeviceSide
 from .base import Checkpointer
 from .thresholds import SavepointName, SavepointThresholds
@@ -167,13 +167,11 @@ class ValidationCheckpointer(Checkpointer, DeviceSide):
         yield
 
     def _stage(self, total):
-        """A host buffer of `total` doubles (pinned where there is a device) and the device's copy of it."""
-        if self.device.type == "cpu":
-            host = torch.empty(total, dtype=torch.float64)
-            return host, host
-        if self._staging is None or self._staging.numel() < total:
-            self._staging = torch.empty(total, dtype=torch.float64, pin_memory=True)
-        return self._staging[:total], torch.empty(total, dtype=torch.float64, device=self.device)
+        """A host buffer of `total` doubles (pinned where there is a device) and the device's (on the CPU: itself); kept."""
+        if self._staging is None or self._staging[0].numel() < total:
+            self._staging = _launch.staging(total, torch.float64, self.device, alias_on_cpu=True)
+        device, host = self._staging
+        return host[:total], device[:total]
 
     def __call__(self, savepoint_name: str, **kwargs) -> None:
         """
@@ -213,8 +211,8 @@ class ValidationCheckpointer(Checkpointer, DeviceSide):
             flat = host.numpy()
             for var, expected, _, offset in entries:
                 np.copyto(flat[offset:offset + expected.size].reshape(expected.shape), expected, casting="same_kind")
-            if device is not host:
-                device.copy_(host, non_blocking=True)
+            if self.device.type != "cpu":
+                _launch.to_device(host, device)
             found = self._validate(entries, var_thresholds, device)
             for (var, expected, _, _), (nrel, nabs, max_abs, max_rel, first, compared) in zip(entries, found):
                 if nrel > 0 or nabs > 0:
@@ -235,8 +233,7 @@ class ValidationCheckpointer(Checkpointer, DeviceSide):
         """pace_ckpt_validate's six doubles per variable: a launch pair per 32 variables, ONE transfer."""
         out = torch.empty(6 * len(entries), dtype=torch.float64, device=self.device)
         chunks = []
-        for start in range(0, len(entries), _lib.CKPT_MAX_ITEMS):
-            chunk = entries[start:start + _lib.CKPT_MAX_ITEMS]
+        for start, chunk in _launch.chunks(entries, _lib.CKPT_MAX_ITEMS):
             items = (_lib.CkptItem * len(chunk))()
             for item, (var, slab, window, offset) in zip(items, chunk):
                 var.fill(item)

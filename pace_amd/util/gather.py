@@ -24,7 +24,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _launch, _lib
 from . import constants as c
 from .quantity import Quantity, QuantityFactory, SubtileGridSizer
 
@@ -96,19 +96,14 @@ def build_cube_table(geom, items, scatter=False):
 
 
 def geom_of(quantities):
-    """The one geometry of the fields of a call, from their strides."""
-    q3 = [q for q in quantities if q.data.dim() == 3]
-    q = q3[0] if q3 else quantities[0]
-    stride, shape = q.data.stride(), q.shape
-    # (2-D fields only: a plane item reads neither nk nor sk; the entry point wants a geometry of at least one level)
-    geom = _lib.Geom(shape[0] - 7, shape[2] - 1 if q3 else 1, stride[1], 0, stride[2] if q3 else stride[1] * shape[1])
+    """The one geometry of the fields of a call: the first 3-D field gives the levels, a later one may have fewer."""
+    def refuse(q):
+        return f"gather and scatter move (x, y) and (x, y, z) fields, not {q.dims}"
+
     for q in quantities:
-        s = q.data.stride()
-        if len(q.dims) not in (2, 3) or q.dims[0] not in c.X_DIMS or q.dims[1] not in c.Y_DIMS or len(s) not in (2, 3):
-            raise ValueError(f"gather and scatter move (x, y) and (x, y, z) fields, not {q.dims}")
-        if q.shape[0] != geom.n + 7 or s[0] != 1 or s[1] != geom.sj or (len(s) == 3 and (s[2] != geom.sk or q.shape[2] > geom.nk + 1)):
-            raise ValueError("the fields of one gather or scatter differ in geometry")
-    return geom
+        if len(q.dims) not in (2, 3) or q.dims[0] not in c.X_DIMS or q.dims[1] not in c.Y_DIMS:
+            raise ValueError(refuse(q))
+    return _launch.geometry(quantities, refuse, "the fields of one gather or scatter differ in geometry", fewer_levels=True)
 
 
 class Window:
@@ -118,7 +113,7 @@ class Window:
 
     def __init__(self, quantity, kind, level, window, dims, units):
         self.data, self.shape, self.kind, self.window = quantity.data, quantity.shape, kind, tuple(window)
-        self.ptr = quantity.ptr + (level * quantity.data.stride(2) * quantity.data.element_size() if level else 0)
+        self.ptr = _launch.window_of(quantity, level or None, window)[0]
         self.dims, self.units = tuple(dims), units
         self.origin = self.window[:len(self.dims)]
         self.extent = self.window[3:3 + len(self.dims)]
@@ -128,16 +123,8 @@ def item_of(q, offset):
     """The compute domain of a field (interface points included), or a Window, as one item at `offset` elements of the dense
     buffer."""
     x = _lib.CubeItem()
-    x.field, x.offset = q.ptr, int(offset)
-    if isinstance(q, Window):
-        x.kind = q.kind
-        x.i0, x.j0, x.k0, x.ni, x.nj, x.nk = q.window
-        return x
-    x.i0, x.j0, x.ni, x.nj = q.origin[0], q.origin[1], q.extent[0], q.extent[1]
-    if len(q.dims) == 3:
-        x.kind, x.k0, x.nk = _lib.DIAG_WINDOW3D, q.origin[2], q.extent[2]
-    else:
-        x.kind, x.k0, x.nk = _lib.DIAG_PLANE, 0, 1
+    _launch.set_window(x, (q.ptr, q.kind) + q.window if isinstance(q, Window) else _launch.window_of(q))
+    x.offset = int(offset)
     return x
 
 
@@ -209,8 +196,6 @@ class GatherScatter:
 
     def _gs_launch(self, scatter, per_rank, layout, dense):
         """ONE launch for the tiles in per_rank = {rank: quantities}; the table is cached per set of addresses."""
-        from . import halo
-
         self._gs_state()
         key = (bool(scatter), layout.rank_major, tuple((r, tuple((q.ptr, tuple(q.origin), tuple(q.extent)) for q in qs)) for r, qs in sorted(per_rank.items())),
                tuple(layout.sizes))
@@ -222,7 +207,7 @@ class GatherScatter:
             slot = 0 if (layout.rank_major and len(per_rank) == 1) else None  # (a rank's own pack under TorchDistComm)
             items = [item_of(q, layout.offset(f, r if slot is None else slot)) for r, qs in sorted(per_rank.items()) for f, q in enumerate(qs)]
             buf = build_cube_table(geom, items, scatter)
-            hit = self._gs_tables[key] = (halo._upload_table(buf, self.device), len(items), geom)
+            hit = self._gs_tables[key] = (_launch.upload_table(buf, self.device), len(items), geom)
             if len(self._gs_tables) > TABLE_CACHE:
                 self._gs_tables.popitem(last=False)
         else:
@@ -232,8 +217,7 @@ class GatherScatter:
                       _dense_code(dense.dtype), C.c_void_p(dense.data_ptr()), self.stream())
 
     def _gs_stream_id(self):
-        s = self.stream()
-        return s.value if s is not None else None
+        return getattr(self.stream(), "value", None)
 
     def _gs_bcast(self, obj):
         """An object from the root to every rank of a TorchDistComm."""
@@ -265,14 +249,8 @@ class GatherScatter:
         buf = self._gs_state()._gs_buffers
         key = (int(elements), dtype)
         if key not in buf:
-            dev = torch.empty(elements, dtype=dtype, device=self.device)
-            host = dev if self.device.type == "cpu" else torch.empty(elements, dtype=dtype, pin_memory=True)
-            buf[key] = (dev, host)
+            buf[key] = _launch.staging(elements, dtype, self.device, alias_on_cpu=True)
         return buf[key]
-
-    def _gs_sync(self):
-        if self.device.type != "cpu":
-            torch.cuda.current_stream().synchronize()
 
     # ---- gather ------------------------------------------------------------------------------------------------
     def _gs_recv_flat(self, send_quantity, recv_quantity, ranks):
@@ -306,7 +284,7 @@ class GatherScatter:
             local = torch.empty(layout.per_rank, dtype=dtype, device=self.device)
             self._gs_launch(False, {self.rank: [send_quantity]}, layout, local)
             dense = (inplace if inplace is not None else torch.empty(layout.total, dtype=dtype, device=self.device)) if root else None
-            self._gs_sync()
+            _launch.wait_for(self.device)
             self.comm._dist.gather(local, list(dense.reshape(ranks, -1).unbind(0)) if root else None, dst=c.ROOT_RANK,
                                    group=self.comm._group)
         else:
@@ -323,7 +301,7 @@ class GatherScatter:
             if torch.is_tensor(recv_quantity.data):
                 recv_quantity.data.copy_(out)
             else:
-                self._gs_sync()
+                _launch.wait_for(self.device)
                 np.copyto(recv_quantity.data, out.cpu().numpy())
         return recv_quantity
 
@@ -397,7 +375,7 @@ class GatherScatter:
             local = torch.empty(layout.per_rank, dtype=dtype, device=self.device)
             self._gs_launch(False, {self.rank: qs}, layout, local)
             dense, host = self._gs_buffer(layout.total, dtype) if root else (None, None)
-            self._gs_sync()
+            _launch.wait_for(self.device)
             self.comm._dist.gather(local, list(dense.reshape(ranks, -1).unbind(0)) if root else None, dst=c.ROOT_RANK,
                                    group=self.comm._group)
             if root and host is not dense:
@@ -411,7 +389,7 @@ class GatherScatter:
                 host.copy_(dense, non_blocking=True)
         if not root:
             return recv_state
-        self._gs_sync()
+        _launch.wait_for(self.device)
         flat = host.numpy()
         for f, m in enumerate(metas):
             arr = layout.array(flat, f)
@@ -454,7 +432,7 @@ class GatherScatter:
             return [], dict(recv)
         if not metas:
             return metas, {}
-        real = torch.float64 if self.lib.real_bytes == 8 else torch.float32
+        real = _launch.real_of(self.lib)
         out = {}
         for m in metas:
             if m.name in recv:
@@ -483,8 +461,7 @@ class GatherScatter:
                     torch.from_numpy(view).copy_(a) if view.flags.c_contiguous else np.copyto(view, a.cpu().numpy())
                 else:
                     np.copyto(view, a, casting="same_kind")
-            if host is not dev:
-                dev.copy_(host, non_blocking=True)
+            _launch.to_device(host, dev)
             return dev
 
         if mode in ("cube", "ranks"):
@@ -506,7 +483,7 @@ class GatherScatter:
         elif mode == "dist":
             local = torch.empty(layout.per_rank, dtype=dtype, device=self.device)
             dense = stage() if root else None
-            self._gs_sync()
+            _launch.wait_for(self.device)
             self.comm._dist.scatter(local, list(dense.reshape(ranks, -1).unbind(0)) if root else None, src=c.ROOT_RANK,
                                     group=self.comm._group)
             self._gs_launch(True, {self.rank: qs}, layout, local)

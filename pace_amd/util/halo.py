@@ -25,7 +25,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _launch, _lib
 from . import constants as c
 from .comm import Request
 from .gather import GatherScatter
@@ -264,19 +264,8 @@ def check_cube_table(geom, entries):
                 raise ValueError(f"halo table entry {t} writes what entry {u} reads from the same field")
 
 
-def _upload_table(arr, device):
-    """The table on the device: through a pinned staging array on the launch stream (no synchronisation).  Returns the tensors
-    to keep alive with the table (device copy first)."""
-    nbytes = C.sizeof(arr)
-    if device.type == "cpu":
-        dev = torch.empty(nbytes // 8, dtype=torch.int64)  # (an entry is a whole number of 8-byte units)
-        C.memmove(dev.data_ptr(), arr, nbytes)
-        return (dev,)
-    stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-    C.memmove(stage.data_ptr(), arr, nbytes)
-    dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    dev.copy_(stage, non_blocking=True)
-    return dev, stage
+def _upload_table(arr, device):  # (the fused path uploads through this name; it and gather share _launch.upload_table)
+    return _launch.upload_table(arr, device)
 
 
 def _build_cube_table(updaters, ptrs):
@@ -507,9 +496,7 @@ class CubedSphereCommunicator(GatherScatter):
         return self.comm.Get_rank()
 
     def stream(self):
-        if self.device.type == "cpu":
-            return None
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _launch.stream_of(self.device)
 
     def _get_halo_tag(self) -> int:
         self._last_tag += 1

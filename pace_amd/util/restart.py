@@ -41,7 +41,7 @@ from typing import Iterable, Optional, Tuple
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _launch, _lib
 from . import _nc3
 from .checkpointer.validation import _open_nc
 from .constants import X_DIM, X_INTERFACE_DIM, Y_DIM, Y_INTERFACE_DIM, Z_DIM
@@ -148,30 +148,15 @@ def get_start_date_from_coupler_res(path) -> Optional[datetime]:
         return None
 
 
-def _to_device(staging, staged):
-    """The call's one host-to-device copy (on the current stream: the unpack launch follows it there)."""
-    staged.copy_(staging, non_blocking=True)
+# the call's one host-to-device copy, and its one device-to-host copy with the one wait for it (the calls go through these names:
+# the one-transfer tests count them here)
+_to_device, _to_host = _launch.to_device, _launch.to_host
 
 
 def _geometry(quantities):
     """The storage layout the Quantities share, as the C ABI takes it."""
-    sj = nk = sk = None
-    for q in quantities:
-        stride, shape = q.data.stride(), q.data.shape
-        if len(shape) not in (2, 3) or stride[0] != 1:
-            raise ValueError(f"to_state: cannot fill a quantity of dims {q.dims}")
-        layout = (shape[0] - 7, stride[1])
-        if sj is not None and layout != sj:
-            raise ValueError("to_state: the quantities do not share one storage layout")
-        sj = layout
-        if len(shape) == 3:
-            if nk is not None and (shape[2] - 1, stride[2]) != (nk, sk):
-                raise ValueError("to_state: the quantities do not share one storage layout")
-            nk, sk = shape[2] - 1, stride[2]
-    n, row = sj
-    if nk is None:
-        nk, sk = 1, row * (n + 7)
-    return _lib.Geom(n, nk, row, 0, sk)
+    return _launch.geometry(quantities, lambda q: f"to_state: cannot fill a quantity of dims {q.dims}",
+                            "to_state: the quantities do not share one storage layout")
 
 
 def _attribute(file, restart_name, attribute):
@@ -191,33 +176,25 @@ def _attribute(file, restart_name, attribute):
 
 def _windows_of(entries, real_bytes):
     """(quantity, level or None) pairs -> the windows pace_restart_pack takes: (pointer, kind, i0, j0, k0, ni, nj, nk)."""
-    windows = []
-    for quantity, level in entries:
-        if level is None and len(quantity.dims) == 3:
-            windows.append((quantity.ptr, _lib.DIAG_WINDOW3D) + tuple(quantity.origin) + tuple(quantity.extent))
-        else:
-            pointer = quantity.ptr + (0 if level is None else level * quantity.data.stride()[2] * real_bytes)
-            windows.append((pointer, _lib.DIAG_PLANE, quantity.origin[0], quantity.origin[1], 0, quantity.extent[0], quantity.extent[1], 1))
-    return windows
+    return [_launch.window_of(quantity, level) for quantity, level in entries]
 
 
 def _pack(lib, geom, windows, offsets, out_type, out, sums, device, stream):
     """pace_restart_pack over the windows, one launch per 32: the bytes to out + offsets[m] (device address, or None) and the
     sums to sums + 8 * m (device address, or None).  -> the workspace, which the launches read until the stream has run them."""
-    chunks = [range(start, min(start + _lib.RESTART_MAX_ITEMS, len(windows))) for start in range(0, len(windows), _lib.RESTART_MAX_ITEMS)]
     tables, need = [], 0
-    for chunk in chunks:
+    for first, chunk in _launch.chunks(windows, _lib.RESTART_MAX_ITEMS):
         items = (_lib.RestartItem * len(chunk))()
-        for item, m in zip(items, chunk):
-            item.field, item.kind, item.i0, item.j0, item.k0, item.ni, item.nj, item.nk = windows[m]
+        for m, (item, window) in enumerate(zip(items, chunk), first):
+            _launch.set_window(item, window)
             item.out_offset = offsets[m] if out is not None else 0
-        tables.append(items)
+        tables.append((first, items))
         if sums is not None:
-            need = max(need, int(lib.cdll.pace_restart_pack_workspace_bytes(C.byref(geom), items, len(chunk))))
+            need = max(need, int(lib.cdll.pace_restart_pack_workspace_bytes(C.byref(geom), items, len(items))))
     workspace = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=device)
-    for chunk, items in zip(chunks, tables):
-        lib.call("pace_restart_pack", C.byref(geom), items, len(chunk), out_type, None if out is None else C.c_void_p(out),
-                 None if sums is None else C.c_void_p(sums + 8 * chunk[0]), C.c_void_p(workspace.data_ptr()), stream)
+    for first, items in tables:
+        lib.call("pace_restart_pack", C.byref(geom), items, len(items), out_type, None if out is None else C.c_void_p(out),
+                 None if sums is None else C.c_void_p(sums + 8 * first), C.c_void_p(workspace.data_ptr()), stream)
     return workspace
 
 
@@ -281,24 +258,17 @@ def _fill(found, to_state, communicator, verify_checksums=False, missing_ok=()):
     if not entries:
         return
     geom = _geometry([quantity for quantity, _, _, _ in entries])
-    staging = torch.empty(total, dtype=torch.float64, pin_memory=device.type != "cpu")
+    staged, staging = _launch.staging(total, torch.float64, device)
     flat = staging.numpy()
     for _, array, offset, _ in entries:
         np.copyto(flat[offset:offset + array.size].reshape(array.shape), array, casting="same_kind")
-    staged = torch.empty(total, dtype=torch.float64, device=device)
     _to_device(staging, staged)
     stream = communicator.stream()
-    for start in range(0, len(entries), _lib.UNPACK_MAX_ITEMS):
-        chunk = entries[start:start + _lib.UNPACK_MAX_ITEMS]
+    for _, chunk in _launch.chunks(entries, _lib.UNPACK_MAX_ITEMS):
         items = (_lib.UnpackItem * len(chunk))()
-        for item, (quantity, array, offset, level) in zip(items, chunk):
-            item.field = quantity.ptr + (0 if level is None else level * quantity.data.stride()[2] * lib.real_bytes)
-            item.kind = _lib.DIAG_WINDOW3D if array.ndim == 3 else _lib.DIAG_PLANE
-            item.order = _lib.ORDER_XFAST
-            item.i0, item.j0 = quantity.origin[0], quantity.origin[1]
-            item.ni, item.nj = quantity.extent[0], quantity.extent[1]
-            item.k0, item.nk = (quantity.origin[2], quantity.extent[2]) if array.ndim == 3 else (0, 1)
-            item.in_step, item.in_offset = 1, offset
+        for item, (quantity, _, offset, level) in zip(items, chunk):
+            _launch.set_window(item, _launch.window_of(quantity, level))
+            item.order, item.in_step, item.in_offset = _lib.ORDER_XFAST, 1, offset
         lib.call("pace_state_unpack", C.byref(geom), items, len(chunk), C.c_void_p(staged.data_ptr()), stream)
     if verify_checksums:
         _verify(sources, geom, communicator)
@@ -368,13 +338,6 @@ class LevelOf:
         if len(quantity.dims) != 3 or not 0 <= level < quantity.data.shape[2]:
             raise ValueError(f"LevelOf: level {level} of a quantity of dims {quantity.dims} and shape {quantity.shape}")
         self.quantity, self.level = quantity, int(level)
-
-
-def _to_host(packed, host):
-    """The call's one device-to-host copy (on the current stream, behind the pack launch), and the one wait for it."""
-    host.copy_(packed, non_blocking=True)
-    if packed.device.type != "cpu":
-        torch.cuda.current_stream().synchronize()
 
 
 _COUPLER_RES = ("{:6d}        (Calendar: no_calendar=0, thirty_day_months=1, julian=2, gregorian=3, noleap=4)\n"
@@ -487,8 +450,7 @@ def write_restart(dirname: str, communicator, from_state: dict, *, time: datetim
         sums_at = (total + 7) // 8 * 8
         words = sums_at // 8 + len(entries)
         geom = _geometry([quantity for _, _, quantity, _ in entries])
-        packed = torch.empty(words, dtype=torch.int64, device=device)
-        host = torch.empty(words, dtype=torch.int64, pin_memory=device.type != "cpu")
+        packed, host = _launch.staging(words, torch.int64, device)
         windows = _windows_of([(quantity, level) for _, _, quantity, level in entries], lib.real_bytes)
         workspace = _pack(lib, geom, windows, offsets, out_type, packed.data_ptr(), packed.data_ptr() + sums_at, device,
                           communicator.stream())

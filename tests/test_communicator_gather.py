@@ -180,11 +180,12 @@ def check_launch_structure(device):
     launches for itself."""
     import torch
 
-    from pace_amd.util import CubedSphereCommunicator, QuantityFactory, SubtileGridSizer, halo, run_cube
+    from pace_amd import _launch
+    from pace_amd.util import CubedSphereCommunicator, QuantityFactory, SubtileGridSizer, run_cube
 
     lib = CountingLib(_libs(device)[0])
     uploads = []
-    real_upload = halo._upload_table
+    real_upload = _launch.upload_table
 
     def counted_upload(arr, dev):
         uploads.append(len(arr))
@@ -217,12 +218,12 @@ def check_launch_structure(device):
         counted(lambda: cube.scatter_state(whole, recv_state=state))
         return counts
 
-    halo._upload_table = counted_upload
+    _launch.upload_table = counted_upload
     try:
         fused = run_cube(program)
         snap = run_cube(program, snapshot=True)
     finally:
-        halo._upload_table = real_upload
+        _launch.upload_table = real_upload
     table = lambda items: (48 * items + 4 * (items + 1) + 7) // 8 * 8  # noqa: E731
     for counts in fused:
         assert counts[0] == ({"pace_cube_gather": 1}, [table(24)]), counts[0]
