@@ -886,6 +886,44 @@ int pace_cube_gather(const pace_geom_t* geom, const pace_cube_item_t* table_on_d
 int pace_cube_scatter(const pace_geom_t* geom, const pace_cube_item_t* table_on_device, int n, int dense_type, const void* dense,
                       void* stream);
 
+/* ---- Regridding the cube to a list of points (lat-lon diagnostics; no counterpart in the reference): piecewise-linear
+ * interpolation of cell-centre fields of the six tiles' storages of one geometry to `npoints` target points, any number of
+ * variables by ONE launch into ONE dense device buffer, both storage types, no atomics, no workspace, no host synchronisation.
+ * A point names three source cells (tile, i, j) -- storage indices, the halo origin added -- and three float64 weights
+ * (pace_amd/util/latlon.py builds them from the spherical Delaunay triangulation of the cell centres).  An item is one variable
+ * given as its six tiles' pointers: PACE_DIAG_WINDOW3D with the levels k0 .. k0 + nk - 1, or PACE_DIAG_PLANE (nk is read as 1,
+ * k0 as 0) whose pointers are at element (0, 0) of a 2-D field or of ONE level of a 3-D one.  With f_m(k) the stored value of
+ * source m at level k, widened to double first in the float32 library,
+ *   dense[offset + p * nk + k] = (dense type)((w0 * f_0(k0 + k) + w1 * f_1(k0 + k)) + w2 * f_2(k0 + k))
+ * in double, in exactly this order, products then adds, without FMA; the cast is plain (round to nearest even, overflow to
+ * +-inf).  NaN and inf propagate by ordinary arithmetic: 0 * NaN and 0 * inf are NaN.  Only the three named elements per point
+ * and level are read, nothing is written outside an item's npoints * nk dense elements, and the storages are not written.
+ * points_on_device and items_on_device are DEVICE memory, read in place: npoints points; n items, and right behind them
+ * int32_t first[n + 1], the prefix sums of the items' tile counts (first[0] = 0, first[n] = all tiles), where an item has
+ *   ceil(npoints / 64) * ceil(nk / 32) tiles (WINDOW3D),   ceil(npoints / 64) tiles (PLANE).
+ * The entry point refuses only what it can see -- npoints < 1, n < 1 or n > PACE_REGRID_MAX_ITEMS (a variable is one item for
+ * all six tiles, where pace_cube_gather's table has six), an unknown dense_type, a NULL pointer (PACE_ERR_ARG).  The entries
+ * cannot be checked here: whoever builds the tables guarantees that every tile is 0 .. 5, every source inside the storage
+ * (n + 7, n + 7; the host check asks for the compute domain), every weight finite, every kind one of the two, every level range inside nk + 1 levels, no field NULL, no
+ * offset negative, the prefix table the one above and first[n] < 2^31 (pace_amd/util/latlon.py check_regrid_table,
+ * check_regrid_items). */
+#define PACE_REGRID_MAX_ITEMS 1024
+typedef struct {            /* one target point: 64 bytes */
+  int32_t tile[3];          /* the three sources: tile 0 .. 5, */
+  int32_t i[3];             /* ... x and */
+  int32_t j[3];             /* ... y index in the storage */
+  int32_t pad_;
+  double  w[3];             /* their weights */
+} pace_regrid_point_t;
+typedef struct {            /* one variable */
+  void*   field[6];         /* element (0,0,0) of each tile's storage (2-D field or one level's plane for a PLANE item) */
+  int32_t kind;             /* PACE_DIAG_WINDOW3D | PACE_DIAG_PLANE */
+  int32_t k0, nk, pad_;
+  int64_t offset;           /* in elements of the dense buffer */
+} pace_regrid_item_t;
+int pace_cube_regrid(const pace_geom_t* geom, const pace_regrid_point_t* points_on_device, int npoints,
+                     const pace_regrid_item_t* items_on_device, int n, int dense_type, void* dense, void* stream);
+
 const char* pace_version(void);
 /* sizeof(pace_real_t) of this build: 8 (libpace_hip.so) or 4 (libpace_hip_f32.so). */
 int pace_real_bytes(void);

@@ -166,6 +166,18 @@ class CubeItem(C.Structure):  # include/pace_hip.h pace_cube_item_t
                 ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32), ("offset", C.c_int64)]
 
 
+REGRID_MAX_ITEMS = 1024  # include/pace_hip.h PACE_REGRID_MAX_ITEMS
+
+
+class RegridPoint(C.Structure):  # include/pace_hip.h pace_regrid_point_t
+    _fields_ = [("tile", C.c_int32 * 3), ("i", C.c_int32 * 3), ("j", C.c_int32 * 3), ("pad_", C.c_int32), ("w", C.c_double * 3)]
+
+
+class RegridItem(C.Structure):  # include/pace_hip.h pace_regrid_item_t
+    _fields_ = [("field", c_dp * 6), ("kind", C.c_int32), ("k0", C.c_int32), ("nk", C.c_int32), ("pad_", C.c_int32),
+                ("offset", C.c_int64)]
+
+
 RESTART_MAX_ITEMS = 32  # include/pace_hip.h PACE_RESTART_MAX_ITEMS
 RESTART_BE_F64, RESTART_BE_F32 = 0, 1  # include/pace_hip.h PACE_RESTART_*
 
@@ -301,6 +313,7 @@ _PROTOS = {
     "pace_halo_cube": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_void_p]),
     "pace_cube_gather": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pace_cube_scatter": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pace_cube_regrid": (C.c_int, [_P(Geom), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

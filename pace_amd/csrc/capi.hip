@@ -862,6 +862,15 @@ int pace_cube_scatter(const pace_geom_t* geom, const pace_cube_item_t* table_on_
   return cube_xfer(geom, table_on_device, n, dense_type, (void*)dense, 1, stream);
 }
 
+int pace_cube_regrid(const pace_geom_t* geom, const pace_regrid_point_t* points_on_device, int npoints,
+                     const pace_regrid_item_t* items_on_device, int n, int dense_type, void* dense, void* stream) {
+  NEED(geom && points_on_device && items_on_device && dense);
+  if (npoints < 1 || n < 1 || n > PACE_REGRID_MAX_ITEMS) return PACE_ERR_ARG;
+  if (dense_type != PACE_DENSE_F64 && dense_type != PACE_DENSE_F32) return PACE_ERR_ARG;
+  return launch_cube_regrid(make_geo(geom), points_on_device, npoints, items_on_device, n, dense_type == PACE_DENSE_F64, dense,
+                            S(stream));
+}
+
 int pace_stencil(const pace_geom_t* geom, const pace_metrics_t* met, int id, void* const* fields, int nfields, const double* scalars,
                  int nscalars, const int* origin, const int* domain, void* stream) {
   NEED(geom && met && fields && origin && domain && nfields >= 1 && nfields <= 16 && nscalars >= 0 && (nscalars == 0 || scalars));

@@ -288,6 +288,9 @@ int launch_plev_diag(const Geo& g, const real* peln, const double* log_p, int nl
 // k_gather.hip
 int launch_cube_xfer(const Geo& g, const pace_cube_item_t* table_on_device, int n, int dense_is_double, void* dense, int scatter,
                      hipStream_t st);
+// k_regrid.hip
+int launch_cube_regrid(const Geo& g, const pace_regrid_point_t* points_on_device, int npoints,
+                       const pace_regrid_item_t* items_on_device, int n, int dense_is_double, void* dense, hipStream_t st);
 // k_state.hip
 int launch_state_unpack(const Geo& g, const pace_unpack_item_t* items, int nitems, const double* in, hipStream_t st);
 // k_restart.hip

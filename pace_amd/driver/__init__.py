@@ -21,6 +21,7 @@ from .config import (  # noqa: F401
 from .diagnostics import (  # noqa: F401
     Diagnostics,
     DiagnosticsConfig,
+    LatLonSelect,
     MonitorDiagnostics,
     NpzMonitor,
     NullDiagnostics,

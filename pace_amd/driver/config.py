@@ -22,6 +22,8 @@ What is accepted, refused and ignored:
   initialization.config.surface_winds     (fortran_restart; not in the reference) u_srf / v_srf into the lowest level of ua / va
   diagnostics_config    output_format npz with a path: written (driver/diagnostics.py); zarr, netcdf: parsed and kept, nothing is
                         written (the Driver warns once)
+  diagnostics_config.latlon  (not in the reference) cell-centre variables on a regular latitude-longitude grid, regridded on the
+                        device; with comm_config.type cube only, ValueError with any other
   performance_config    parsed and kept; nothing is written
   stencil_config.compilation_config.backend  kept as `requested_backend`; the backend is always hip:gfx950
 """

@@ -22,6 +22,12 @@ Fields on pressure surfaces (`p_select`: pt_p850, height_p500, ...; this project
 are interpolated on the device by pace_plev_diag (pace_amd/csrc/k_plev.hip), one launch per PACE_PLEV_MAX_LEVELS pressures and
 PACE_PLEV_MAX_ITEMS planes, into the same packed buffer: a step is still one transfer and one synchronisation, and a plane is
 1 / nz of the volume a host-side interpolation would need.
+
+Fields on a regular latitude-longitude grid (`latlon`: pt_ll, phis_ll, pt_z65_ll, ...; this project's extension, the horizontal
+counterpart of p_select) are regridded on the device by pace_cube_regrid (pace_amd/csrc/k_regrid.hip) where one communicator
+holds the whole cube: a store adds ONE launch for every requested variable and ONE transfer of the lat-lon arrays alone
+(CubedSphereCommunicator.regrid_state) -- 64 800 points of a 1 degree grid against the 221 184 cells of C192.  The monitors write
+them with the dimensions [time, lon, lat(, z)], without a tile axis.
 """
 import abc
 import ctypes as C
@@ -116,6 +122,60 @@ class PSelect:
 
 
 @dataclasses.dataclass
+class LatLonSelect:
+    """Cell-centre variables on a regular nlon x nlat latitude-longitude grid (pace_amd/util/latlon.py; piecewise-linear on the
+    spherical Delaunay triangulation of the cell centres): `<name>_ll` with dims (lon, lat, z) or (lon, lat); with `levels`,
+    every 3-D variable as the planes `<name>_z<k>_ll` of those levels instead.  The names are looked up in the dycore state,
+    then the physics state: pt, delp, ua, va (the zonal and meridional A-grid winds: scalars on the sphere), w, qvapor, phis,
+    ..."""
+
+    nlon: int
+    nlat: int
+    names: List[str]
+    levels: Optional[List[int]] = None
+
+    def __post_init__(self):
+        if self.nlon < 1 or self.nlat < 1:
+            raise ValueError(f"latlon: the grid has at least one point each way, not {self.nlon} x {self.nlat}")
+
+    def grid(self):
+        from ..util.latlon import LatLonGrid
+
+        return LatLonGrid(self.nlon, self.nlat)
+
+    def variable(self, state, name: str) -> Quantity:
+        """The state's cell-centre variable `name`."""
+        quantity = None
+        for part in (getattr(state, "dycore_state", None), getattr(state, "physics_state", None)):
+            if name in getattr(part, "__dict__", {}):
+                quantity = getattr(part, name)
+                break
+        if quantity is None:
+            raise ValueError(f"Invalid state variable {name} for latlon")
+        if tuple(quantity.dims) not in ((c.X_DIM, c.Y_DIM), (c.X_DIM, c.Y_DIM, c.Z_DIM)):
+            raise ValueError(f"latlon only works for cell-centre state variables with dimension (x, y) or (x, y, z). \n {name} has "
+                             f"dimension {quantity.dims}")
+        return quantity
+
+    def windows(self, state):
+        """{output name: Quantity or gather Window} of a store, in the names' order."""
+        from ..util.gather import Window
+
+        out = {}
+        for name in self.names:
+            quantity = self.variable(state, name)
+            if len(quantity.dims) == 2 or self.levels is None:
+                out[f"{name}_ll"] = quantity
+                continue
+            for level in self.levels:
+                if not 0 <= level < quantity.data.shape[2]:
+                    raise IndexError(f"latlon level {level} of {name}: the storage has {quantity.data.shape[2]} levels")
+                window = _launch.window_of(quantity, level)[2:]
+                out[f"{name}_z{level}_ll"] = Window(quantity, _lib.DIAG_PLANE, level, window, quantity.dims[:2], quantity.units)
+        return out
+
+
+@dataclasses.dataclass
 class DiagnosticsConfig:
     """
     Attributes:
@@ -128,6 +188,8 @@ class DiagnosticsConfig:
         derived_names: derived diagnostics to save
         z_select: save a vertical slice of a 3D state
         p_select: save state variables, or `height`, on pressure surfaces (this project's extension)
+        latlon: save cell-centre state variables on a regular latitude-longitude grid (this project's extension; needs a
+            communicator that holds the whole cube: comm_config.type: cube)
     """
 
     path: Optional[str] = None
@@ -137,9 +199,10 @@ class DiagnosticsConfig:
     derived_names: List[str] = dataclasses.field(default_factory=list)
     z_select: List[ZSelect] = dataclasses.field(default_factory=list)
     p_select: List[PSelect] = dataclasses.field(default_factory=list)
+    latlon: Optional[LatLonSelect] = None
 
     def __post_init__(self):
-        if (len(self.names) > 0 or len(self.derived_names) > 0 or len(self.p_select) > 0) and self.path is None:
+        if (len(self.names) > 0 or len(self.derived_names) > 0 or len(self.p_select) > 0 or self.latlon is not None) and self.path is None:
             raise ValueError("DiagnosticsConfig.path must be given to enable diagnostics")
         if self.output_format not in _OUTPUT_FORMATS:
             raise ValueError(f"output_format must be one of 'zarr', 'netcdf' or 'npz', got {self.output_format}")
@@ -161,6 +224,9 @@ class DiagnosticsConfig:
                 files; nothing is gathered)
             lib: the kernel library the state's fields belong to (default: the product library)
         """
+        if self.latlon is not None and not whole_cube(communicator):
+            raise ValueError("diagnostics_config.latlon regrids the whole cube on one device: run the configuration with "
+                             "comm_config.type: cube (pace_amd.driver.run_cube_driver); a per-rank communicator holds one tile")
         if not self.writes_files_for(communicator):
             return NullDiagnostics()
         os.makedirs(self.path, exist_ok=True)
@@ -171,8 +237,17 @@ class DiagnosticsConfig:
         else:
             monitor = NpzMonitor(self.path, tile=communicator.partitioner.tile_index(communicator.rank),
                                  time_chunk_size=self.time_chunk_size)
+        latlon_monitor = None
+        if self.latlon is not None:  # files of their own: the per-tile and whole-cube files are what they are without `latlon`
+            if self.output_format == "netcdf":
+                latlon_monitor = NetCDFMonitor(self.path, communicator, time_chunk_size=self.time_chunk_size)
+                latlon_monitor.FILENAME_FORMAT = "latlon_{chunk:04d}.nc"
+            else:
+                latlon_monitor = NpzMonitor(self.path, tile=0, time_chunk_size=self.time_chunk_size)
+                latlon_monitor.FILENAME_FORMAT, latlon_monitor.CONSTANT_FILENAME_FORMAT = "latlon_{chunk:04d}.npz", "constants_{name}.npz"
         return MonitorDiagnostics(monitor=monitor, names=self.names, derived_names=self.derived_names, z_select=self.z_select,
-                                  lib=lib, communicator=communicator if whole_cube(communicator) else None, p_select=self.p_select)
+                                  lib=lib, communicator=communicator if whole_cube(communicator) else None, p_select=self.p_select,
+                                  latlon=self.latlon, latlon_monitor=latlon_monitor)
 
     @classmethod
     def from_dict(cls, config) -> "DiagnosticsConfig":
@@ -184,6 +259,8 @@ class DiagnosticsConfig:
         # (parsed before the constructor sees them: a pressure that is no number is named as the setting it is)
         config["p_select"] = [p if isinstance(p, PSelect) else _strict(PSelect, "diagnostics_config.p_select", p)
                               for p in config.get("p_select") or []]
+        if config.get("latlon") is not None and not isinstance(config["latlon"], LatLonSelect):
+            config["latlon"] = _strict(LatLonSelect, "diagnostics_config.latlon", config["latlon"])
         out = _strict(cls, "diagnostics_config", config)
         out.z_select = [z if isinstance(z, ZSelect) else _strict(ZSelect, "diagnostics_config.z_select", z) for z in out.z_select]
         return out
@@ -355,7 +432,7 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
     """Diagnostics that save to a sympl-style Monitor."""
 
     def __init__(self, monitor, names: List[str], derived_names: List[str], z_select: List[ZSelect], lib=None, communicator=None,
-                 p_select=()):
+                 p_select=(), latlon=None, latlon_monitor=None):
         """
         Args:
             monitor: a sympl-style Monitor object
@@ -366,7 +443,15 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
             communicator: a communicator that holds the whole cube (run_cube): every store is gathered over it and only its
                 root hands the monitor anything -- quantities that lead with TILE_DIM.  None: this rank's tile alone
             p_select: the pressure surfaces to save variables of the dycore state (or `height`) on
+            latlon: a LatLonSelect: the variables to save on a regular latitude-longitude grid (needs `communicator`)
+            latlon_monitor: the monitor the lat-lon variables go to with the step's time (default: `monitor`, in one state with
+                the others)
         """
+        if latlon is not None and communicator is None:
+            raise ValueError("latlon regrids the whole cube on one device: MonitorDiagnostics needs the whole-cube communicator of "
+                             "pace_amd.util.run_cube (the driver: comm_config.type: cube, run_cube_driver)")
+        self.latlon = latlon
+        self.latlon_monitor = latlon_monitor if latlon_monitor is not None else monitor
         self.communicator = communicator
         self.names = names
         self.derived_names = derived_names
@@ -456,10 +541,23 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
         else:
             columns = self.pack([r for r in requests if r.packed_by_rank])
             gathered = self._gather(requests, columns, np.float32)
+            regridded = self._regrid(state) if self.latlon is not None else {}
             if gathered is None:
                 return
             monitor_state.update(gathered)
+            if self.latlon is not None and self.latlon_monitor is not self.monitor:
+                self.latlon_monitor.store({"time": time, **regridded})
+            else:
+                monitor_state.update(regridded)
         self.monitor.store(monitor_state)
+
+    def _regrid(self, state):
+        """The lat-lon arrays of a step: ONE pace_cube_regrid launch for all six tiles and ONE transfer (regrid_state).
+        {name: Quantity leading with LON_DIM} on the root, None elsewhere.  They are views of a buffer of their own, apart from
+        the gathered arrays'."""
+        grid_data = getattr(state, "grid_data", None)
+        centres = (grid_data.lon_agrid, grid_data.lat_agrid) if grid_data is not None else None
+        return self.communicator.regrid_state(self.latlon.windows(state), self.latlon.grid(), np.float32, centres=centres)
 
     def store_grid(self, grid_data):
         """lat, lon, lon_agrid, lat_agrid over their compute domains in float64.  GridData keeps these four on the host (numpy,
@@ -505,10 +603,16 @@ class MonitorDiagnostics(Diagnostics, WindowPacker):
                 self.monitor.store_constant({name: Quantity(stacked[name], dims=(c.TILE_DIM,) + dims[name], units="radians")})
             else:
                 self.monitor.store_constant({name: gathered[name]})
+        if self.latlon is not None:  # the targets' coordinates: lon_ll (nlon values) and lat_ll (nlat values)
+            grid = self.latlon.grid()
+            self.latlon_monitor.store_constant({"lon_ll": Quantity(grid.lon.copy(), dims=(c.LON_DIM,), units="radians")})
+            self.latlon_monitor.store_constant({"lat_ll": Quantity(grid.lat.copy(), dims=(c.LAT_DIM,), units="radians")})
 
     def cleanup(self):
         if self.communicator is None or self.communicator.rank == c.ROOT_RANK:
             self.monitor.cleanup()
+            if self.latlon_monitor is not self.monitor:
+                self.latlon_monitor.cleanup()
 
 
 # ---- the monitor ------------------------------------------------------------------------------------------------------------------
@@ -519,20 +623,24 @@ def _host_array(quantity, dims=None) -> np.ndarray:
     return view.detach().cpu().numpy() if torch.is_tensor(view) else np.asarray(view)
 
 
+GLOBAL_GRID_DIMS = ((c.LON_DIM,), (c.LAT_DIM,))  # what a global array on a regular grid leads with: it has no tile axis
+
+
 class _TimeChunkedVariable:
     """netcdf_monitor.py:20-40 with the tile axis already in place: (time_chunk_size, 1, *extent)."""
 
     def __init__(self, initial, time_chunk_size: int):
         first = _host_array(initial)
         self._global = tuple(initial.dims[:1]) == (c.TILE_DIM,)  # (the whole cube: the tile axis comes with the data)
-        self._data = np.zeros((time_chunk_size,) + (() if self._global else (1,)) + first.shape, dtype=first.dtype)
+        self.latlon = tuple(initial.dims[:1]) in GLOBAL_GRID_DIMS  # (a lat-lon array: global, and no tile axis at all)
+        self._data = np.zeros((time_chunk_size,) + (() if self._global or self.latlon else (1,)) + first.shape, dtype=first.dtype)
         self._data[0].reshape(first.shape)[...] = first
         self.dims = tuple(initial.dims[1:]) if self._global else tuple(initial.dims)
         self.units = initial.units
         self._i_time = 1
 
     def append(self, quantity):
-        a = _host_array(quantity) if self._global else _host_array(quantity, self.dims)
+        a = _host_array(quantity) if self._global or self.latlon else _host_array(quantity, self.dims)
         self._data[self._i_time].reshape(a.shape)[...] = a
         self._i_time += 1
 
@@ -606,7 +714,7 @@ class NpzMonitor:
             meta = {"time": {"dims": ["time"], "units": ""}}
             for name, chunked in self._chunked.items():
                 arrays[name] = chunked.data
-                meta[name] = {"dims": ["time", "tile"] + list(chunked.dims), "units": chunked.units}
+                meta[name] = {"dims": ["time"] + ([] if chunked.latlon else ["tile"]) + list(chunked.dims), "units": chunked.units}
             chunk_index = self._i_time // self._time_chunk_size
             self._write(self.FILENAME_FORMAT.format(chunk=chunk_index, tile=self._tile), arrays, meta)
         self._chunked = None
@@ -615,7 +723,7 @@ class NpzMonitor:
     def store_constant(self, state: Dict[str, Quantity]) -> None:
         for name, quantity in state.items():
             a, dims = _host_array(quantity), list(quantity.dims)
-            if dims[:1] != [c.TILE_DIM]:
+            if dims[:1] != [c.TILE_DIM] and tuple(dims[:1]) not in GLOBAL_GRID_DIMS:
                 a, dims = a[None], ["tile"] + dims
             self._write(self.CONSTANT_FILENAME_FORMAT.format(name=name, tile=self._tile), {name: a},
                         {name: {"dims": dims, "units": quantity.units}})

@@ -8,5 +8,6 @@ from .checkpointer import (Checkpointer, InsufficientTrialsError, NullCheckpoint
                            Threshold, ThresholdCalibrationCheckpointer, ValidationCheckpointer)
 from .restart import LevelOf, open_restart, write_restart  # noqa: F401,E402
 from .gather import Window, check_cube_items  # noqa: F401,E402
+from .latlon import LatLonGrid, build_regrid_table, check_regrid_table  # noqa: F401,E402
 from .monitor import NetCDFMonitor  # noqa: F401,E402
 from . import testing  # noqa: F401,E402

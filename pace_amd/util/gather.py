@@ -244,10 +244,11 @@ class GatherScatter:
             fac[key] = QuantityFactory(SubtileGridSizer(nx, ny, key[2]), self.device, meta.dtype)
         return fac[key]
 
-    def _gs_buffer(self, elements, dtype):
-        """The device buffer and the pinned host buffer of a whole state (kept: the next call of the same size reuses them)."""
+    def _gs_buffer(self, elements, dtype, what=None):
+        """The device buffer and the pinned host buffer of a whole state (kept: the next call of the same size reuses them;
+        `what`: a buffer apart from gather_state's of the same size)."""
         buf = self._gs_state()._gs_buffers
-        key = (int(elements), dtype)
+        key = (int(elements), dtype) if what is None else (int(elements), dtype, what)
         if key not in buf:
             buf[key] = _launch.staging(elements, dtype, self.device, alias_on_cpu=True)
         return buf[key]
@@ -402,6 +403,118 @@ class GatherScatter:
             else:
                 recv_state[m.name] = Quantity(arr, (c.TILE_DIM,) + m.dims, m.units, origin=(0,) * (len(m.dims) + 1), extent=arr.shape)
         return recv_state
+
+    # ---- regrid ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _rg_to_host(dense, host):
+        """The one transfer of a regrid_state call (regrid_state calls it through this name: the one-transfer tests count it
+        here); the root waits for it once."""
+        if host is not dense:
+            host.copy_(dense, non_blocking=True)
+
+    def _rg_points(self, geom, grid, posts):
+        """The point table of (geometry, grid) on the device: built from the six ranks' cell centres and uploaded ONCE."""
+        from . import latlon
+
+        state = self._gs_state()
+        if not hasattr(state, "_rg_tables"):
+            state._rg_tables = {}  # (n, nlon, nlat) -> (the tensors that keep the point table alive, npoints)
+            state._rg_items = collections.OrderedDict()  # the item tables, cached per set of addresses like gather's
+        key = (geom.n, grid.nlon, grid.nlat)
+        if key not in state._rg_tables:
+            centres = []
+            for r in sorted(posts):
+                given = posts[r]["centres"]
+                if given is None:  # the grid this project generates: a function of (n, tile) alone
+                    from . import gridgen
+
+                    terms = gridgen.tiles(geom.n, geom.nk)[r % 6]
+                    given = (terms["lon_agrid"], terms["lat_agrid"])
+                centres.append([latlon.compute_domain(a, geom.n) for a in given])
+            table = latlon.build_regrid_table(np.stack([x[0] for x in centres]), np.stack([x[1] for x in centres]), *grid.targets())
+            state._rg_tables[key] = (latlon.upload_points(geom, table, self.device), table.npoints)
+        return state._rg_tables[key]
+
+    def _rg_launch(self, posts, names, grid, dtype):
+        """On the last rank to arrive, as the root's communicator: the launches and the transfer of one regrid_state call.
+        Returns (host buffer, metas)."""
+        from . import latlon
+
+        ranks = sorted(posts)
+        if len({posts[r]["stream"] for r in ranks}) != 1:
+            raise RuntimeError("the tiles of a regrid called it on different streams: the launch is ordered behind one")
+        shapes = [[(q.dims, q.extent, q.data.dtype) for q in posts[r]["qs"]] for r in ranks]
+        if any(s != shapes[0] for s in shapes[1:]):
+            raise ValueError("the tiles of a regrid hand over different fields")
+        every = [q for r in ranks for q in posts[r]["qs"]]
+        self._gs_check_real(every)
+        geom = geom_of(every)
+        keep, npoints = self._rg_points(geom, grid, posts)
+        specs, metas, offset = [], [], 0
+        for f, name in enumerate(names):
+            q = posts[ranks[0]]["qs"][f]
+            kind, k0, nk = latlon.levels_of(name, q, geom.n)
+            if kind == _lib.DIAG_WINDOW3D:
+                metas.append(Meta(name, (c.LON_DIM, c.LAT_DIM, c.Z_DIM), (grid.nlon, grid.nlat, nk), q.units, dtype))
+            else:
+                metas.append(Meta(name, (c.LON_DIM, c.LAT_DIM), (grid.nlon, grid.nlat), q.units, dtype))
+            specs.append((tuple(posts[r]["qs"][f].ptr for r in ranks), kind, k0, nk, offset))
+            offset += npoints * nk
+        dense, host = self._gs_buffer(offset, dtype, "regrid")
+        key = (geom.n, grid.nlon, grid.nlat, tuple(specs))  # (the table does not depend on the dense type)
+        state = self._gs_state()
+        tables = state._rg_items.get(key)
+        if tables is not None:
+            state._rg_items.move_to_end(key)
+        items = [latlon.regrid_item(*spec) for spec in specs] if tables is None else None
+        state._rg_items[key] = latlon.launch_regrid(self.lib, geom, keep[0], npoints, items, dense, self.stream(), tables)
+        if len(state._rg_items) > TABLE_CACHE:
+            state._rg_items.popitem(last=False)
+        self._rg_to_host(dense, host)
+        return host, metas
+
+    def regrid_state(self, windows, grid, transfer_type=None, centres=None):
+        """The state on a regular latitude-longitude grid (this project's extension; pace_amd/util/latlon.py): cell-centre
+        fields of all six tiles interpolated on the device and only the lat-lon arrays transferred.
+
+        ``windows``: {name: Quantity with dims (x, y) or (x, y, z), or a gather Window -- one level's plane, or a level range} of
+        this rank's tile (``time`` is copied from the root); ``grid``: a LatLonGrid; ``transfer_type``: numpy.float32 or
+        numpy.float64 (by default the fields' own type); ``centres``: this tile's (lon_agrid, lat_agrid) [radians], by default
+        those of the grid pace_amd.util.gridgen generates.  The table is built once per (geometry, grid) and uploaded once; a
+        call is ONE pace_cube_regrid launch per PACE_REGRID_MAX_ITEMS variables, ONE transfer and ONE synchronisation.  On the
+        root the values are Quantities of numpy arrays with dims (lon, lat) or (lon, lat, z) -- views of ONE pinned host buffer
+        that THE NEXT CALL OVERWRITES, as gather_state's are; None on the other ranks.  Needs the whole cube on one device
+        (run_cube, run_cube_driver)."""
+        if self._gs_mode() != "cube":
+            raise ValueError("regrid_state needs a communicator that holds the whole cube on one device: run the six tiles with "
+                             "pace_amd.util.run_cube (the driver: comm_config.type: cube, run_cube_driver)")
+        root = self.rank == c.ROOT_RANK
+        names = [n for n in windows if n != "time"]
+        qs = [windows[n] for n in names]
+        if not names:
+            return ({"time": windows["time"]} if "time" in windows else {}) if root else None
+        dtype = _TORCH_OF[np.dtype(transfer_type)] if transfer_type is not None else qs[0].data.dtype
+        from . import latlon
+
+        for name, q in zip(names, qs):  # (every rank refuses its own before the ranks meet)
+            latlon.levels_of(name, q, q.data.shape[0] - 2 * c.N_HALO_DEFAULT - 1)
+
+        def last(posts):
+            return posts[c.ROOT_RANK]["owner"]._rg_launch(posts, names, grid, posts[c.ROOT_RANK]["dtype"])
+
+        payload = {"qs": qs, "stream": self._gs_stream_id(), "owner": self, "centres": centres, "dtype": dtype}
+        host, metas = self.comm.rendezvous(("regrid_state", tuple(names), grid.nlon, grid.nlat), payload, last)
+        if not root:
+            return None
+        _launch.wait_for(self.device)
+        flat = host.numpy()
+        out = {"time": windows["time"]} if "time" in windows else {}
+        offset = 0
+        for m in metas:
+            size = _size(m.extent)
+            out[m.name] = Quantity(flat[offset:offset + size].reshape(m.extent), m.dims, m.units, origin=(0,) * len(m.dims), extent=m.extent)
+            offset += size
+        return out
 
     # ---- scatter -----------------------------------------------------------------------------------------------
     def _gs_global_meta(self, name, q):

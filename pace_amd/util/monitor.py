@@ -13,7 +13,8 @@ Where the chunks differ from the reference: it gathers a state over the TILE com
 own chunks with a tile axis of length 1, and only the constants are gathered over the globe.  With layout (1, 1) a tile is one
 rank and that gather moves nothing; here the state is gathered over the globe as the constants are, the tile axis has its true
 length of 6, and the one file per chunk carries the root's tile in its name (``_tile0``).  A state whose quantities already
-lead with TILE_DIM (what MonitorDiagnostics hands over after its own gather) is appended as it is.
+lead with TILE_DIM (what MonitorDiagnostics hands over after its own gather) is appended as it is, and so is one that leads
+with LON_DIM or LAT_DIM (a regridded array: ``[time, lon, lat(, z)]``, no tile axis).
 """
 import os
 from datetime import datetime, timedelta
@@ -101,7 +102,7 @@ class NetCDFMonitor:
     def _gathered(self, state):
         """The state over the globe: on the root {name: Quantity leading with TILE_DIM} (and "time"), None elsewhere."""
         fields = [q for name, q in state.items() if name != "time"]
-        if fields and all(tuple(q.dims[:1]) == (c.TILE_DIM,) for q in fields):
+        if fields and all(tuple(q.dims[:1]) in ((c.TILE_DIM,), (c.LON_DIM,), (c.LAT_DIM,)) for q in fields):  # (global already)
             return dict(state)
         return self._communicator.gather_state(state, transfer_type=np.float32)
 

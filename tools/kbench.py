@@ -19,6 +19,11 @@
     python tools/kbench.py --only cube_gather       one output step (fourteen variables as float32 on the host) of six C96 and six
                                                     C192 tiles on this device: one pace_cube_gather launch and one transfer
                                                     against six pace_diag_pack passes, one per tile, with a transfer each
+    python tools/kbench.py --only cube_regrid       one output step of fourteen 3-D variables of six C96 and six C192 tiles to a
+                                                    1 degree lat-lon grid as float32 on the host: one pace_cube_regrid launch and
+                                                    one transfer, against one pace_cube_gather launch, the whole cube's transfer
+                                                    and the same table applied with numpy, and against a torch restatement on
+                                                    the device; alternating, medians, launches and transfers apart
     python tools/kbench.py --only halo_cube         the seven halo-updater groups of an acoustic substep for six tiles on this
                                                     device: the fused path (run_cube: one pace_halo_cube launch per update for
                                                     the whole cube) against the snapshot path (ThreadComm's pack, copies,
@@ -70,6 +75,10 @@ def main():
     if args.only == "cube_gather":  # (its own fields, six tiles, C96 and C192)
         for size in (96, 192):
             cube_gather_bench(lib, size, nz, args.reps)
+        return
+    if args.only == "cube_regrid":  # (its own fields, six tiles, C96 and C192)
+        for size in (96, 192):
+            cube_regrid_bench(lib, size, nz, args.reps)
         return
     if args.only == "plev_diag":  # (its own fields)
         plev_diag_bench(lib, n, nz, max(args.reps, 30))
@@ -967,6 +976,132 @@ def cube_gather_bench(lib, n, nz, reps, device="cuda"):
               f"transfers alone {med['transfer']:9.1f} us ({mib / 1024 / (med['transfer'] * 1e-6):5.1f} GiB/s)")
     print(f"  ratio per tile / fused: step {np.median(times['per tile', 'step']) / np.median(times['fused', 'step']):.2f}, "
           f"launches {np.median(times['per tile', 'launches']) / np.median(times['fused', 'launches']):.2f}")
+
+
+def cube_regrid_bench(lib, n, nz, reps, device="cuda", grid=(360, 180)):
+    """One output step of fourteen 3-D cell-centre variables of six tiles on a regular lat-lon grid, as float32 on the host.
+
+    regrid    ONE pace_cube_regrid launch for all variables, one transfer of the lat-lon arrays, one synchronisation -- what
+              MonitorDiagnostics does with `latlon` under run_cube_driver;
+    gather    the route without the kernel: ONE pace_cube_gather launch for all six tiles and all variables (84 items), the
+              whole cube's transfer, then the same table applied on the host with numpy (float64, the contract's order);
+    torch     a torch restatement on the device -- per variable the six compute domains stacked, three index_select and the
+              weighted sum in float64, narrowed to float32 -- and the transfer of the lat-lon arrays.
+    Host clock from an idle device to the end of the last synchronisation (gather: to the end of the numpy step); the three
+    alternate, medians are reported.  The split: the launches alone (enqueued, then one synchronisation), the transfers alone
+    (of the buffers they filled), and for `gather` the numpy step alone."""
+    import time
+
+    from pace_amd import _launch
+    from pace_amd import _lib as L
+    from pace_amd.util import CubedSphereCommunicator, NullComm, QuantityFactory, SubtileGridSizer, gridgen, latlon
+    from pace_amd.util.gather import _Layout, _meta_of
+
+    X, Y, Z, H = "x", "y", "z", 3
+    real = torch.float32 if lib.real_bytes == 4 else torch.float64
+    qf = QuantityFactory(SubtileGridSizer(n, n, nz), device, real)
+    names = ["ua", "va", "w", "pt", "delp", "delz", "qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel", "qo3mr", "qcld"]
+    rng = np.random.default_rng(n)
+    fields = {name: [qf.from_array(rng.random((n + 7, n + 7, nz + 1)), [X, Y, Z], "") for _ in range(6)] for name in names}
+    assert len(fields) == 14
+    terms = gridgen.tiles(n, nz)
+    target = latlon.LatLonGrid(*grid)
+    table = latlon.build_regrid_table(np.stack([t["lon_agrid"][H:H + n, H:H + n] for t in terms]),
+                                      np.stack([t["lat_agrid"][H:H + n, H:H + n] for t in terms]), *target.targets())
+    npoints = table.npoints
+    cube = CubedSphereCommunicator(NullComm(0, 6), device=device, lib=lib)
+    stream = _launch.stream_of(device)
+    # regrid
+    some = fields[names[0]][0]
+    geom = _launch.geometry([some], lambda q: "", "")
+    points = latlon.upload_points(geom, table, torch.device(device))
+    items = [latlon.regrid_item([q.ptr for q in fields[name]], L.DIAG_WINDOW3D, 0, nz, f * npoints * nz) for f, name in enumerate(names)]
+    ll_dense, ll_host = _launch.staging(len(names) * npoints * nz, torch.float32, device)
+    tables = latlon.launch_regrid(lib, geom, points[0], npoints, items, ll_dense, stream)
+    # gather
+    windows = {t: [fields[name][t] for name in names] for t in range(6)}
+    layout = _Layout([_meta_of(name, fields[name][0]) for name in names], 6)
+    cube_dense, cube_host = _launch.staging(layout.total, torch.float32, device)
+    flat = cube_host.numpy()
+    lin = ((table.tile.astype(np.int64) * n + (table.i - H)) * n + (table.j - H))  # into a variable's [6 n n, nz] block
+    on_host = np.empty((len(names), npoints, nz), dtype=np.float32)
+    # torch
+    lin_dev = [torch.as_tensor(lin[:, m].copy(), device=device) for m in range(3)]
+    w_dev = [torch.as_tensor(table.w[:, m].copy(), device=device)[:, None] for m in range(3)]
+    t_dense, t_host = _launch.staging(len(names) * npoints * nz, torch.float32, device)
+    t_view = t_dense.view(len(names), npoints, nz)
+
+    def sync():
+        if device == "cuda":
+            torch.cuda.synchronize()
+
+    def numpy_step():
+        for f in range(len(names)):
+            block = layout.array(flat, f).reshape(6 * n * n, nz)
+            a = [table.w[:, m, None] * block[lin[:, m]].astype(np.float64) for m in range(3)]
+            on_host[f] = (a[0] + a[1]) + a[2]
+
+    def regrid(launch=True, transfer=True, host_step=True):
+        if launch:
+            latlon.launch_regrid(lib, geom, points[0], npoints, None, ll_dense, stream, tables)
+        if transfer:
+            ll_host.copy_(ll_dense, non_blocking=True)
+        sync()
+
+    def gather(launch=True, transfer=True, host_step=True):
+        if launch:
+            cube._gs_launch(False, windows, layout, cube_dense)
+        if transfer:
+            cube_host.copy_(cube_dense, non_blocking=True)
+        sync()
+        if host_step:
+            numpy_step()
+
+    def restated(launch=True, transfer=True, host_step=True):
+        if launch:
+            for f, name in enumerate(names):
+                block = torch.stack([q.data[H:H + n, H:H + n, :nz] for q in fields[name]]).reshape(6 * n * n, nz).to(torch.float64)
+                a = [w_dev[m] * block.index_select(0, lin_dev[m]) for m in range(3)]
+                t_view[f] = (a[0] + a[1]) + a[2]
+        if transfer:
+            t_host.copy_(t_dense, non_blocking=True)
+        sync()
+
+    paths = (("regrid", regrid), ("gather", gather), ("torch", restated))
+    for _, fn in paths:  # warm-up: tables built, buffers allocated and pinned
+        fn()
+    got = ll_host.numpy().reshape(on_host.shape)
+    # (the gather route interpolates what was narrowed to float32 first: the same arrays to rounding, not to the bit)
+    assert np.allclose(got, on_host, rtol=1e-6, atol=0) and np.allclose(got, t_host.numpy().reshape(on_host.shape), rtol=1e-6, atol=0), \
+        "the three routes differ"
+    parts = {"step": (True, True, True), "launches": (True, False, False), "transfer": (False, True, False)}
+    times = {(path, part): [] for path, _ in paths for part in parts}
+    host_times = []
+    for _ in range(reps):
+        for part, flags in parts.items():
+            for path, fn in paths:
+                sync()
+                t0 = time.perf_counter()
+                fn(*flags)
+                times[path, part].append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        numpy_step()
+        host_times.append(time.perf_counter() - t0)
+    ll_mib, cube_mib = ll_dense.numel() * 4 / 2 ** 20, layout.total * 4 / 2 ** 20
+    print(f"one output step of six C{n} x {nz} tiles, fourteen 3-D variables, to {grid[0]} x {grid[1]} points as float32 on the host: "
+          f"{ll_mib:.1f} MiB of lat-lon arrays ({npoints} points) against {cube_mib:.1f} MiB of the cube ({6 * n * n} cells, ratio "
+          f"{ll_mib / cube_mib:.3f}); {reps} repetitions, alternating; host clock, idle device to the end; medians")
+    what = {"regrid": "1 pace_cube_regrid, 1 transfer         ", "gather": "1 pace_cube_gather, 1 transfer, numpy  ",
+            "torch": "torch index_select + sum, 1 transfer   "}
+    for path, _ in paths:
+        med = {part: float(np.median(times[path, part])) * 1e6 for part in parts}
+        mib = cube_mib if path == "gather" else ll_mib
+        extra = f"   numpy alone {float(np.median(host_times)) * 1e6:11.1f} us" if path == "gather" else ""
+        print(f"  {path:6s} ({what[path]}): step {med['step']:11.1f} us   launches alone {med['launches']:9.1f} us   "
+              f"transfer alone {med['transfer']:9.1f} us ({mib:6.1f} MiB, {mib / 1024 / (med['transfer'] * 1e-6):5.1f} GiB/s){extra}")
+    step = {path: float(np.median(times[path, "step"])) for path, _ in paths}
+    print(f"  ratio to regrid: gather {step['gather'] / step['regrid']:.2f}, torch {step['torch'] / step['regrid']:.2f}; the cube's "
+          f"launch and transfer without the numpy step: {(float(np.median(times['gather', 'launches'])) + float(np.median(times['gather', 'transfer']))) * 1e6:.1f} us")
 
 
 def checkpointer_bench(lib, n, nz, reps):
