@@ -757,6 +757,35 @@ int pace_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_trials
 int64_t pace_ckpt_validate_workspace_bytes(const pace_ckpt_item_t* items, int nitems);
 int pace_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspace, double* out, void* stream);
 
+/* ---- Nudging (util/pace/util/nudging.py:44,70): the state relaxed toward reference fields.  Up to PACE_NUDGE_MAX_ITEMS windows
+ * of fields by ONE launch, both storage types, no atomics, no workspace, no host synchronisation.  items: HOST array of nitems
+ * items.  field, ref0, ref1 and tendency of an item share the storage geometry of geom.  For every point of an item's window, in
+ * double on the stored values (the float32 library widens first; exact), without FMA and without a reciprocal, in this order:
+ *   r = ref1 ? r0 + (r1 - r0) * weight : r0      the reference, held (ref1 == NULL) or interpolated within its bracket
+ *   t = (r - q) / timescale                      the nudging tendency
+ *   if tendency:    tendency = (pace_real_t) t
+ *   if apply != 0:  field    = (pace_real_t)(q + t * dt)
+ * In the float64 library with ref1 == NULL that is the reference's expression bit for bit.  The narrowing is a plain cast (round to
+ * nearest even, overflow to +-inf).  For a PACE_DIAG_PLANE item k0 = 0 and nk = 1, and each pointer is element (0, 0) of a 2-D field
+ * or of ONE level.  Nothing outside the windows is written (not the halo, not level nk, not the row padding), nothing outside the
+ * windows' elements is read, and with apply == 0 the field is only read.  ref0 and ref1 may be one array; tendency may be ref0 or
+ * ref1 (an element is read and written by one thread).  Two items whose windows overlap on one written array: undefined.
+ * PACE_ERR_ARG: nitems < 1 or > PACE_NUDGE_MAX_ITEMS, a kind other than WINDOW3D and PLANE, a window that is empty or outside the
+ * storage (n + 7, n + 7, nk + 1), a NULL field or ref0, tendency == NULL with apply == 0 (nothing to do), a timescale that is not
+ * finite and > 0, a weight outside [0, 1] or NaN, a dt that is not finite, a field whose pointer equals ref0, ref1 or tendency. */
+#define PACE_NUDGE_MAX_ITEMS 32
+typedef struct {
+  pace_real_t* field;            /* the state's field, element (0,0,0) of its storage; read, and written when apply != 0 */
+  const pace_real_t* ref0;       /* reference at the bracket's start, same storage geometry */
+  const pace_real_t* ref1;       /* reference at the bracket's end, or NULL: no interpolation */
+  pace_real_t* tendency;         /* out, same geometry, or NULL */
+  int32_t kind;                  /* PACE_DIAG_WINDOW3D | PACE_DIAG_PLANE */
+  int32_t i0, j0, k0, ni, nj, nk;   /* window in the storage; PLANE: k0 = 0, nk = 1 */
+  double timescale;              /* seconds */
+} pace_nudge_item_t;
+int pace_nudge(const pace_geom_t* geom, const pace_nudge_item_t* items, int nitems, double weight, double dt, int apply,
+               void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

@@ -89,7 +89,7 @@ def window_of(quantity, level=None, window=None):
 
 
 def set_window(item, window):
-    """What window_of returned into a DiagItem, UnpackItem, CubeItem or RestartItem."""
+    """What window_of returned into a DiagItem, UnpackItem, CubeItem, RestartItem or NudgeItem."""
     item.field, item.kind, item.i0, item.j0, item.k0, item.ni, item.nj, item.nk = window
 
 

@@ -197,6 +197,15 @@ class CkptItem(C.Structure):  # include/pace_hip.h pace_ckpt_item_t
                 ("expected", c_dp), ("ei", C.c_int64), ("ej", C.c_int64), ("ek", C.c_int64), ("rtol", C.c_double), ("atol", C.c_double)]
 
 
+NUDGE_MAX_ITEMS = 32  # include/pace_hip.h PACE_NUDGE_MAX_ITEMS
+
+
+class NudgeItem(C.Structure):  # include/pace_hip.h pace_nudge_item_t
+    _fields_ = [("field", c_dp), ("ref0", c_dp), ("ref1", c_dp), ("tendency", c_dp), ("kind", C.c_int32), ("i0", C.c_int32),
+                ("j0", C.c_int32), ("k0", C.c_int32), ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32),
+                ("timescale", C.c_double)]
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -305,6 +314,7 @@ _PROTOS = {
     "pace_ckpt_thresholds": (C.c_int, [_P(CkptItem), C.c_int, C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_ckpt_validate_workspace_bytes": (C.c_int64, [_P(CkptItem), C.c_int]),
     "pace_ckpt_validate": (C.c_int, [_P(CkptItem), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
+    "pace_nudge": (C.c_int, [_P(Geom), _P(NudgeItem), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

@@ -816,6 +816,21 @@ int pace_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspac
   return launch_ckpt_validate(items, nitems, workspace, out, S(stream));
 }
 
+int pace_nudge(const pace_geom_t* geom, const pace_nudge_item_t* items, int nitems, double weight, double dt, int apply,
+               void* stream) {
+  NEED(geom && items);
+  if (nitems < 1 || nitems > PACE_NUDGE_MAX_ITEMS) return PACE_ERR_ARG;
+  if (!(weight >= 0.0 && weight <= 1.0) || !std::isfinite(dt)) return PACE_ERR_ARG;
+  for (int m = 0; m < nitems; ++m) {
+    const pace_nudge_item_t& it = items[m];
+    if (!window_ok(geom, it) || !it.ref0) return PACE_ERR_ARG;
+    if (!it.tendency && !apply) return PACE_ERR_ARG;
+    if (!(std::isfinite(it.timescale) && it.timescale > 0.0)) return PACE_ERR_ARG;
+    if (it.field == it.ref0 || it.field == it.ref1 || it.field == it.tendency) return PACE_ERR_ARG;
+  }
+  return launch_nudge(make_geo(geom), items, nitems, weight, dt, apply, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

@@ -304,6 +304,8 @@ long ckpt_validate_blocks(const pace_ckpt_item_t* items, int nitems);
 int launch_ckpt_accumulate(const pace_ckpt_item_t* items, int nitems, int first, hipStream_t st);
 int launch_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_trials, void* workspace, double* out, hipStream_t st);
 int launch_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspace, double* out, hipStream_t st);
+// k_nudge.hip
+int launch_nudge(const Geo& g, const pace_nudge_item_t* items, int nitems, double weight, double dt, int apply, hipStream_t st);
 // k_dycore.hip
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);

@@ -24,6 +24,9 @@ What is accepted, refused and ignored:
                         written (the Driver warns once)
   diagnostics_config.latlon  (not in the reference) cell-centre variables on a regular latitude-longitude grid, regridded on the
                         device; with comm_config.type cube only, ValueError with any other
+  nudging_config        (not in the reference) timescale_seconds, reference_paths, label, store_tendencies: the state relaxed
+                        toward a sequence of Fortran restarts, interpolated in time, one launch per step (driver/nudging.py);
+                        delp, delz, phis and anything that is no 3-D field of a Fortran restart: ValueError
   performance_config    parsed and kept; nothing is written
   stencil_config.compilation_config.backend  kept as `requested_backend`; the backend is always hip:gfx950
 """
@@ -42,6 +45,7 @@ from ..fv3core import DynamicalCoreConfig
 from ..fv3core._config import strict_value
 from ..physics import PhysicsConfig, PhysicsState
 from .diagnostics import DiagnosticsConfig, ZSelect  # noqa: F401  (ZSelect: named here before diagnostics.py existed)
+from .nudging import NudgingConfig
 from .state import DriverState, TendencyState
 
 _DERIVED = ("dt_atmos", "layout", "npx", "npy", "npz", "ntiles")
@@ -451,6 +455,7 @@ class DriverConfig:
         safety_check_frequency: number of model timesteps between checks of the state, None or 0 for never
         restart_config: the reference's own restart format: refused when it enables output
         fortran_restart_config: restart files in the Fortran model's format (not in the reference)
+        nudging_config: relax the state toward a sequence of Fortran restarts (not in the reference); None: no nudging
     """
 
     stencil_config: StencilConfig
@@ -478,6 +483,7 @@ class DriverConfig:
     output_initial_state: bool = False
     output_frequency: int = 1
     safety_check_frequency: Optional[int] = None
+    nudging_config: Optional[NudgingConfig] = None
 
     def __post_init__(self):
         if self.pair_debug:
@@ -585,6 +591,8 @@ class DriverConfig:
                           ("restart_config", RestartConfig), ("fortran_restart_config", FortranRestartConfig)):
             if key in kwargs:
                 kwargs[key] = kind.from_dict(kwargs[key])
+        if kwargs.get("nudging_config") is not None:
+            kwargs["nudging_config"] = NudgingConfig.from_dict(kwargs["nudging_config"])
         config = cls(**kwargs)
         config.source = source
         return config

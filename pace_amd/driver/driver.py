@@ -8,7 +8,8 @@ A step is the reference's (driver.py:618-640): DynamicalCore.step_dynamics, Dyco
 each a class of its own that can also be called by hand; the driver only strings them together, advances the time and, every
 safety_check_frequency steps, checks the state (SafetyChecker: one launch pair and one transfer) and, every output_frequency
 steps, stores the diagnostics (MonitorDiagnostics: one pack launch and one transfer).  What the reference's constructor does
-for DaCe, build modes, its own restart format and the performance collector's files is not here.  Restart files are written in
+for DaCe, build modes, its own restart format and the performance collector's files is not here.  With nudging_config the state is relaxed toward a sequence of
+Fortran restarts after the end-of-step update (driver/nudging.py: one pace_nudge launch a step).  Restart files are written in
 the FORTRAN model's format (fortran_restart_config, write_fortran_restart: one pack launch and one transfer), which
 initialization.type fortran_restart reads back.
 
@@ -26,6 +27,7 @@ from ..physics import Physics
 from ..stencils import update_atmos_state
 from ..util import CubedSphereCommunicator, Timer
 from .config import DriverConfig
+from .nudging import Nudging
 from .safety_checks import SafetyChecker
 
 _REGISTRATION_LOCK = threading.Lock()
@@ -105,6 +107,10 @@ class Driver:
                 self.dycore_to_physics = None
                 self.end_of_step_update = None
             self.diagnostics = config.diagnostics_config.diagnostics_factory(communicator=communicator, lib=self.lib)
+            self.nudging = None
+            if config.nudging_config is not None:
+                self.nudging = Nudging(config.nudging_config, quantity_factory=self.quantity_factory, communicator=communicator)
+            self.nudging_tendencies = None  # the last step's, with nudging_config.store_tendencies
         if config.output_initial_state:
             self.diagnostics.store(time=self.time, state=self.state)
         self._time_run = self.config.start_time
@@ -176,6 +182,9 @@ class Driver:
                     self.end_of_step_update(dycore_state=self.state.dycore_state, phy_state=self.state.physics_state,
                                             u_dt=self.state.tendency_state.u_dt, v_dt=self.state.tendency_state.v_dt,
                                             pt_dt=self.state.tendency_state.pt_dt, dt=float(dt))
+                if self.nudging is not None:  # toward the reference at the END of the step (self.time is still its beginning)
+                    self.nudging_tendencies = self.nudging(self.state.dycore_state, self.time + self.config.timestep,
+                                                           self.config.timestep)
             self._end_of_step_actions(step)
 
     def step_all(self):

@@ -7,6 +7,7 @@ from ._timing import KernelTimes, NullTimer, Timer  # noqa: F401,E402
 from .checkpointer import (Checkpointer, InsufficientTrialsError, NullCheckpointer, SavepointThresholds, SnapshotCheckpointer,  # noqa: F401,E402
                            Threshold, ThresholdCalibrationCheckpointer, ValidationCheckpointer)
 from .restart import LevelOf, open_restart, write_restart  # noqa: F401,E402
+from .nudging import apply_nudging, get_nudging_tendencies  # noqa: F401,E402
 from .gather import Window, check_cube_items  # noqa: F401,E402
 from .latlon import LatLonGrid, build_regrid_table, check_regrid_table  # noqa: F401,E402
 from .monitor import NetCDFMonitor  # noqa: F401,E402

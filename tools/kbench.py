@@ -16,6 +16,9 @@
     python tools/kbench.py --only restart_pack      write_restart of a state's fifteen 3-D fields and three planes (launch,
                                                     device-to-host copy, file writes) against a torch / numpy restatement, the
                                                     same way, with the split into launch, transfer and write
+    python tools/kbench.py --only nudging           apply_nudging of u, v, pt, qvapor between two references with the tendencies
+                                                    stored (one pace_nudge launch) against a torch restatement on the device,
+                                                    the same way, with the launch alone and its bandwidth
     python tools/kbench.py --only cube_gather       one output step (fourteen variables as float32 on the host) of six C96 and six
                                                     C192 tiles on this device: one pace_cube_gather launch and one transfer
                                                     against six pace_diag_pack passes, one per tile, with a transfer each
@@ -85,6 +88,9 @@ def main():
         return
     if args.only == "checkpointer":  # (its own fields)
         checkpointer_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "nudging":  # (its own fields)
+        nudging_bench(lib, n, nz, args.reps)
         return
     m = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(m, n, nz)
@@ -1201,6 +1207,68 @@ def checkpointer_bench(lib, n, nz, reps):
     print(f"  pace_ckpt_validate alone (launch pair, device events, mean of {pair['ncalls']}): {pair_ms:.3f} ms for {read / 1e6:.0f} MB read "
           f"= {read / (pair_ms * 1e-3) / 1e9:.0f} GB/s (the expected slabs are C-ordered: lanes read them with a stride of {(n + 7) * (nz + 1)} doubles)")
     scratch.cleanup()
+
+
+def nudging_bench(lib, n, nz, reps):
+    """apply_nudging of u, v, pt and qvapor of a C<n> x <nz> tile between two references, tendencies stored (ONE pace_nudge
+    launch), against the same four expressions per field restated with torch on the device (views of the compute domains; the
+    tendency into its preallocated storage, the state in place).  Neither synchronises; both are timed with the host clock from
+    an idle device to the end of a synchronisation added for the measurement, alternating, medians; then the launch alone in
+    device events, with its bandwidth over the algorithmic bytes: three reads and two writes per element of the windows."""
+    import time
+    from datetime import timedelta
+
+    from pace_amd.util import CubedSphereCommunicator, NullComm, QuantityFactory, SubtileGridSizer, apply_nudging
+
+    real = torch.float32 if lib.real_bytes == 4 else torch.float64
+    sizer = SubtileGridSizer.from_tile_params(nx_tile=n, ny_tile=n, nz=nz, n_halo=3, extra_dim_lengths={}, layout=(1, 1))
+    qf = QuantityFactory(sizer, device="cuda", dtype=real)
+    communicator = CubedSphereCommunicator(NullComm(rank=0, total_ranks=6, fill_value=0.0), device="cuda", lib=lib)
+    dims = {"u": ["x", "y_interface", "z"], "v": ["x_interface", "y", "z"], "pt": ["x", "y", "z"], "qvapor": ["x", "y", "z"]}
+    rng = np.random.default_rng(0)
+
+    def fields(units=""):
+        return {name: qf.from_array(rng.uniform(1.0, 2.0, (n + 7, n + 7, nz + 1)), d, units) for name, d in dims.items()}
+
+    state, start, end, tendencies = fields("u"), fields(), fields(), fields()
+    timescales = {name: timedelta(seconds=21600) for name in dims}
+    step, weight = timedelta(seconds=225), 0.3
+    elements = sum(int(np.prod(q.extent)) for q in state.values())
+
+    def hip():
+        apply_nudging(state, start, timescales, step, communicator=communicator, end_reference_state=end, weight=weight,
+                      tendencies=tendencies)
+
+    def restated():
+        for name in dims:
+            q, r0, r1, t = state[name].view[:], start[name].view[:], end[name].view[:], tendencies[name].view[:]
+            r = r0 + (r1 - r0) * weight
+            t.copy_((r - q) / 21600.0)
+            q += t * 225.0
+
+    paths = {"hip": hip, "torch": restated}
+    times = {k: [] for k in paths}
+    for fn in paths.values():
+        for _ in range(3):
+            fn()
+    for _ in range(reps):
+        for k, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    moved = elements * 5 * lib.real_bytes
+    print(f"nudging C{n} x {nz}, float{8 * lib.real_bytes} fields: u, v, pt, qvapor between two references, tendencies stored; "
+          f"{elements} elements, {moved / 1e6:.0f} MB algorithmic (3 reads, 2 writes); medians of {reps} alternating runs, ms")
+    for k in paths:
+        print(f"  {k:6s} {med[k]:9.3f} ms   (min {min(times[k]):.3f})")
+    print(f"  ratio torch / hip {med['torch'] / med['hip']:.2f}")
+    events = times_hip_calibrate(hip, reps)
+    launch = float(np.median(events))
+    print(f"  the pace_nudge launch in device events: median {launch:.3f} ms (min {min(events):.3f}) = "
+          f"{moved / (launch * 1e-3) / 1e9:.0f} GB/s over the algorithmic bytes")
 
 
 def times_hip_calibrate(fn, reps=10):
