@@ -190,7 +190,8 @@ int pace_d_sw_pingpong_supported(const pace_geom_t* geom, const pace_dsw_config_
  * d_sw.py:633-683; otherwise the call returns PACE_ERR_UNSUPPORTED.) */
 int pace_d_sw_wind_outputs_supported(const pace_geom_t* geom, const pace_dsw_config_t* cfg);
 /* The two queries above AND the condition on the column namelist in one call (what pace_d_sw* really accepts for this object):
- * 0 = no separate outputs, 1 = the four scalars', 3 = the scalars' and the winds'.  col: the HOST arrays given to pace_d_sw_prepare
+ * 0 = no separate outputs, 1 = the four scalars', 3 = the scalars' and the winds' (this library answers 0 or 3: the kernel that
+ * gives the scalars outputs of their own takes the winds too).  col: the HOST arrays given to pace_d_sw_prepare
  * (get_column_namelist, d_sw.py:633-683). */
 int pace_d_sw_outputs_supported(const pace_geom_t* geom, const pace_column_t* col, const pace_dsw_config_t* cfg);
 /* Once per object, after zero-filling the workspace: uploads the column namelist (synchronises). */

@@ -161,11 +161,11 @@ int pace_d_sw_pingpong_supported(const pace_geom_t* geom, const pace_dsw_config_
   return (geom && cfg && dsw_pingpong_supported(make_geo(geom), cfg)) ? 1 : 0;
 }
 int pace_d_sw_wind_outputs_supported(const pace_geom_t* geom, const pace_dsw_config_t* cfg) {
-  return (geom && cfg && dsw_winds_in_scalars(make_geo(geom), cfg)) ? 1 : 0;
+  return pace_d_sw_pingpong_supported(geom, cfg);  // (the kernel that gives the scalars outputs of their own takes the winds too)
 }
 
 int pace_d_sw_outputs_supported(const pace_geom_t* geom, const pace_column_t* col, const pace_dsw_config_t* cfg) {
-  // the ONE predicate of what launch_d_sw accepts: the two queries above plus the condition on the column namelist they cannot see
+  // the ONE predicate of what launch_d_sw accepts: the query above plus the condition on the column namelist it cannot see
   if (!geom || !col || !cfg || !col->nord_v || !col->nord_w || !col->nord_t) return 0;
   return dsw_outputs_supported(make_geo(geom), col, cfg);
 }
@@ -231,7 +231,7 @@ int pace_d_sw_overlapped(int prep, DSW_PARAMS, void* side_stream, void* ev_prep,
   hipStream_t main_s = S(stream), side_s = S(side_stream);
   hipEvent_t e_prep = (hipEvent_t)ev_prep, e_scal = (hipEvent_t)ev_scalars, e_done = (hipEvent_t)ev_done;
   int rc;
-  if (geom && cfg && dsw_winds_in_scalars(make_geo(geom), cfg)) {
+  if (geom && cfg && dsw_pingpong_supported(make_geo(geom), cfg)) {
     // the winds are the last pass of the kernel that transports the scalars: one stream, nothing left for the side stream (the
     // kinetic energy there next to vorticity + divergence damping measured slower: profiles/r05_experiments x05)
     if ((rc = run(prep | 14, stream))) return rc;

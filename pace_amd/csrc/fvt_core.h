@@ -19,7 +19,7 @@
 // w, q_con and pt back to back, the mass fluxes of delp stay in the registers of the threads that need them as unit fluxes,
 // the new delp divides the other three in the same workgroup (apply_pt_delp_fluxes / adjust_w_and_qcon, d_sw.py:148-201,
 // 331-350: no k_finish_scalars pass, no flux-form intermediates), results go to buffers of their own (the neighbouring tiles
-// still read the old values).  Other tilings, ord 8 and the float32 build take k_fvtp2d.hip.
+// still read the old values).  Other tilings and ord 8 take k_fvtp2d.hip.
 #pragma once
 #include <type_traits>
 
@@ -85,9 +85,9 @@ struct FvtLds {
   double sqc[9];  // the tile's corner block with corners copied in x (corner tiles)
 };
 
-// The layout of the scalar-phase kernel since round 6: the damping's iterate and its two metric planes have places of their own
-// instead of aliasing the sweeps' arrays.  del6_v / del6_u are then staged ONCE per tile (they used to be fetched again at the start
-// of every pass -- 0.35 GB of a launch's 1.06 GB, L2 misses every time: 50 us of 420, experiment x25 of round 5), and the iterate
+// The layout of the scalar-phase kernel (the resident layout): the damping's iterate and its two metric planes have places of their
+// own instead of aliasing the sweeps' arrays as in FvtLds.  del6_v / del6_u are then staged ONCE per tile (fetched again at the start
+// of every pass they were 0.35 GB of a launch's 1.06 GB, L2 misses every time: 50 us of 420, experiment x25 of round 5), and the iterate
 // lives until the outer sweep has formed its fluxes, so the damping's face values are read from it where they are used (no
 // per-thread store of them: 20 KB) and the damping's passes share barrier intervals with the sweeps, which read q only.
 struct FvtLdsRes {
@@ -126,18 +126,7 @@ __device__ __forceinline__ int fvt_launder(int x) {
 }
 #define FVT_LAUNDER(x) fvt_launder(x)
 #endif
-// ... of the scalar-phase kernel (two workgroups per CU: 80 KB each): the transport's arrays, the mass on the tile and one cell
-// around it (the mass-weighted damping of q_con and pt reads it at the faces, the cell update at the cells), and ten doubles
-// per thread that would otherwise be spilled registers (the damping fluxes of the thread's faces while the inner sweeps run)
-constexpr int MP = TI + 3;  // pitch of the mass tile
-struct FvtLdsScalars {
-  FvtLds t;
-  double mass[(TJ + 2) * MP];
-  double priv[2 * NF][256];
-  double newmass[TI * TJ];  // (512-thread form: the new delp of the tile's cells; the 256-thread form keeps it in registers)
-  double heat[TI * TJ];     // (512-thread form with the winds: w's heating term, heat_diss -> the dissipative heating at the end)
-};
-static_assert(2 * sizeof(FvtLdsScalars) <= 160 * 1024, "two workgroups per CU");
+constexpr int MP = TI + 3;  // pitch of the scalar-phase kernel's mass tile (FvtLdsScalars)
 
 #define LDG(p, off) (*(const real*)((const char*)(p) + (off)))
 #define STG(p, off) (*(real*)((char*)(p) + (off)))
@@ -257,19 +246,19 @@ struct FvtPiecesT {
     }
   }
 };
-using FvtPieces = FvtPiecesT<256>;
 
 // The stages of one tile.  EX / EY: the tile holds a west or east / south or north edge of the cubed-sphere tile (block-uniform).
-// NT = 256: every thread owns one y-run AND one x-run.  NT = 512 (the scalar-phase kernel): the first four waves own the x-runs,
-// the last four the y-runs -- half the persistent state per thread, twice the waves per SIMD.
+// LT = FvtLds (the single-scalar kernel), 256 threads: every thread owns one y-run AND one x-run.  LT = FvtLdsRes (the scalar-phase
+// kernel), 512 threads: the first four waves own the x-runs, the last four the y-runs -- half the persistent state per thread, twice
+// the waves per SIMD.
 // MT: the metric planes' pointers as the kernel holds them (a plain object, or read in place: common.h PACE_KERNARG)
-template <int MORD, bool EX, bool EY, int NT = 256, class LT = FvtLds, class MT = const FvMet>
+template <int MORD, bool EX, bool EY, class LT = FvtLds, class MT = const FvMet>
 struct FvtTile {
-  static constexpr bool RES = std::is_same<LT, FvtLdsRes>::value;  // the damping's planes have places of their own
+  static constexpr bool RES = std::is_same<LT, FvtLdsRes>::value;  // the damping's planes have places of their own, two thread roles
+  static_assert(RES || std::is_same<LT, FvtLds>::value, "one of the two layouts");
+  static constexpr int NT = RES ? 512 : 256;
   static constexpr bool RC = EX && EY;  // the footprint reaches a corner of the halo: the corner copies apply
-  static constexpr bool SPLIT = NT == 512;
-  static_assert(NT == 256 || NT == 512, "thread places of one or two roles");
-  static constexpr int DRC = SPLIT ? 3 : DN_RC;       // cells per column run of the damping
+  static constexpr int DRC = RES ? 3 : DN_RC;         // cells per column run of the damping
   static constexpr int DNR = (QH + DRC - 1) / DRC;   // runs per column
   static_assert(QW * DNR <= NT, "one column run per thread");
   static constexpr int NCU = (TI * TJ + NT - 1) / NT;  // cells per thread in the cell update
@@ -309,8 +298,8 @@ struct FvtTile {
     // which edges of the cubed-sphere tile this workgroup tile holds (one per axis at most: >= 2 tiles each way)
     west = EX && bx == 0, east = EX && !west;
     south = EY && by == 0, north = EY && !south;
-    const bool xrole = !SPLIT || tid < 256, yrole = !SPLIT || tid >= 256;  // (wave-uniform)
-    const int tr = SPLIT ? (tid & 255) : tid;                               // the thread's number within its role
+    const bool xrole = !RES || tid < 256, yrole = !RES || tid >= 256;  // (wave-uniform)
+    const int tr = RES ? (tid & 255) : tid;                             // the thread's number within its role
     y_on = yrole;
     if (tr < NYO) {
       yg = tr / TI;
@@ -736,66 +725,6 @@ struct FvtTile {
     __syncthreads();
   }
 
-  // The operands of the inner sweeps that do not depend on the scalar: the Courant numbers and area fluxes of the thread's five
-  // y- and five x-faces, the areas of its cells (pointers with the level applied).  The scalar-phase kernel loads them once.
-  struct SweepOperands {
-    double cx[NF], cy[NF], xf[NF], yf[NF], arx[C], ary[C];
-  };
-  __device__ __forceinline__ void load_sweep_operands(const real* __restrict__ crx, const real* __restrict__ cry,
-                                                      const real* __restrict__ xfx, const real* __restrict__ yfx, SweepOperands& o) const {
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      o.cy[f] = LDG(cry, yoff + (unsigned)(f * sj8));
-      o.yf[f] = LDG(yfx, yoff + (unsigned)(f * sj8));
-      o.cx[f] = LDG(crx, xoff + (unsigned)(f * RB));
-      o.xf[f] = LDG(xfx, xoff + (unsigned)(f * RB));
-    }
-#pragma unroll
-    for (int t = 0; t < C; ++t) {
-      o.ary[t] = LDG(m.area, yoff + (unsigned)(t * sj8));
-      o.arx[t] = LDG(m.area, xoff + (unsigned)(t * RB));
-    }
-  }
-  // stage I with the operands given.  Ends with a barrier.
-  template <bool DO_Y = true, bool DO_X = true>
-  __device__ __forceinline__ void inner_with(const SweepOperands& o, double* si_x, double* si_y) {
-    if (DO_Y && y_on) {
-      double Q[NF + 5];
-#pragma unroll
-      for (int u = 0; u < NF + 5; ++u) Q[u] = L.sq[ybase + u * P];
-      FvtSpacing sp;
-      if (EY) sp = fvt_spacing(m.dya, (unsigned)((ilo + ycol) * RB), sj8, g.js, g.je, south && yg == 0, north && yg == GYN - 1);
-      fvt_run<MORD, EY>(Q, o.cy, south && yg == 0, north && yg == GYN - 1, sp, si_y);
-#pragma unroll
-      for (int t = 0; t < C; ++t)
-        L.u.s.sqi[ybase + t * P] = (Q[t + 3] * o.ary[t] + o.yf[t] * si_y[t] - o.yf[t + 1] * si_y[t + 1]) / (o.ary[t] + o.yf[t] - o.yf[t + 1]);
-    }
-    if (DO_X && x_on) {
-      double Q[NF + 5];
-#pragma unroll
-      for (int u = 0; u < NF + 5; ++u) Q[u] = L.sq[xbase + u];
-      if (RC) {  // halo rows of a corner tile: the three corner columns hold the x-direction copies
-        const bool halo_row = south ? xrow < 3 : xrow >= TJ + 3;
-        const int b = south ? xrow : xrow - (TJ + 3);
-        if (halo_row && west && xg == 0) {
-#pragma unroll
-          for (int a = 0; a < 3; ++a) Q[a] = L.sqc[b * 3 + a];
-        }
-        if (halo_row && east && xg == GXN - 1) {
-#pragma unroll
-          for (int a = 0; a < 3; ++a) Q[NF + 2 + a] = L.sqc[b * 3 + a];
-        }
-      }
-      FvtSpacing sp;
-      if (EX) sp = fvt_spacing(m.dxa, (unsigned)((jlo + xrow) * sj8), RB, g.is, g.ie, west && xg == 0, east && xg == GXN - 1);
-      fvt_run<MORD, EX>(Q, o.cx, west && xg == 0, east && xg == GXN - 1, sp, si_x);
-#pragma unroll
-      for (int t = 0; t < C; ++t)
-        L.u.s.sqj[xrow * PJ + C * xg + t] = (Q[t + 3] * o.arx[t] + o.xf[t] * si_x[t] - o.xf[t + 1] * si_x[t + 1]) / (o.arx[t] + o.xf[t] - o.xf[t + 1]);
-    }
-    __syncthreads();
-  }
-
   // ---- stage II: the outer sweeps (fvtp2d.py:80-119): the mean advected value through the run's five faces, 0.5 * (outer + inner).
   // x: on q_i, tile row xr (= footprint row xrow), faces i0 + C*xg + f.  Only for x_outer threads.
   __device__ __forceinline__ void outer_x(const double* cx, const double* si_x, double* mean) const {
@@ -1073,7 +1002,7 @@ struct FvtScalars {
   double dt;
   real *dw, *heat_s, *diss_est;
   const real* ke_bg;
-  // ---- the winds (512-thread form only; winds != 0): the vorticity transport, u / v from it and the kinetic energy, the
+  // ---- the winds (winds != 0): the vorticity transport, u / v from it and the kinetic energy, the
   // dissipative heating and the final winds as a fifth pass of the tile (d_sw.py:406-477,493-608) ----
   const real *u, *v;         // the winds before d_sw (read at the tile's faces only)
   real *u_out, *v_out;       // the winds after it: buffers of their own (a tile reads the old wind on the face its neighbour writes)
@@ -1086,7 +1015,7 @@ struct FvtScalars {
   int ke_plus_vort;          // ke is the plain kinetic energy: ke + vort_b (the divergence damping's increment) is formed here
 };
 // The one argument of k_fvt_scalars (common.h PACE_KERNARG): 60 pointers and the scalars are more than the scalar register file
-// holds, so the resident form reads S where it uses it instead of carrying the table through the kernel in spilled registers.
+// holds, so the kernel reads S where it uses it instead of carrying the table through the kernel in spilled registers.
 struct FvtScalarsArgs {
   Geo g;
   FvMet m;
@@ -1096,593 +1025,34 @@ static_assert(std::is_trivially_copyable<FvtScalarsArgs>::value && alignof(FvtSc
                   offsetof(FvtScalarsArgs, S) % 32 == 0 && sizeof(FvtScalarsArgs) == offsetof(FvtScalarsArgs, S) + sizeof(FvtScalars),
               "one kernel argument at offset 0 of the argument segment, the passes' records on 32-byte boundaries");
 
-
-template <int MORD, bool EX, bool EY>
-__device__ __forceinline__ void fvt_scalars_tile(FvtLdsScalars& LS, const Geo& g, const FvMet& m, const FvtScalars& S, int bx, int by, int k) {
-  // Register budget: 256 VGPRs = TWO workgroups per CU.  What a thread needs again for the next scalar and nobody else needs --
-  // the Courant numbers and area fluxes of its runs, the mass fluxes through its faces, the new mass of its cells -- stays in
-  // registers; the mass itself sits in the LDS.  At the 128 registers of four workgroups per CU the same kernel spilled (every
-  // spilled register is 8 MB of scratch traffic per launch on a kernel that runs at the speed of its L2 misses: 2.1 GB per
-  // launch against 1.7 GB for the four separate launches), and re-reading the operands per scalar misses the L2 every time (an
-  // XCD's 4 MB turn over in ~6 us, a scalar takes ~20).  Measured: DESIGN.md section 4.
-  FvtLds& L = LS.t;
-  FvtTile<MORD, EX, EY> T(L, g, m, bx, by, k, (int)threadIdx.x);
-  const int tid = T.tid;
-  const long kb = (long)k * g.sk;
-  const int sj8 = T.sj8;
-  const bool w_on = S.damp_w[k] > 1e-5;
-  double cx[NF], cy[NF], xf[NF], yf[NF];  // Courant numbers and area fluxes of the thread's faces
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    cy[f] = LDG(S.cry + kb, T.yoff + (unsigned)(f * sj8));
-    yf[f] = LDG(S.yfx + kb, T.yoff + (unsigned)(f * sj8));
-    cx[f] = LDG(S.crx + kb, T.xoff + (unsigned)(f * RB));
-    xf[f] = LDG(S.xfx + kb, T.xoff + (unsigned)(f * RB));
-  }
-  double mfx[NF], mfy[NF];  // the mass fluxes through them (unit fluxes of w, q_con, pt)
-  double dn[NEC];           // the new mass of the thread's cells
-
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {  // delp, w, q_con, pt
-    FVT_STAMP(4 * s);
-    const real* const q = S.pass[s].q + kb;
-    real* const qout = S.pass[s].qout + kb;
-    const bool is_delp = s == 0, is_w = s == 1;
-    const bool mass_weighted = s >= 2;  // DelnFlux with mass (q_con, pt); delp: plain DelnFlux; w: DelnFluxNoSG -> heat_diss
-    const double damp = S.pass[s].fac[k];
-    T.load_footprint(q, qout);
-    T.stage_damping_metrics();
-    __syncthreads();
-    FVT_STAMP(4 * s + 1);
-    if (is_delp) {  // the mass on the tile and one cell around it, from the footprint while it is there
-      for (int e = tid; e < (TJ + 2) * (TI + 2); e += 256) {
-        const int r = e / (TI + 2), c = e - r * (TI + 2);
-        LS.mass[r * MP + c] = L.sq[(r + 2) * P + c + 2];
-      }
-    }
-    {
-      double dvx[NF], dvy[NF];
-      const auto D = T.damp(mass_weighted ? 1.0 : damp, S.pass[s].nord[k] > 0.0, S.pass[s].nmax);
-      if (is_w) {
-        T.heat_diss(D, S.dw + kb, S.heat_s + kb, S.diss_est + kb, w_on, S.ke_bg[k] * fabs(S.dt));
-      } else {
-        T.damping_faces(D, dvx, dvy);
-        if (T.x_outer) {
-#pragma unroll
-          for (int f = 0; f < NF; ++f) LS.priv[f][tid] = dvx[f];
-        }
-        if (T.y_outer) {
-#pragma unroll
-          for (int f = 0; f < NF; ++f) LS.priv[NF + f][tid] = dvy[f];
-        }
-      }
-      __syncthreads();  // the sweeps overwrite the damping planes
-    }
-    FVT_STAMP(4 * s + 2);
-    double si_y[NF], si_x[NF];
-    {
-      typename FvtTile<MORD, EX, EY>::SweepOperands O;
-#pragma unroll
-      for (int f = 0; f < NF; ++f) O.cx[f] = cx[f], O.cy[f] = cy[f], O.xf[f] = xf[f], O.yf[f] = yf[f];
-#pragma unroll
-      for (int t = 0; t < C; ++t) {
-        O.ary[t] = LDG(m.area, T.yoff + (unsigned)(t * sj8));
-        O.arx[t] = LDG(m.area, T.xoff + (unsigned)(t * RB));
-      }
-      T.inner_with(O, si_x, si_y);
-    }
-    FVT_STAMP(4 * s + 3);
-    if (T.x_outer) {
-      double v[NF];
-      T.outer_x(cx, si_x, v);
-      FVT_FENCE();
-      if (is_delp) {
-        double wa[NF];
-        const bool last = T.east && T.xg == GXN - 1;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) wa[f] = LDG(S.mfx + kb, T.xoff + (unsigned)(f * RB));
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          mfx[f] = v[f] * xf[f] + LS.priv[f][tid];
-          v[f] = mfx[f];
-          if (f < C || last) STG(S.mfx + kb, T.xoff + (unsigned)(f * RB)) = wa[f] + mfx[f];  // flux_capacitor (d_sw.py:33-60)
-        }
-      } else {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          v[f] = v[f] * mfx[f];
-          if (mass_weighted) {
-            const double* ms = LS.mass + (T.xr + 1) * MP + C * T.xg + f;  // the cells on either side of the face
-            v[f] = v[f] + 0.5 * damp * (ms[0] + ms[1]) * LS.priv[f][tid];
-          }
-        }
-      }
-      T.put_ax(v);
-    }
-    FVT_FENCE();
-    if (T.y_outer) {
-      double v[NF];
-      T.outer_y(cy, si_y, v);
-      FVT_FENCE();
-      if (is_delp) {
-        double wa[NF];
-        const bool last = T.north && T.yg == GYN - 1;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) wa[f] = LDG(S.mfy + kb, T.yoff + (unsigned)(f * sj8));
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          mfy[f] = v[f] * yf[f] + LS.priv[NF + f][tid];
-          v[f] = mfy[f];
-          if (f < C || last) STG(S.mfy + kb, T.yoff + (unsigned)(f * sj8)) = wa[f] + mfy[f];
-        }
-      } else {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          v[f] = v[f] * mfy[f];
-          if (mass_weighted) {
-            const double* ms = LS.mass + (C * T.yg + f) * MP + T.ycol - 2;
-            v[f] = v[f] + 0.5 * damp * (ms[0] + ms[MP]) * LS.priv[NF + f][tid];
-          }
-        }
-      }
-      T.put_ay(v);
-    }
-    __syncthreads();
-    {
-      int jj[NEC], ii[NEC];
-      unsigned c2[NEC];
-      double ra[NEC], dwv[NEC];
-      T.cell_places(jj, ii, c2);
-#pragma unroll
-      for (int t = 0; t < NEC; ++t) ra[t] = LDG(m.rarea, c2[t]);
-      if (is_w && w_on) {
-#pragma unroll
-        for (int t = 0; t < NEC; ++t) dwv[t] = LDG(S.dw + kb, c2[t]);
-      }
-#pragma unroll
-      for (int t = 0; t < NEC; ++t) {
-        const double am = LS.mass[(jj[t] + 1) * MP + ii[t] + 1];
-        double val;
-        if (is_delp) {
-          // the new delp (apply_pt_delp_fluxes, d_sw.py:148-201)
-          dn[t] = am + T.flux_increment(jj[t], ii[t], ra[t]);
-          val = dn[t];
-        } else {
-          val = T.flux_form(jj[t], ii[t], am, ra[t]) / dn[t];
-          if (is_w && w_on) val = val + dwv[t];  // adjust_w_and_qcon (d_sw.py:331-350)
-        }
-        STG(qout, c2[t]) = val;
-      }
-    }
-    if (s < 3) __syncthreads();  // (the cell update read sq / ax / ay)
-  }
-  FVT_STAMP(16);
-}
-
-
-// ---- the same with 512 threads: x-runs and y-runs owned by different waves ----------------------------------------------------
-// Round 5.  The 256-thread form holds the Courant numbers, area fluxes and mass fluxes of ten faces per thread (its y-run and
-// its x-run): ~250 VGPRs = two waves per SIMD, and the counters showed the issue slots two thirds empty (one wave issues at most
-// every ~8 cycles; 54 % of wave time in memory / LDS / barrier waits with nothing else to issue).  Here waves 0-3 own the x-runs
-// (inner sweep in x on q, outer sweep in x on q_i) and waves 4-7 the y-runs, so a thread carries the operands of FIVE faces:
-// <= 128 VGPRs = four waves per SIMD at the same LDS per workgroup, the same tile and the same arithmetic (same bits).  The
-// stages every thread shares (footprint, damping passes, cell update) are spread over twice the threads.
-template <int MORD, bool EX, bool EY>
-__device__ __forceinline__ void fvt_scalars_tile_split(FvtLdsScalars& LS, const Geo& g, const FvMet& m, const FvtScalars& S, int bx, int by, int k) {
-  constexpr int NT = 512;
-  using Tile = FvtTile<MORD, EX, EY, NT>;
-  constexpr int NCU = Tile::NCU;
-  FvtLds& L = LS.t;
-  const int tid = (int)threadIdx.x;
-  const bool xrole = tid < 256;  // wave-uniform
-  const long kb = (long)k * g.sk;
-  const int sj8 = g.sj * RB;
-  const bool w_on = S.damp_w[k] > 1e-5;
-  double* const priv = &LS.priv[0][0];  // [NF][NT]: the damping fluxes of the thread's faces while the sweeps run
-  double c[NF], af[NF], mf[NF];    // Courant numbers, area fluxes, mass fluxes (unit fluxes of w, q_con, pt) of the run's faces
-  D2 fp[5][Tile::Pieces::NP];      // the thread's pieces of the footprints: every load of the tile's inputs is in flight at once
-  {
-    Tile T(L, g, m, bx, by, k, tid);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) T.fetch_footprint(S.pass[s].q + kb, fp[s]);
-    if (S.winds) T.fetch_footprint(S.pass[4].q + kb, fp[4]);
-    const unsigned roff = xrole ? T.xoff : T.yoff;
-  if (xrole) {
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      c[f] = LDG(S.crx + kb, roff + (unsigned)(f * RB));
-      af[f] = LDG(S.xfx + kb, roff + (unsigned)(f * RB));
-    }
-  } else {
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      c[f] = LDG(S.cry + kb, roff + (unsigned)(f * sj8));
-      af[f] = LDG(S.yfx + kb, roff + (unsigned)(f * sj8));
-    }
-  }
-  }
-
-  // one pass of the tile: s = 0 .. 4 = delp, w, q_con, pt, (the winds:) relative vorticity -- a compile-time constant
-  auto pass = [&](auto s_) {
-    constexpr int s = decltype(s_)::value;
-    constexpr bool is_delp = s == 0, is_w = s == 1, is_vort = s == 4;
-    FVT_STAMP(4 * s);
-    const real* const q = S.pass[s].q + kb;
-    real* const qout = is_vort ? nullptr : S.pass[is_vort ? 0 : s].qout + kb;
-    // DelnFlux with mass (q_con, pt); delp: plain DelnFlux; w: DelnFluxNoSG -> heat_diss; vorticity: DelnFluxNoSG -> the winds
-    const bool mass_weighted = s == 2 || s == 3;
-    const double damp = S.pass[s].fac[k];
-    // the thread's places, derived again for every scalar: only the operands above live through the whole kernel
-    Tile T(L, g, m, bx, by, k, FVT_LAUNDER(tid));
-    // the thread's run: its five faces in memory (first face, step), whether it takes part in the inner / the outer sweep
-    const unsigned roff = xrole ? T.xoff : T.yoff;
-    const bool run_outer = xrole ? T.x_outer : T.y_outer;
-    const bool lane_lo = xrole ? (T.west && T.xg == 0) : (T.south && T.yg == 0);
-    const bool lane_hi = xrole ? (T.east && T.xg == GXN - 1) : (T.north && T.yg == GYN - 1);
-    const bool last_face = lane_hi;  // the run that stores the face past the end of the tile (ie + 1 / je + 1)
-    // the one-sided forms' spacings (edge tiles), loaded by the runs that hold the edge where a sweep needs them
-    auto spacing = [&]() {
-      FvtSpacing sp;
-      if (EX && xrole) sp = fvt_spacing(m.dxa, (unsigned)((T.jlo + T.xrow) * sj8), RB, g.is, g.ie, lane_lo, lane_hi);
-      if (EY && !xrole) sp = fvt_spacing(m.dya, (unsigned)((T.ilo + T.ycol) * RB), sj8, g.js, g.je, lane_lo, lane_hi);
-      return sp;
-    };
-    T.stage_damping_planes();  // (its loads first: the metric planes are cache hits, the footprint may still be on its way)
-    T.load_damping_rarea();
-    T.place_footprint(q, fp[s], qout);
-    // the winds: the kinetic energy and the damped vorticity at the tile's (TI + 1) x (TJ + 1) B-grid points, on their way now,
-    // into the LDS after the inner sweeps (where q's footprint and the mass tile are dead)
-    constexpr int BW = TI + 1, NBP = (BW * (TJ + 1) + NT - 1) / NT;
-    double bke[NBP], bvb[NBP];
-    if (is_vort) {
-#pragma unroll
-      for (int t = 0; t < NBP; ++t) {
-        int e = tid + NT * t;
-        if (e >= BW * (TJ + 1)) e = BW * (TJ + 1) - 1;
-        const int r = e / BW, cc = e - r * BW;
-        const unsigned o = (unsigned)((T.j0 + r) * sj8 + (T.i0 + cc) * RB);
-        bke[t] = LDG(S.ke + kb, o);
-        bvb[t] = LDG(S.vort_b + kb, o);
-      }
-    }
-    FVT_ARRIVE(4 * s);
-    __syncthreads();
-    FVT_STAMP(4 * s + 1);
-    if (is_delp) {  // the mass on the tile and one cell around it, from the footprint while it is there
-      for (int e = tid; e < (TJ + 2) * (TI + 2); e += NT) {
-        const int r = e / (TI + 2), cc = e - r * (TI + 2);
-        LS.mass[r * MP + cc] = L.sq[(r + 2) * P + cc + 2];
-      }
-    }
-    {
-      const auto D = T.damp(mass_weighted ? 1.0 : damp, S.pass[s].nord[k] > 0.0, S.pass[s].nmax);
-      if (is_w) {
-        // (w has no face values: priv is free for dw; with the winds its heating term stays in the LDS as well)
-        T.heat_diss(D, S.dw + kb, S.heat_s + kb, S.diss_est + kb, w_on, S.ke_bg[k] * fabs(S.dt), priv, S.winds ? LS.heat : nullptr);
-      } else if (run_outer) {
-        if (xrole) {
-#pragma unroll
-          for (int f = 0; f < NF; ++f)
-            priv[f * NT + tid] = Tile::face(D, T.sdv[T.xbase + f + 3], D.last[T.xbase + f + 2], D.last[T.xbase + f + 3]);
-        } else {
-#pragma unroll
-          for (int f = 0; f < NF; ++f)
-            priv[f * NT + tid] = Tile::face(D, T.sdu[T.ybase + (f + 3) * P], D.last[T.ybase + (f + 2) * P], D.last[T.ybase + (f + 3) * P]);
-        }
-      }
-      FVT_ARRIVE(4 * s + 1);
-      __syncthreads();  // the sweeps overwrite the damping planes
-    }
-    if (is_vort) T.add_2d(S.fC);  // the damped scalar was the relative vorticity, the transported one is the absolute (d_sw.py:389-402)
-    FVT_STAMP(4 * s + 2);
-    // stage I: the inner sweep of the thread's run on q, and the field advected along it (fvtp2d.py:34-77).  The inner fluxes of
-    // the runs that take part in the outer sweep wait in ax / ay, each run using the places of the C faces it opens (the places
-    // its final fluxes go to; the face it shares with the next run is that run's place) and a register for the last one,
-    // instead of ten registers across the barrier.
-    double si_last = 0.0;
-    double* const slot = xrole ? L.u.s.ax + T.xr * PJ + C * T.xg : L.u.s.ay + (C * T.yg) * TI + T.ycol - 3;  // of the run's first face
-    constexpr int XS = 1, YS = TI;  // from face to face in ax / ay
-    if (xrole) {
-      if (T.x_on) {
-        double Q[NF + 5], ar[C];
-#pragma unroll
-        for (int u = 0; u < NF + 5; ++u) Q[u] = L.sq[T.xbase + u];
-        if (Tile::RC) {  // halo rows of a corner tile: the three corner columns hold the x-direction copies
-          const bool halo_row = T.south ? T.xrow < 3 : T.xrow >= TJ + 3;
-          const int b = T.south ? T.xrow : T.xrow - (TJ + 3);
-          if (halo_row && T.west && T.xg == 0) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) Q[a] = L.sqc[b * 3 + a];
-          }
-          if (halo_row && T.east && T.xg == GXN - 1) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) Q[NF + 2 + a] = L.sqc[b * 3 + a];
-          }
-        }
-        double si[NF];
-        fvt_run<MORD, EX>(Q, c, lane_lo, lane_hi, spacing(), si);
-        FVT_FENCE();
-#pragma unroll
-        for (int t = 0; t < C; ++t) ar[t] = LDG(m.area, roff + (unsigned)(t * RB));
-        if (T.x_outer) {
-#pragma unroll
-          for (int f = 0; f < C; ++f) slot[f * XS] = si[f];
-          si_last = si[C];
-        }
-#pragma unroll
-        for (int t = 0; t < C; ++t)
-          L.u.s.sqj[T.xrow * PJ + C * T.xg + t] = (Q[t + 3] * ar[t] + af[t] * si[t] - af[t + 1] * si[t + 1]) / (ar[t] + af[t] - af[t + 1]);
-      }
-    } else {
-      if (T.y_on) {
-        double Q[NF + 5], ar[C];
-#pragma unroll
-        for (int u = 0; u < NF + 5; ++u) Q[u] = L.sq[T.ybase + u * P];
-        double si[NF];
-        fvt_run<MORD, EY>(Q, c, lane_lo, lane_hi, spacing(), si);
-        FVT_FENCE();
-#pragma unroll
-        for (int t = 0; t < C; ++t) ar[t] = LDG(m.area, roff + (unsigned)(t * sj8));
-        if (T.y_outer) {
-#pragma unroll
-          for (int f = 0; f < C; ++f) slot[f * YS] = si[f];
-          si_last = si[C];
-        }
-#pragma unroll
-        for (int t = 0; t < C; ++t)
-          L.u.s.sqi[T.ybase + t * P] = (Q[t + 3] * ar[t] + af[t] * si[t] - af[t + 1] * si[t + 1]) / (ar[t] + af[t] - af[t + 1]);
-      }
-    }
-    FVT_ARRIVE(4 * s + 2);
-    __syncthreads();
-    FVT_STAMP(4 * s + 3);
-    double* const tke = L.sq;     // the winds: kinetic energy / damped vorticity at the tile's B-grid points, pitch BW
-    double* const tvb = LS.mass;
-    if (is_vort) {
-#pragma unroll
-      for (int t = 0; t < NBP; ++t) {
-        const int e = tid + NT * t;
-        if (e < BW * (TJ + 1)) tke[e] = S.ke_plus_vort ? bke[t] + bvb[t] : bke[t], tvb[e] = bvb[t];
-      }
-    }
-    // stage II: the outer sweep on the field advected across the run (fvtp2d.py:80-119), the fluxes through the run's faces
-    double v[NF];
-    double wind[NF];  // the winds: the old wind on the run's faces, on its way while the sweep runs
-    if (is_vort && run_outer) {
-      if (xrole) {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) wind[f] = LDG(S.v + kb, roff + (unsigned)(f * RB));
-      } else {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) wind[f] = LDG(S.u + kb, roff + (unsigned)(f * sj8));
-      }
-    }
-    if (run_outer) {
-      {
-        double Q[NF + 5], out[NF];
-        if (xrole) {
-#pragma unroll
-          for (int u = 0; u < NF + 5; ++u) Q[u] = L.u.s.sqi[T.xr * P + C * T.xg + u];
-          fvt_run<MORD, EX>(Q, c, lane_lo, lane_hi, spacing(), out);
-        } else {
-#pragma unroll
-          for (int u = 0; u < NF + 5; ++u) Q[u] = L.u.s.sqj[(C * T.yg + u) * PJ + T.ycol - 3];
-          fvt_run<MORD, EY>(Q, c, lane_lo, lane_hi, spacing(), out);
-        }
-        if (xrole) {
-#pragma unroll
-          for (int f = 0; f < C; ++f) v[f] = 0.5 * (out[f] + slot[f * XS]);
-        } else {
-#pragma unroll
-          for (int f = 0; f < C; ++f) v[f] = 0.5 * (out[f] + slot[f * YS]);
-        }
-        v[C] = 0.5 * (out[C] + si_last);
-      }
-      FVT_FENCE();
-      if (is_vort) {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) v[f] = v[f] * af[f];  // (the unit fluxes of the vorticity are the area fluxes)
-      } else if (is_delp) {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          mf[f] = v[f] * af[f] + priv[f * NT + tid];
-          v[f] = mf[f];
-        }
-        // flux_capacitor (d_sw.py:33-60): mfx += fx, mfy += fy, each face by the run that opens it.  (As load - add - store the
-        // accumulators' loads sat between the sweep and the stores with a memory latency to wait for: 7.6 k cycles for delp's
-        // last stage against 4.5 k for pt's.)
-        if (xrole) {
-#pragma unroll
-          for (int f = 0; f < NF; ++f)
-            if (f < C || last_face) fvt_accumulate((real*)((char*)(S.mfx + kb) + roff + (unsigned)(f * RB)), mf[f]);
-        } else {
-#pragma unroll
-          for (int f = 0; f < NF; ++f)
-            if (f < C || last_face) fvt_accumulate((real*)((char*)(S.mfy + kb) + roff + (unsigned)(f * sj8)), mf[f]);
-        }
-      } else {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          v[f] = v[f] * mf[f];
-          if (mass_weighted) {  // the cells on either side of the face
-            const double* ms = xrole ? LS.mass + (T.xr + 1) * MP + C * T.xg + f : LS.mass + (C * T.yg + f) * MP + T.ycol - 2;
-            const double m1 = xrole ? ms[1] : ms[MP];
-            v[f] = v[f] + 0.5 * damp * (ms[0] + m1) * priv[f * NT + tid];
-          }
-        }
-      }
-      // a face's flux is put down by the run that opens it; the last face of the row / column by its last run
-      if (is_vort) {
-        // (the winds take the fluxes from the registers below)
-      } else if (xrole) {
-#pragma unroll
-        for (int f = 0; f < C; ++f) slot[f * XS] = v[f];
-        if (T.xg == GXN - 1) slot[C * XS] = v[C];
-      } else {
-#pragma unroll
-        for (int f = 0; f < C; ++f) slot[f * YS] = v[f];
-        if (T.yg == GYN - 1) slot[C * YS] = v[C];
-      }
-    }
-    __syncthreads();
-    if (is_vort) {
-      // ---- the winds.  On a face of the tile: u_and_v_from_ke (d_sw.py:406-477) with the vorticity flux through it, the
-      // vorticity-damping increment (vort_differencing :353-380, the damping flux from priv), the final wind (update_u_and_v
-      // :582-608) and the face's terms of heat_source_from_vorticity_damping (:493-577: ubt, fy / vbt, fx); then, per cell, the
-      // damping term from its four faces and the heating.  The face terms travel through the LDS arrays the sweeps are done
-      // with: vbt -> ax, fx -> sqj (rows x TI + 1 faces), ubt -> ay, fy -> sqi (TJ + 1 faces x columns).
-      const bool upd = S.damp_vt[k] > 1e-5;
-      const double dck = S.d_con_k[k];
-      const bool don = dck > 1e-5;
-      double* const avbt = L.u.s.ax;
-      double* const afx = L.u.s.sqj;
-      double* const aubt = L.u.s.ay;
-      double* const afy = L.u.s.sqi;
-      if (run_outer) {
-        if (xrole) {  // x-faces: v-points (i0 + C * xg + f, j0 + xr)
-          double dyv[NF], rdyv[NF];
-#pragma unroll
-          for (int f = 0; f < NF; ++f) {
-            dyv[f] = LDG(m.dy, roff + (unsigned)(f * RB));
-            rdyv[f] = LDG(S.rdy, roff + (unsigned)(f * RB));
-          }
-#pragma unroll
-          for (int f = 0; f < NF; ++f) {
-            const int b = T.xr * BW + C * T.xg + f;
-            const double vmid = wind[f] * dyv[f] + tke[b] - tke[b + BW] - v[f];  // v_from_ke (d_sw.py:423-436)
-            const double ut2 = priv[f * NT + tid];
-            const double vyd = don ? tvb[b] - tvb[b + BW] : 0.0;
-            const double vbt = (vyd - ut2) * rdyv[f];
-            const double fxh = vmid * rdyv[f];
-            if (f < C || last_face) STG(S.v_out + kb, roff + (unsigned)(f * RB)) = upd ? vmid - ut2 : vmid;
-            if (f < C || T.xg == GXN - 1) avbt[T.xr * PJ + C * T.xg + f] = vbt, afx[T.xr * PJ + C * T.xg + f] = fxh;
-          }
-        } else {  // y-faces: u-points (i0 + ycol - 3, j0 + C * yg + f)
-          double dxv[NF], rdxv[NF];
-#pragma unroll
-          for (int f = 0; f < NF; ++f) {
-            dxv[f] = LDG(m.dx, roff + (unsigned)(f * sj8));
-            rdxv[f] = LDG(S.rdx, roff + (unsigned)(f * sj8));
-          }
-#pragma unroll
-          for (int f = 0; f < NF; ++f) {
-            const int b = (C * T.yg + f) * BW + T.ycol - 3;
-            const double umid = wind[f] * dxv[f] + tke[b] - tke[b + 1] + v[f];  // u_from_ke (d_sw.py:406-420)
-            const double vt2 = priv[f * NT + tid];
-            const double vxd = don ? tvb[b] - tvb[b + 1] : 0.0;
-            const double ubt = (vxd + vt2) * rdxv[f];
-            const double fyh = umid * rdxv[f];
-            if (f < C || last_face) STG(S.u_out + kb, roff + (unsigned)(f * sj8)) = upd ? umid + vt2 : umid;
-            if (f < C || T.yg == GYN - 1) aubt[(C * T.yg + f) * TI + T.ycol - 3] = ubt, afy[(C * T.yg + f) * TI + T.ycol - 3] = fyh;
-          }
-        }
-      }
-      __syncthreads();
-      {
-        int jj[NCU], ii[NCU];
-        unsigned c2[NCU];
-        T.cell_places(jj, ii, c2);
-        const bool any = S.d_con > 1e-5 || S.do_skeb;
-#pragma unroll
-        for (int t = 0; t < NCU; ++t) {
-          if (NCU * NT > TI * TJ && tid + NT * t >= TI * TJ) continue;  // (no cell of its own: the spare lanes would add twice)
-          const double heat_s = LS.heat[jj[t] * TI + ii[t]];
-          if (don || S.do_skeb) {
-            const int ey = jj[t] * TI + ii[t], ex = jj[t] * PJ + ii[t];
-            const double ubt0 = aubt[ey], ubtj = aubt[ey + TI], fy0 = afy[ey], fyj = afy[ey + TI];
-            const double vbt0 = avbt[ex], vbti = avbt[ex + 1], fx0 = afx[ex], fxi = afx[ex + 1];
-            const double gy0 = fy0 * ubt0, gyj = fyj * ubtj, gx0 = fx0 * vbt0, gxi = fxi * vbti;
-            const double u2 = fy0 + fyj, du2 = ubt0 + ubtj, v2 = fx0 + fxi, dv2 = vbt0 + vbti;
-            const double dampterm = LDG(S.rsin2, c2[t]) * 0.25 *
-                                    ((ubt0 * ubt0 + ubtj * ubtj + vbt0 * vbt0 + vbti * vbti) + 2.0 * (gy0 + gyj + gx0 + gxi) -
-                                     LDG(S.cosa_s, c2[t]) * (u2 * dv2 + v2 * du2 + du2 * dv2));
-            const double hs = LS.newmass[jj[t] * TI + ii[t]] * (heat_s - dck * dampterm);
-            if (any) {
-              fvt_accumulate((real*)((char*)(S.heat_source + kb) + c2[t]), hs);
-              if (S.do_skeb) STG(S.diss_est + kb, c2[t]) = LDG(S.diss_est + kb, c2[t]) - dampterm;
-            }
-          } else if (any) {
-            fvt_accumulate((real*)((char*)(S.heat_source + kb) + c2[t]), heat_s);
-          }
-        }
-      }
-      if ((EX || EY) && S.copy_wind_halo) {
-        // the output buffers of the winds get the halo the inputs have (the caller swaps the buffers): this tile's share of the
-        // storage outside the faces the kernel writes -- u: [is, ie] x [js, je + 1], v: [is, ie + 1] x [js, je]
-        const int xa = T.west ? 0 : T.i0, xb = T.east ? g.ni : T.i0 + TI, ya = T.south ? 0 : T.j0, yb = T.north ? g.nj : T.j0 + TJ;
-        const int bw = xb - xa, nbox = bw * (yb - ya);
-        for (int e = tid; e < nbox; e += NT) {
-          const int r = e / bw, i = xa + (e - r * bw), j = ya + r;
-          const unsigned o = (unsigned)(j * sj8 + i * RB);
-          const bool in_i = i >= g.is && i <= g.ie, in_j = j >= g.js && j <= g.je;
-          if (!(in_i && (in_j || j == g.je + 1))) STG(S.u_out + kb, o) = LDG(S.u + kb, o);
-          if (!((in_i || i == g.ie + 1) && in_j)) STG(S.v_out + kb, o) = LDG(S.v + kb, o);
-        }
-      }
-      return;
-    }
-    {
-      int jj[NCU], ii[NCU];
-      unsigned c2[NCU];
-      double ra[NCU], dwv[NCU];
-      T.cell_places(jj, ii, c2);
-#pragma unroll
-      for (int t = 0; t < NCU; ++t) ra[t] = LDG(m.rarea, c2[t]);
-      if (is_w && w_on) {
-#pragma unroll
-        for (int t = 0; t < NCU; ++t) dwv[t] = priv[jj[t] * TI + ii[t]];
-      }
-#pragma unroll
-      for (int t = 0; t < NCU; ++t) {
-        const double am = LS.mass[(jj[t] + 1) * MP + ii[t] + 1];
-        double val;
-        if (is_delp) {
-          // the new delp (apply_pt_delp_fluxes, d_sw.py:148-201)
-          val = am + T.flux_increment(jj[t], ii[t], ra[t]);
-          LS.newmass[jj[t] * TI + ii[t]] = val;  // (read back by this same thread)
-        } else {
-          val = T.flux_form(jj[t], ii[t], am, ra[t]) / LS.newmass[jj[t] * TI + ii[t]];
-          if (is_w && w_on) val = val + dwv[t];  // adjust_w_and_qcon (d_sw.py:331-350)
-        }
-        STG(qout, c2[t]) = val;
-      }
-    }
-    FVT_ARRIVE(4 * s + 3);
-    if (s < 3 || S.winds) __syncthreads();  // (the cell update read sq / ax / ay)
-  };
-  pass(std::integral_constant<int, 0>{});
-  pass(std::integral_constant<int, 1>{});
-  pass(std::integral_constant<int, 2>{});
-  pass(std::integral_constant<int, 3>{});
-  if (S.winds) pass(std::integral_constant<int, 4>{});
-  FVT_STAMP(S.winds ? 20 : 16);
-}
-
-
-// ---- round 6: the 512-thread form on the resident layout (FvtLdsRes) --------------------------------------------------------------
-// What changes against fvt_scalars_tile_split (same stages, same expressions, same bits):
-//  * del6_v / del6_u are staged once per tile; the iterate has a plane of its own; no store of face values (see FvtLdsRes).
-//  * The barrier intervals of a pass -- each now holds a piece of the damping AND a piece of the transport, which read different
-//    arrays:   [footprint] | [damping pass 1: q -> iterate; inner sweep: q -> q_i / q_j] | [outer sweep -> registers; damping pass 2
-//    read] | [pass 2 written] | [face values from the iterate -> fluxes] | [cell update]      -- six barriers where there were eight,
-//    and none of them closes an interval of a dozen instructions.
+// ---- the tile of the scalar-phase kernel: 512 threads on the resident layout (FvtLdsRes); DESIGN.md section 4.2 -----------------------
+//  * Waves 0-3 own the x-runs (inner sweep in x on q, outer sweep in x on q_i), waves 4-7 the y-runs: a thread carries the Courant
+//    numbers, area fluxes and mass fluxes of FIVE faces through the kernel, <= 128 VGPRs = four waves per SIMD, two workgroups per CU.
+//    The stages every thread shares (footprint, damping passes, cell update) are spread over all 512.
+//  * del6_v / del6_u are staged once per tile; the iterate has a plane of its own; the damping's face values are read from it where
+//    they are used (see FvtLdsRes).
+//  * The barrier intervals of a pass -- each holds a piece of the damping AND a piece of the transport, which read different arrays:
+//    [footprint] | [damping pass 1: q -> iterate; inner sweep: q -> q_i / q_j] | [outer sweep -> registers; damping pass 2 read] |
+//    [pass 2 written] | [face values from the iterate -> fluxes] | [cell update]      -- six barriers, none of which closes an
+//    interval of a dozen instructions.
 //  * The new mass and w's heating term of a thread's cells stay in its registers (the thread that forms them is the thread that
-//    uses them; the footprint pieces prefetched at kernel start have been released by then): 12 KB of LDS less.  73.6 KB per workgroup.
-struct FvtLdsScalarsRes {
+//    uses them; the footprint pieces prefetched at kernel start have been released by then).  73.6 KB of LDS per workgroup: the
+//    transport's and the damping's arrays, and the mass on the tile and one cell around it (the mass-weighted damping of q_con and
+//    pt reads it at the faces, the cell update at the cells).
+struct FvtLdsScalars {
   FvtLdsRes t;
-  double mass[(TJ + 2) * MP];  // the mass on the tile and one cell around it (the winds: the damped vorticity at the B-grid points)
+  double mass[(TJ + 2) * MP];  // (the winds: the damped vorticity at the B-grid points)
 };
-static_assert(2 * sizeof(FvtLdsScalarsRes) <= 160 * 1024, "two workgroups per CU");
+static_assert(2 * sizeof(FvtLdsScalars) <= 160 * 1024, "two workgroups per CU");
 
 // ST, MT: FvtScalars and FvMet as the kernel reads them -- in the kernel-argument segment (common.h PACE_KERNARG), or plain const
 // objects.  m serves the prologue (del6_u, del6_v, dxa, dya: used once, fetched there); mv is the by-value copy, of which the passes
 // keep area, rarea, dx and dy in registers.  (All of FvMet in place costs nothing in spills but makes the compiler duplicate a few
 // blocks of the edge tiles' arithmetic; all of it by value leaves two spilled SGPRs in two of the four builds.)
 template <int MORD, bool EX, bool EY, class MT, class ST>
-__device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const Geo& g, const FvMet& mv, MT& m, ST& S, int bx, int by, int k) {
-  constexpr int NT = 512;
-  using Tile = FvtTile<MORD, EX, EY, NT, FvtLdsRes>;
-  constexpr int NCU = Tile::NCU, DRC = Tile::DRC;
+__device__ __forceinline__ void fvt_scalars_tile(FvtLdsScalars& LS, const Geo& g, const FvMet& mv, MT& m, ST& S, int bx, int by, int k) {
+  using Tile = FvtTile<MORD, EX, EY, FvtLdsRes>;
+  constexpr int NT = Tile::NT, NCU = Tile::NCU, DRC = Tile::DRC;
   FvtLdsRes& L = LS.t;
   const int tid = (int)threadIdx.x;
   const bool xrole = tid < 256;  // wave-uniform
@@ -1692,19 +1062,10 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
   double c[NF], af[NF], mf[NF];    // Courant numbers, area fluxes, mass fluxes (unit fluxes of w, q_con, pt) of the run's faces
   double nm[NCU], heat_r[NCU];     // the new mass and w's heating term of the thread's cells
   D2 fp[5][Tile::Pieces::NP];      // the thread's pieces of the footprints: every load of the tile's inputs is in flight at once
-#ifndef FVT_RA_REGS
-#define FVT_RA_REGS 0  // 1: rarea of the thread's damping run loaded once per tile and kept in registers (0: once per pass)
-#endif
-  double ra_keep[DRC];
 #pragma unroll
   for (int t = 0; t < NCU; ++t) nm[t] = 1.0, heat_r[t] = 0.0;
   {
-    FvtTile<MORD, EX, EY, NT, FvtLdsRes, MT> T(L, g, m, bx, by, k, tid);
-    if (FVT_RA_REGS) {
-      T.load_damping_rarea();
-#pragma unroll
-      for (int t = 0; t < DRC; ++t) ra_keep[t] = T.dra[t];
-    }
+    FvtTile<MORD, EX, EY, FvtLdsRes, MT> T(L, g, m, bx, by, k, tid);
 #pragma unroll
     for (int s = 0; s < 4; ++s) T.fetch_footprint(S.pass[s].q + kb, fp[s]);
     if (S.winds) T.fetch_footprint(S.pass[4].q + kb, fp[4]);
@@ -1769,12 +1130,7 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
     };
 
     // ---- interval 0: the footprint
-    if (FVT_RA_REGS) {
-#pragma unroll
-      for (int t = 0; t < DRC; ++t) T.dra[t] = ra_keep[t];
-    } else {
-      T.load_damping_rarea();
-    }
+    T.load_damping_rarea();  // (once per pass: kept in registers through the tile it gained nothing)
     T.template place_footprint<true>(q, fp[s], qout);
     constexpr int BW = TI + 1, NBP = (BW * (TJ + 1) + NT - 1) / NT;
     double bke[NBP], bvb[NBP];  // the winds: kinetic energy and damped vorticity at the tile's B-grid points, on their way
@@ -1905,9 +1261,6 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
     // the winds: the old wind on the run's faces and the faces' grid spacings (dy, 1 / dy at the x-faces; dx, 1 / dx at the y-faces),
     // on their way while the sweep runs (at the top of the face stage they were a round trip to memory with nothing beside it)
     double wind[NF], dsp[NF], rdsp[NF];
-#ifndef FVT_HOIST_WIND
-#define FVT_HOIST_WIND 2  // the faces' spacings of the winds pass: 0 loaded where they are used, 1 before the outer sweep, 2 behind it
-#endif
     auto load_spacings = [&]() {
       if (xrole) {
 #pragma unroll
@@ -1925,7 +1278,6 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
 #pragma unroll
         for (int f = 0; f < NF; ++f) wind[f] = LDG(S.u + kb, roff + (unsigned)(f * sj8));
       }
-      if (FVT_HOIST_WIND == 1) load_spacings();
     }
     if (run_outer) {
       double Q[NF + 5], out[NF];
@@ -1953,7 +1305,7 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
       }
     }
     FVT_FENCE();
-    if (is_vort && run_outer && FVT_HOIST_WIND == 2) load_spacings();  // (behind the sweep: they travel under the damping's pass 2)
+    if (is_vort && run_outer) load_spacings();  // (behind the sweep: they travel under the damping's pass 2; in front of it they cost spills)
     double res2[DRC], fix2 = 0.0;
     if (iters >= 2) T.template deln_compute<false>(d0, res2, fix2);
     if (iters >= 2) {
@@ -2015,7 +1367,6 @@ __device__ __forceinline__ void fvt_scalars_tile_res(FvtLdsScalarsRes& LS, const
       double* const aubt = L.u.s.ay;
       double* const afy = L.u.s.sqi;
       if (run_outer) {
-        if (FVT_HOIST_WIND == 0) load_spacings();
         if (xrole) {  // x-faces: v-points (i0 + C * xg + f, j0 + xr)
 #pragma unroll
           for (int f = 0; f < NF; ++f) {

@@ -1732,8 +1732,9 @@ int dsw_prepare(const Geo& g, const pace_column_t* col, void* ws, hipStream_t st
 enum DswWindHalo { WIND_HALO_NOBODY, WIND_HALO_FLUX_PREP, WIND_HALO_OWN_LAUNCH, WIND_HALO_EDGE_TILES };
 // nmax_*: the column's highest damping orders.  kstart, nonzero_nord: the divergence damping's column is split at the first level with
 // nord > 0 (divergence_damping.py:307-331).  pingpong: the caller gave the four transported scalars outputs of their own
-// (pace_dsw_config_t).  lean_scalars: the fused scalar kernel (k_fvt.hip launch_dsw_scalars_lean) covers this tiling and these orders;
-// winds_in_scalars: ... and this call runs the winds as its fifth pass, the FUSED order of launch_d_sw.  skip_dead:
+// (pace_dsw_config_t).  lean_scalars: the fused scalar kernel (k_fvt.hip launch_dsw_scalars_lean) covers this tiling and these
+// transport orders (dsw_pingpong_supported); winds_in_scalars: ... and the column's damping orders, and this call runs the whole of
+// d_sw: the winds are that kernel's fifth pass, the FUSED order of launch_d_sw.  skip_dead:
 // PACE_DSW_SKIP_DEAD_OUTPUTS.  ke_by_consumer: `ke += damped vorticity` is left to the fused kernel.
 struct DswPlan {
   int nmax_v, nmax_w, nmax_t, kstart, nonzero_nord;
@@ -1742,13 +1743,11 @@ struct DswPlan {
 };
 
 // The scalars can have outputs of their own where ONE kernel transports them: the production tilings, one order for all transports.
+// There a whole-d_sw call also runs the winds as that kernel's fifth pass (then nothing of d_sw is left to overlap with what
+// follows it, and the winds can have outputs of their own): pace_d_sw_pingpong_supported and pace_d_sw_wind_outputs_supported both
+// answer this.
 bool dsw_pingpong_supported(const Geo& g, const pace_dsw_config_t* cfg) {
   return cfg->hord_dp == cfg->hord_vt && cfg->hord_dp == cfg->hord_tm && transport_lean_covers(g, cfg->hord_dp);
-}
-// whether a whole-d_sw call runs the winds as the fifth pass of the scalar-phase kernel (then nothing of d_sw is left to overlap
-// with what follows it, and the winds can have outputs of their own)
-bool dsw_winds_in_scalars(const Geo& g, const pace_dsw_config_t* cfg) {
-  return dsw_pingpong_supported(g, cfg) && dsw_scalars_take_winds();
 }
 static void dsw_max_orders(const Geo& g, const pace_column_t* col, DswPlan& p) {
   p.nmax_v = p.nmax_w = p.nmax_t = 0;
@@ -1758,12 +1757,11 @@ static void dsw_max_orders(const Geo& g, const pace_column_t* col, DswPlan& p) {
     p.nmax_t = std::max(p.nmax_t, (int)col->nord_t[k]);
   }
 }
-// the two queries above plus the condition on the column namelist they cannot see
+// the query above plus the condition on the column namelist it cannot see: 3 (the scalars' outputs and the winds') or 0
 int dsw_outputs_supported(const Geo& g, const pace_column_t* col, const pace_dsw_config_t* cfg) {
   DswPlan p;
   dsw_max_orders(g, col, p);
-  if (!dsw_fused_takes_orders(p.nmax_v, p.nmax_w, p.nmax_t) || !dsw_pingpong_supported(g, cfg)) return 0;
-  return dsw_winds_in_scalars(g, cfg) ? 3 : 1;
+  return dsw_fused_takes_orders(p.nmax_v, p.nmax_w, p.nmax_t) && dsw_pingpong_supported(g, cfg) ? 3 : 0;
 }
 
 // phases (bit mask): 1 = flux preparation (fxadv), 2 = transport of delp, w, q_con, pt (everything riem_solver3 /
@@ -1782,12 +1780,12 @@ static int dsw_plan(const Geo& g, const pace_column_t* col, const pace_dsw_confi
   p.kstart = 0, p.nonzero_nord = cfg->nord;
   for (int k = g.nk - 1; k >= 0; --k)  // (downwards: what stays is the FIRST level with nord > 0)
     if (col->nord[k] > 0) p.kstart = k, p.nonzero_nord = (int)col->nord[k];
-  // Where the scalar-phase kernel can take the winds (the production tilings, one order for all transports, the 512-thread form)
-  // and the call asks for scalars and winds together, the vorticity transport, the wind update and the dissipative heating are
-  // the FIFTH PASS of that kernel (fvt_core.h): k_fvt<.., 0, 0> and k_heat_source, and the fields between them, disappear.
+  // Where the scalar-phase kernel covers the call (the production tilings, one order for all transports) and the call asks for
+  // scalars and winds together, the vorticity transport, the wind update and the dissipative heating are the FIFTH PASS of that
+  // kernel (fvt_core.h): k_fvt<.., 0, 0> and k_heat_source, and the fields between them, disappear.
   // (16-byte rows of the relative vorticity: a condition on the workspace the caller handed over, known only here)
   const bool whole = ((phases & 2) && (phases & 4) && (phases & 8)) || (phases & 256);
-  p.winds_in_scalars = whole && dsw_winds_in_scalars(g, cfg) && dsw_fused_takes_orders(p.nmax_v, p.nmax_w, p.nmax_t) && ((uintptr_t)W.wk & 15) == 0;
+  p.winds_in_scalars = whole && p.lean_scalars && dsw_fused_takes_orders(p.nmax_v, p.nmax_w, p.nmax_t) && ((uintptr_t)W.wk & 15) == 0;
   if ((phases & 256) && !p.winds_in_scalars) return PACE_ERR_UNSUPPORTED;
   // (separate wind outputs exist in that form only; a call that runs neither the scalars nor the heating does not touch them)
   if (cfg->u_out != nullptr && !p.winds_in_scalars && (phases & (2 | 8))) return PACE_ERR_UNSUPPORTED;

@@ -35,55 +35,28 @@ __global__ void __launch_bounds__(256, FVT_WAVES) k_fvt(Geo g, FvMet m, const re
   else fvt_tile<MORD, DMODE, EPI, false, false>(L, g, m, q, crx, cry, xfx, yfx, fx, fy, xunit, yunit, dp, wg.bx, wg.by, wg.bz);
 }
 
-#ifndef FVT_SCALARS_NT
-#define FVT_SCALARS_NT 512  // threads per workgroup of the scalar-phase kernel: 512 = x-runs and y-runs in different waves
-#endif
-// two workgroups per CU either way (LDS: 78 KB each); 512 threads -> four waves per SIMD at <= 128 VGPRs, 256 -> two at <= 256.
-// (__launch_bounds__(512, 2) alone does not hold the compiler to 128 registers -- it took 134 once, which is ONE workgroup per
-// CU: 342 -> 447 us --, the waves-per-EU attribute does)
+// The scalar-phase kernel: 512 threads (x-runs and y-runs in different waves), two workgroups per CU (LDS: 78 KB each), four waves
+// per SIMD at <= 128 VGPRs.  (__launch_bounds__(512, 2) alone does not hold the compiler to 128 registers -- it took 134 once,
+// which is ONE workgroup per CU: 342 -> 447 us --, the waves-per-EU attribute does)
 #ifdef PACE_EMU
 #define FVT_SCALARS_ATTR
-#elif FVT_SCALARS_NT == 512
-#define FVT_SCALARS_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #else
-#define FVT_SCALARS_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
-#endif
-#ifndef FVT_RESIDENT
-#define FVT_RESIDENT 1  // the 512-thread form on the layout with the damping's planes resident (round 6; 0: round 5's, for A/B builds)
+#define FVT_SCALARS_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
 template <int MORD>
-__global__ void __launch_bounds__(FVT_SCALARS_NT) FVT_SCALARS_ATTR k_fvt_scalars(FvtScalarsArgs A_) {
-#if FVT_SCALARS_NT == 512 && FVT_RESIDENT
-  __shared__ FvtLdsScalarsRes L;
+__global__ void __launch_bounds__(512) FVT_SCALARS_ATTR k_fvt_scalars(FvtScalarsArgs A_) {
+  __shared__ FvtLdsScalars L;
   PACE_KERNARG(FvtScalarsArgs, A, A_);  // (the table is read where it is used: no SGPR spills)
   const Geo& g = A_.g;  // (twelve registers, used everywhere)
   auto& m = A.m;
   auto& S = A.S;
-#else
-  __shared__ FvtLdsScalars L;
-  const Geo& g = A_.g;
-  const FvMet& m = A_.m;
-  const FvtScalars& S = A_.S;
-#endif
   const FvTile wg = fv_tile_of_workgroup();
   const int gx = g.n / TI, gy = g.n / TJ;
   const bool ex = wg.bx == 0 || wg.bx == gx - 1, ey = wg.by == 0 || wg.by == gy - 1;
-#if FVT_SCALARS_NT == 512 && FVT_RESIDENT
-  if (ex && ey) fvt_scalars_tile_res<MORD, true, true>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
-  else if (ex) fvt_scalars_tile_res<MORD, true, false>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
-  else if (ey) fvt_scalars_tile_res<MORD, false, true>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
-  else fvt_scalars_tile_res<MORD, false, false>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
-#elif FVT_SCALARS_NT == 512
-  if (ex && ey) fvt_scalars_tile_split<MORD, true, true>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else if (ex) fvt_scalars_tile_split<MORD, true, false>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else if (ey) fvt_scalars_tile_split<MORD, false, true>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else fvt_scalars_tile_split<MORD, false, false>(L, g, m, S, wg.bx, wg.by, wg.bz);
-#else
-  if (ex && ey) fvt_scalars_tile<MORD, true, true>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else if (ex) fvt_scalars_tile<MORD, true, false>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else if (ey) fvt_scalars_tile<MORD, false, true>(L, g, m, S, wg.bx, wg.by, wg.bz);
-  else fvt_scalars_tile<MORD, false, false>(L, g, m, S, wg.bx, wg.by, wg.bz);
-#endif
+  if (ex && ey) fvt_scalars_tile<MORD, true, true>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
+  else if (ex) fvt_scalars_tile<MORD, true, false>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
+  else if (ey) fvt_scalars_tile<MORD, false, true>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
+  else fvt_scalars_tile<MORD, false, false>(L, g, A_.m, m, S, wg.bx, wg.by, wg.bz);
 }
 
 }  // namespace FVT_NS
@@ -142,21 +115,11 @@ int FVT_FN(launch_transport)(const Geo& g, const Met& m, const real* q, const re
 
 // The scalar phase of d_sw (delp, w, q_con, pt) in one launch; see fvt_core.h.  kc: the device column block of dsw_prepare
 // (kernels.h DswColumn).  outs[4] = delp, pt, w, q_con outputs, distinct from the inputs.  PACE_ERR_UNSUPPORTED if the geometry /
-// orders are not covered (the caller then runs the scalars one by one).
-// whether the scalar-phase kernel can take the winds as its fifth pass (the 512-thread form)
-bool FVT_FN(take_winds)() {
-#if FVT_AVAILABLE && FVT_SCALARS_NT == 512
-  return true;
-#else
-  return false;
-#endif
-}
-
+// orders are not covered (the caller then runs the scalars one by one).  winds: if given, the kernel runs them as its fifth pass.
 int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const DswFields& f, real* const* outs, real* dw, real* heat_s, const real* kc, int hord,
                            int nmax_v, int nmax_w, int nmax_t, hipStream_t st, const DswWinds* winds) {
 #if FVT_AVAILABLE
   if (!FVT_FN(covers)(g, hord) || !dsw_fused_takes_orders(nmax_v, nmax_w, nmax_t)) return PACE_ERR_UNSUPPORTED;
-  if (winds && !FVT_FN(take_winds)()) return PACE_ERR_UNSUPPORTED;
   const real* ins[4] = {f.delp, f.pt, f.w, f.q_con};
   for (int n = 0; n < 4; ++n)
     if (((uintptr_t)ins[n] & 15) != 0 || outs[n] == nullptr || outs[n] == ins[n]) return PACE_ERR_UNSUPPORTED;
@@ -185,8 +148,8 @@ int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const DswFields& f, real*
   }
   const dim3 grid(g.n / TI, g.n / TJ, g.nk);
   const FvtScalarsArgs A{g, fv_met(m), S};
-  if (hord == 5) hipLaunchKernelGGL(k_fvt_scalars<5>, grid, dim3(FVT_SCALARS_NT), 0, st, A);
-  else hipLaunchKernelGGL(k_fvt_scalars<6>, grid, dim3(FVT_SCALARS_NT), 0, st, A);
+  if (hord == 5) hipLaunchKernelGGL(k_fvt_scalars<5>, grid, dim3(512), 0, st, A);
+  else hipLaunchKernelGGL(k_fvt_scalars<6>, grid, dim3(512), 0, st, A);
   PACE_CHECK_LAUNCH();
   return PACE_OK;
 #else
@@ -197,7 +160,6 @@ int FVT_FN(launch_scalars)(const Geo& g, const Met& m, const DswFields& f, real*
 #if FVT_SHAPE == 32
 // ---- what the rest of the library calls: the 32 x 24 tile where it tiles the domain, else the 16 x 24 one (k_fvt16.hip) ----
 bool fvt16_covers(const Geo& g, int hord);
-bool fvt16_take_winds();
 int fvt16_launch_transport(const Geo& g, const Met& m, const real* q, const real* crx, const real* cry, const real* xfx, const real* yfx,
                            real* fx, real* fy, const real* xu, const real* yu, int hord, int nlev, int dmode, int epi, const FvDamp& dp,
                            hipStream_t st);
@@ -205,7 +167,6 @@ int fvt16_launch_scalars(const Geo& g, const Met& m, const DswFields& f, real* c
                          int nmax_v, int nmax_w, int nmax_t, hipStream_t st, const DswWinds* winds);
 
 bool transport_lean_covers(const Geo& g, int hord) { return fvt32_covers(g, hord) || fvt16_covers(g, hord); }
-bool dsw_scalars_take_winds() { return fvt32_take_winds(); }  // (both shapes are compiled from the same source with the same form)
 int launch_transport_lean(const Geo& g, const Met& m, const real* q, const real* crx, const real* cry, const real* xfx,
                           const real* yfx, real* fx, real* fy, const real* xu, const real* yu, int hord, int nlev, int dmode,
                           int epi, const FvDamp& dp, hipStream_t st) {

@@ -11,7 +11,6 @@
 #include "common.h"
 #include "kernels.h"
 bool fvt16_covers(const Geo&, int) { return false; }
-bool fvt16_take_winds() { return false; }
 int fvt16_launch_transport(const Geo&, const Met&, const real*, const real*, const real*, const real*, const real*, real*, real*, const real*,
                            const real*, int, int, int, int, const FvDamp&, hipStream_t) {
   return PACE_ERR_UNSUPPORTED;

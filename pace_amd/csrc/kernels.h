@@ -99,7 +99,6 @@ struct DswWinds {
   int ke_plus_vort;  // `ke` is the plain kinetic energy: the kernel adds the damped vorticity to it (divergence_damping.py:161-185)
   double d_con;
 };
-bool dsw_scalars_take_winds();
 // The device column block of d_sw: one array of nk + 1 per slot, uploaded by dsw_prepare, read by the launchers of k_dsw.hip and k_fvt.hip
 enum DswColumn {
   DSWC_NORD_V, DSWC_NORD_W, DSWC_NORD_T, DSWC_DAMP_VT, DSWC_DAMP_W, DSWC_DAMP_T, DSWC_D2_DIVG, DSWC_D_CON, DSWC_KE_BG, DSWC_FAC_VT, DSWC_FAC_T,
@@ -144,10 +143,10 @@ int launch_a2b_ord4_tiled(const Geo& g, const Met& m, const real* qin, real* qou
 int launch_a2b_ord4_batch(const Geo& g, const Met& m, const real* const* qin, real* const* qout, const int* k0, const int* k1,
                           int nfields, hipStream_t st);
 int64_t dsw_workspace_bytes(const Geo& g);
-// whether launch_d_sw can write the four transported scalars to separate buffers (pace_dsw_config_t::delp_out ...)
+// whether launch_d_sw can write the four transported scalars to separate buffers (pace_dsw_config_t::delp_out ...); where it can, a
+// whole-d_sw call runs the winds as the fifth pass of the same kernel, and they can have buffers of their own too (u_out, v_out)
 bool dsw_pingpong_supported(const Geo& g, const pace_dsw_config_t* cfg);
-bool dsw_winds_in_scalars(const Geo& g, const pace_dsw_config_t* cfg);
-// what launch_d_sw accepts with this column namelist (pace_d_sw_outputs_supported): 0, 1 = the scalars' outputs, 3 = the winds' too
+// what launch_d_sw accepts with this column namelist (pace_d_sw_outputs_supported): 0, or 3 = the scalars' outputs and the winds'
 int dsw_outputs_supported(const Geo& g, const pace_column_t* col, const pace_dsw_config_t* cfg);
 int dsw_prepare(const Geo& g, const pace_column_t* col, void* ws, hipStream_t st);
 int launch_d_sw(const Geo& g, const Met& m, const pace_column_t* col, const pace_dsw_config_t* cfg, void* ws, int phases,

@@ -128,6 +128,38 @@ def test_d_sw_outputs_supported_is_what_the_launcher_accepts(emu_lib):
     assert lib.cdll.pace_d_sw_pingpong_supported(C.byref(op3._geom), C.byref(op3._cfg)) == 1
 
 
+def test_d_sw_output_queries_answer_together_on_both_sides_of_covers(emu_lib):
+    """Where the fused scalar kernel covers the call it takes the winds too: the three queries answer 1 / 1 / 3 together or
+    0 / 0 / 0 together -- on the canonical tiling with one order for all transports, with two orders, and on the default emulation
+    library, whose 64 x 16 tile the lean kernels do not cover."""
+    import ctypes as C
+
+    from helpers import build_emu_canon
+    from pace_amd import _lib, synthetic
+    from pace_amd.fv3core import DGridShallowWaterLagrangianDynamicsConfig
+    from pace_amd.fv3core.stencils.d_sw import DGridShallowWaterLagrangianDynamics, get_column_namelist
+
+    n, nz = 24, 4
+    m = synthetic.tile_metrics(n, nz)
+
+    def answers(lib, **orders):
+        env = Env(lib, "cpu", m, n, nz)
+        cfg = DGridShallowWaterLagrangianDynamicsConfig()
+        op = DGridShallowWaterLagrangianDynamics(env.stencil_factory, env.qf, env.grid_data, env.damping, get_column_namelist(cfg, env.qf), False, False,
+                                                 cfg)
+        c = _lib.DswConfig.from_buffer_copy(op._cfg)
+        for k, v in orders.items():
+            setattr(c, k, v)
+        q = lib.cdll
+        return (q.pace_d_sw_pingpong_supported(C.byref(op._geom), C.byref(c)), q.pace_d_sw_wind_outputs_supported(C.byref(op._geom), C.byref(c)),
+                q.pace_d_sw_outputs_supported(C.byref(op._geom), C.byref(op._col), C.byref(c)))
+
+    canon = _lib.Library(build_emu_canon())
+    assert answers(canon) == (1, 1, 3)
+    assert answers(canon, hord_vt=5) == (0, 0, 0)  # (hord_dp = hord_tm = 6)
+    assert answers(emu_lib) == (0, 0, 0)
+
+
 def test_in_checkpoints_hold_the_state_before_the_call(emu_lib):
     """AcousticDynamics overlaps the u / v and uc / vc halo exchanges with the interior of c_sw's first pass and
     of d_sw's flux preparation; with a checkpointer attached those early starts are skipped, so that "C_SW-In" / "D_SW-In" hold

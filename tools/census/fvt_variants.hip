@@ -18,35 +18,12 @@ INST4(1, 0)
 INST4(0, 0)
 INST4(3, 1)
 INST4(2, 1)
-#endif
-#if FVT_AVAILABLE
-template <int MORD, bool EX, bool EY>
-__global__ void __launch_bounds__(256, 2) k_var_scalars(Geo g, FvMet m, FvtScalars S) {
-  __shared__ FvtLdsScalars L;
-  fvt_scalars_tile<MORD, EX, EY>(L, g, m, S, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-template __global__ void k_var_scalars<6, false, false>(Geo, FvMet, FvtScalars);
-template __global__ void k_var_scalars<6, true, false>(Geo, FvMet, FvtScalars);
-template __global__ void k_var_scalars<6, false, true>(Geo, FvMet, FvtScalars);
-template __global__ void k_var_scalars<6, true, true>(Geo, FvMet, FvtScalars);
-// the 512-thread form (x-runs and y-runs in different waves)
-template <int MORD, bool EX, bool EY>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) k_var_scalars_split(Geo g, FvMet m, FvtScalars S) {
-  __shared__ FvtLdsScalars L;
-  fvt_scalars_tile_split<MORD, EX, EY>(L, g, m, S, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-template __global__ void k_var_scalars_split<6, false, false>(Geo, FvMet, FvtScalars);
-template __global__ void k_var_scalars_split<6, true, false>(Geo, FvMet, FvtScalars);
-template __global__ void k_var_scalars_split<6, false, true>(Geo, FvMet, FvtScalars);
-template __global__ void k_var_scalars_split<6, true, true>(Geo, FvMet, FvtScalars);
-#endif
-#if FVT_AVAILABLE
-// the resident-layout form (round 6), its argument table read in place as k_fvt_scalars reads it (common.h PACE_KERNARG)
+// the scalar-phase tile, its argument table read in place as k_fvt_scalars reads it (common.h PACE_KERNARG)
 template <int MORD, bool EX, bool EY>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) k_var_scalars_res(FvtScalarsArgs A_) {
-  __shared__ FvtLdsScalarsRes L;
+  __shared__ FvtLdsScalars L;
   PACE_KERNARG(FvtScalarsArgs, A, A_);
-  fvt_scalars_tile_res<MORD, EX, EY>(L, A_.g, A_.m, A.m, A.S, blockIdx.x, blockIdx.y, blockIdx.z);
+  fvt_scalars_tile<MORD, EX, EY>(L, A_.g, A_.m, A.m, A.S, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 template __global__ void k_var_scalars_res<6, false, false>(FvtScalarsArgs);
 template __global__ void k_var_scalars_res<6, true, false>(FvtScalarsArgs);
