@@ -787,6 +787,47 @@ typedef struct {
 int pace_nudge(const pace_geom_t* geom, const pace_nudge_item_t* items, int nitems, double weight, double dt, int apply,
                void* stream);
 
+/* ---- Held-Suarez (1994) forcing (the Fortran FV3's Held_Suarez_Tend; the reference has none): Newtonian relaxation of the
+ * temperature toward a zonally symmetric equilibrium and Rayleigh friction of the low-level winds, as the tendencies that
+ * pace_update_dwinds_phys and pace_phys_thermo_pressure apply.  ONE launch, both storage types, no atomics, no workspace, no host synchronisation.  pe, ua,
+ * va, pt, u_dt, v_dt, pt_dt and teq share the storage geometry of geom; sin2lat and cos2lat are 2-D planes of the same row
+ * stride holding sin(lat)^2 and cos(lat)^2 of the cell centres.  For every cell of the compute domain -- origin (3, 3, 0), extent
+ * (n, n, nk) -- in double on the stored values (the float32 library widens first; exact), without FMA and without a reciprocal, in
+ * this order, with lean_log / lean_exp of csrc/lean_math.h (<= 0.55 ulp):
+ *   ps    = pe[i,j,nk]
+ *   pm    = 0.5 * (pe[i,j,k] + pe[i,j,k+1])
+ *   sigma = pm / ps
+ *   lp    = lean_log(pm / p0)
+ *   pk    = lean_exp(kappa * lp)
+ *   x     = ((t0 - delta_t_y * s2) - (delta_theta_z * lp) * c2) * pk
+ *   teq   = (x < t_strat) ? t_strat : x                       a NaN stays a NaN
+ *   hx    = (sigma - sigma_b) / (1.0 - sigma_b)               the denominator formed once, in double
+ *   h     = (hx < 0.0) ? 0.0 : hx                             a NaN stays a NaN
+ *   kv    = k_f * h
+ *   kt    = k_a + ((k_s - k_a) * h) * (c2 * c2)
+ *   u_dt  = -((kv * ua) / (1.0 + kv * dt))                    likewise v_dt from va
+ *   pt_dt = -(((kt * (pt - teq)) / (1.0 + kt * dt)) * heating_scale)
+ *   accumulate: out = (pace_real_t)((double)out + value); otherwise out = (pace_real_t)value; teq (if given) is always stored
+ * 1 / (1 + k dt) is backward Euler: applied over dt, friction and relaxation are contractions for every dt; dt = 0 gives the
+ * plain Held-Suarez rates.  The narrowing is a plain cast.  Nothing outside the compute domain's nk levels is written (not the
+ * halo, not level nk, not the row padding); nothing outside the compute domain is read (pe on nk + 1 levels there); the inputs
+ * are only read.
+ * PACE_ERR_ARG: a NULL geom or cfg or any NULL array but teq, struct_bytes != sizeof(pace_held_suarez_config_t), a dt that is
+ * negative or not finite, sigma_b outside [0, 1), p0 <= 0, a rate (k_f, k_a, k_s) that is negative or not finite, accumulate other
+ * than 0 / 1, an output pointer equal to an input pointer or to another output. */
+typedef struct {
+  int32_t struct_bytes;   /* sizeof(pace_held_suarez_config_t) */
+  int32_t accumulate;     /* 0: the three tendencies are stored; 1: added to what the arrays hold */
+  double dt;              /* seconds, >= 0: the implicit factor */
+  double p0, kappa, sigma_b, k_f, k_a, k_s;         /* 1e5 Pa, RDGAS / CP_AIR, 0.7, 1/86400, 1/(40*86400), 1/(4*86400)  [1/s] */
+  double delta_t_y, delta_theta_z, t0, t_strat;     /* 60 K, 10 K, 315 K, 200 K */
+  double heating_scale;   /* multiplies pt_dt: CV_AIR / CP_AIR where the tendency is applied as a constant-pressure heating */
+} pace_held_suarez_config_t;
+int pace_held_suarez(const pace_geom_t* geom, const pace_held_suarez_config_t* cfg, const pace_real_t* pe,
+                     const pace_real_t* ua, const pace_real_t* va, const pace_real_t* pt, const pace_real_t* sin2lat,
+                     const pace_real_t* cos2lat, pace_real_t* u_dt, pace_real_t* v_dt, pace_real_t* pt_dt, pace_real_t* teq,
+                     void* stream);
+
 /* ---- DynamicalCore (fv3core/pace/fv3core/stencils/fv_dynamics.py:92-624): the stencils it runs itself.  water: HOST
  * array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel.
  *   pace_fv_setup_pt  = moist_cv.fv_setup (moist_cv.py:175-234, moist_phys, nwat 6) + pt_to_potential_density_pt

@@ -206,6 +206,13 @@ class NudgeItem(C.Structure):  # include/pace_hip.h pace_nudge_item_t
                 ("timescale", C.c_double)]
 
 
+class HeldSuarezConfig(C.Structure):  # include/pace_hip.h pace_held_suarez_config_t
+    _fields_ = [("struct_bytes", C.c_int32), ("accumulate", C.c_int32), ("dt", C.c_double), ("p0", C.c_double),
+                ("kappa", C.c_double), ("sigma_b", C.c_double), ("k_f", C.c_double), ("k_a", C.c_double), ("k_s", C.c_double),
+                ("delta_t_y", C.c_double), ("delta_theta_z", C.c_double), ("t0", C.c_double), ("t_strat", C.c_double),
+                ("heating_scale", C.c_double)]
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -315,6 +322,7 @@ _PROTOS = {
     "pace_ckpt_validate_workspace_bytes": (C.c_int64, [_P(CkptItem), C.c_int]),
     "pace_ckpt_validate": (C.c_int, [_P(CkptItem), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_nudge": (C.c_int, [_P(Geom), _P(NudgeItem), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "pace_held_suarez": (C.c_int, [_P(Geom), _P(HeldSuarezConfig)] + [c_dp] * 10 + [C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

@@ -831,6 +831,29 @@ int pace_nudge(const pace_geom_t* geom, const pace_nudge_item_t* items, int nite
   return launch_nudge(make_geo(geom), items, nitems, weight, dt, apply, S(stream));
 }
 
+int pace_held_suarez(const pace_geom_t* geom, const pace_held_suarez_config_t* cfg, const real* pe, const real* ua, const real* va,
+                     const real* pt, const real* sin2lat, const real* cos2lat, real* u_dt, real* v_dt, real* pt_dt, real* teq,
+                     void* stream) {
+  NEED(geom && cfg && pe && ua && va && pt && sin2lat && cos2lat && u_dt && v_dt && pt_dt);
+  if (cfg->struct_bytes != (int32_t)sizeof(pace_held_suarez_config_t)) return PACE_ERR_ARG;
+  if (cfg->accumulate != 0 && cfg->accumulate != 1) return PACE_ERR_ARG;
+  if (!(std::isfinite(cfg->dt) && cfg->dt >= 0.0)) return PACE_ERR_ARG;
+  if (!(cfg->sigma_b >= 0.0 && cfg->sigma_b < 1.0) || !(cfg->p0 > 0.0)) return PACE_ERR_ARG;
+  const double rates[] = {cfg->k_f, cfg->k_a, cfg->k_s};
+  for (const double rate : rates)
+    if (!(std::isfinite(rate) && rate >= 0.0)) return PACE_ERR_ARG;
+  const real* const in[] = {pe, ua, va, pt, sin2lat, cos2lat};
+  const real* const out[] = {u_dt, v_dt, pt_dt, teq};
+  for (int a = 0; a < 4; ++a) {
+    if (!out[a]) continue;
+    for (const real* p : in)
+      if (out[a] == p) return PACE_ERR_ARG;
+    for (int b = 0; b < a; ++b)
+      if (out[a] == out[b]) return PACE_ERR_ARG;
+  }
+  return launch_held_suarez(make_geo(geom), *cfg, pe, ua, va, pt, sin2lat, cos2lat, u_dt, v_dt, pt_dt, teq, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

@@ -305,6 +305,10 @@ int launch_ckpt_thresholds(const pace_ckpt_item_t* items, int nitems, int n_tria
 int launch_ckpt_validate(const pace_ckpt_item_t* items, int nitems, void* workspace, double* out, hipStream_t st);
 // k_nudge.hip
 int launch_nudge(const Geo& g, const pace_nudge_item_t* items, int nitems, double weight, double dt, int apply, hipStream_t st);
+// k_heldsuarez.hip
+int launch_held_suarez(const Geo& g, const pace_held_suarez_config_t& cfg, const real* pe, const real* ua, const real* va,
+                       const real* pt, const real* sin2lat, const real* cos2lat, real* u_dt, real* v_dt, real* pt_dt, real* teq,
+                       hipStream_t st);
 // k_dycore.hip
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);

@@ -30,6 +30,7 @@ from .diagnostics import (  # noqa: F401
     ZSelect,
 )
 from .driver import Driver, run_cube_driver  # noqa: F401
+from .forcing import ForcingConfig  # noqa: F401
 from .nudging import Nudging, NudgingConfig  # noqa: F401
 from .safety_checks import SafetyChecker, VariableBounds  # noqa: F401
 from .state import DriverState, TendencyState  # noqa: F401

@@ -27,6 +27,9 @@ What is accepted, refused and ignored:
   nudging_config        (not in the reference) timescale_seconds, reference_paths, label, store_tendencies: the state relaxed
                         toward a sequence of Fortran restarts, interpolated in time, one launch per step (driver/nudging.py);
                         delp, delz, phis and anything that is no 3-D field of a Fortran restart: ValueError
+  forcing_config        (not in the reference) type held_suarez and its constants: the dry climate benchmark in place of the
+                        physics, one launch per step (driver/forcing.py); needs dycore_only true and disable_step_physics false,
+                        ValueError otherwise; apply_tendencies is then true
   performance_config    parsed and kept; nothing is written
   stencil_config.compilation_config.backend  kept as `requested_backend`; the backend is always hip:gfx950
 """
@@ -45,6 +48,7 @@ from ..fv3core import DynamicalCoreConfig
 from ..fv3core._config import strict_value
 from ..physics import PhysicsConfig, PhysicsState
 from .diagnostics import DiagnosticsConfig, ZSelect  # noqa: F401  (ZSelect: named here before diagnostics.py existed)
+from .forcing import ForcingConfig
 from .nudging import NudgingConfig
 from .state import DriverState, TendencyState
 
@@ -456,6 +460,7 @@ class DriverConfig:
         restart_config: the reference's own restart format: refused when it enables output
         fortran_restart_config: restart files in the Fortran model's format (not in the reference)
         nudging_config: relax the state toward a sequence of Fortran restarts (not in the reference); None: no nudging
+        forcing_config: a prescribed forcing in place of the physics, the Held-Suarez benchmark (not in the reference); None: none
     """
 
     stencil_config: StencilConfig
@@ -484,10 +489,16 @@ class DriverConfig:
     output_frequency: int = 1
     safety_check_frequency: Optional[int] = None
     nudging_config: Optional[NudgingConfig] = None
+    forcing_config: Optional[ForcingConfig] = None
 
     def __post_init__(self):
         if self.pair_debug:
             raise NotImplementedError("pair_debug: running two copies of the model that compare their data is not implemented")
+        if self.forcing_config is not None:  # it replaces the physics, and its tendencies are applied by the end-of-step update
+            if not self.dycore_only:
+                raise ValueError("forcing_config needs dycore_only: true (the forcing replaces the physics)")
+            if self.disable_step_physics:
+                raise ValueError("forcing_config needs disable_step_physics: false (the end-of-step update applies its tendencies)")
 
     @functools.cached_property
     def timestep(self) -> timedelta:
@@ -514,7 +525,7 @@ class DriverConfig:
 
     @functools.cached_property
     def apply_tendencies(self) -> bool:
-        return self.do_dry_convective_adjustment or not self.dycore_only
+        return self.do_dry_convective_adjustment or not self.dycore_only or self.forcing_config is not None
 
     def get_grid(self, communicator, quantity_factory):
         return self.grid_config.get_grid(quantity_factory=quantity_factory, communicator=communicator)
@@ -593,6 +604,8 @@ class DriverConfig:
                 kwargs[key] = kind.from_dict(kwargs[key])
         if kwargs.get("nudging_config") is not None:
             kwargs["nudging_config"] = NudgingConfig.from_dict(kwargs["nudging_config"])
+        if kwargs.get("forcing_config") is not None:
+            kwargs["forcing_config"] = ForcingConfig.from_dict(kwargs["forcing_config"])
         config = cls(**kwargs)
         config.source = source
         return config

@@ -8,7 +8,9 @@ A step is the reference's (driver.py:618-640): DynamicalCore.step_dynamics, Dyco
 each a class of its own that can also be called by hand; the driver only strings them together, advances the time and, every
 safety_check_frequency steps, checks the state (SafetyChecker: one launch pair and one transfer) and, every output_frequency
 steps, stores the diagnostics (MonitorDiagnostics: one pack launch and one transfer).  What the reference's constructor does
-for DaCe, build modes, its own restart format and the performance collector's files is not here.  With nudging_config the state is relaxed toward a sequence of
+for DaCe, build modes, its own restart format and the performance collector's files is not here.  With forcing_config the
+Held-Suarez forcing adds its tendencies between DycoreToPhysics and UpdateAtmosphereState (driver/forcing.py: one pace_held_suarez
+launch a step).  With nudging_config the state is relaxed toward a sequence of
 Fortran restarts after the end-of-step update (driver/nudging.py: one pace_nudge launch a step).  Restart files are written in
 the FORTRAN model's format (fortran_restart_config, write_fortran_restart: one pack launch and one transfer), which
 initialization.type fortran_restart reads back.
@@ -106,6 +108,10 @@ class Driver:
                 # Make sure those are set to None to raise any issues
                 self.dycore_to_physics = None
                 self.end_of_step_update = None
+            self.forcing = None
+            if config.forcing_config is not None:
+                self.forcing = config.forcing_config.forcing_factory(self.stencil_factory, self.quantity_factory,
+                                                                     self.state.grid_data)
             self.diagnostics = config.diagnostics_config.diagnostics_factory(communicator=communicator, lib=self.lib)
             self.nudging = None
             if config.nudging_config is not None:
@@ -179,6 +185,9 @@ class Driver:
                                            tendency_state=self.state.tendency_state, timestep=float(dt))
                     if not self.config.dycore_only:
                         self.physics(self.state.physics_state, timestep=float(dt))
+                    if self.forcing is not None:  # added to what the dry convective adjustment left in the tendencies
+                        self.forcing(self.state.dycore_state, self.state.tendency_state.u_dt, self.state.tendency_state.v_dt,
+                                     self.state.tendency_state.pt_dt, float(dt), accumulate=True)
                     self.end_of_step_update(dycore_state=self.state.dycore_state, phy_state=self.state.physics_state,
                                             u_dt=self.state.tendency_state.u_dt, v_dt=self.state.tendency_state.v_dt,
                                             pt_dt=self.state.tendency_state.pt_dt, dt=float(dt))

@@ -19,6 +19,9 @@
     python tools/kbench.py --only nudging           apply_nudging of u, v, pt, qvapor between two references with the tendencies
                                                     stored (one pace_nudge launch) against a torch restatement on the device,
                                                     the same way, with the launch alone and its bandwidth
+    python tools/kbench.py --only held_suarez       the Held-Suarez forcing of a tile of the baroclinic state, accumulated into the
+                                                    tendencies (one pace_held_suarez launch), against a torch restatement on
+                                                    the device, the same way, with the launch alone and its bandwidth
     python tools/kbench.py --only cube_gather       one output step (fourteen variables as float32 on the host) of six C96 and six
                                                     C192 tiles on this device: one pace_cube_gather launch and one transfer
                                                     against six pace_diag_pack passes, one per tile, with a transfer each
@@ -91,6 +94,9 @@ def main():
         return
     if args.only == "nudging":  # (its own fields)
         nudging_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "held_suarez":  # (its own fields)
+        held_suarez_bench(lib, n, nz, args.reps)
         return
     m = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(m, n, nz)
@@ -1268,6 +1274,88 @@ def nudging_bench(lib, n, nz, reps):
     events = times_hip_calibrate(hip, reps)
     launch = float(np.median(events))
     print(f"  the pace_nudge launch in device events: median {launch:.3f} ms (min {min(events):.3f}) = "
+          f"{moved / (launch * 1e-3) / 1e9:.0f} GB/s over the algorithmic bytes")
+
+
+def held_suarez_bench(lib, n, nz, reps):
+    """HeldSuarezForcing on tile 0 of the C<n> x <nz> baroclinic state with accumulate=True (ONE pace_held_suarez launch),
+    against the same expressions restated with torch on the device (views of the compute domains, the tendencies updated in
+    place).  Neither synchronises; both are timed with the host clock from an idle device to the end of a synchronisation added
+    for the measurement, alternating, medians; then the launch alone in device events, with its bandwidth over the algorithmic
+    bytes: pe on nz + 1 levels, ua, va, pt and the two planes read, the three tendencies read and written.  Before the timing
+    the two paths' tendencies from zero are compared at this size.  The state's u and v stand in for ua and va."""
+    import time
+    import types
+
+    from pace_amd.fv3core.initialization.baroclinic import baroclinic_state_six_tiles
+    from pace_amd.stencils import HeldSuarezForcing
+    from pace_amd.tile import setup_factories
+    from pace_amd.util import gridgen
+
+    tiles = gridgen.tiles(n, nz)
+    host = baroclinic_state_six_tiles(tiles, n, nz)[0]
+    _, qf, _, stencil_factory = setup_factories(lib, "cuda", n, nz)
+    forcing = HeldSuarezForcing(stencil_factory, qf, types.SimpleNamespace(lat_agrid=np.asarray(tiles[0]["lat_agrid"])))
+    dims = ["x", "y", "z"]
+    # (the initial state leaves ua, va undefined -- 1e35 -- until the first c2l_ord: the D-grid winds stand in for them)
+    source = {"pe": "pe", "ua": "u", "va": "v", "pt": "pt"}
+    state = types.SimpleNamespace(**{name: qf.from_array(host[source[name]], dims, "") for name in source})
+    tendencies = [qf.zeros(dims, "") for _ in range(3)]
+    restated_tendencies = [qf.zeros(dims, "") for _ in range(3)]
+    c, dt, scale = forcing.config, 225.0, forcing.heating_scale
+    cs = slice(3, 3 + n)
+    pe = state.pe.data[cs, cs]
+    ua, va, pt = (getattr(state, name).data[cs, cs, :nz] for name in ("ua", "va", "pt"))
+    s2, c2 = forcing.sin2lat.data[cs, cs, None].double(), forcing.cos2lat.data[cs, cs, None].double()
+    out = [q.data[cs, cs, :nz] for q in restated_tendencies]
+
+    def hip():
+        forcing(state, *tendencies, dt, accumulate=True)
+
+    def restated():
+        ps = pe[:, :, nz:nz + 1]
+        pm = 0.5 * (pe[:, :, :nz] + pe[:, :, 1:])
+        sigma = pm / ps
+        lp = torch.log(pm / c.p0)
+        pk = torch.exp(c.kappa * lp)
+        teq = torch.clamp(((c.t0 - c.delta_t_y * s2) - (c.delta_theta_z * lp) * c2) * pk, min=c.t_strat)
+        h = torch.clamp((sigma - c.sigma_b) / (1.0 - c.sigma_b), min=0.0)
+        kv = c.k_f * h
+        kt = c.k_a + ((c.k_s - c.k_a) * h) * (c2 * c2)
+        dv = 1.0 + kv * dt
+        out[0].sub_((kv * ua) / dv)
+        out[1].sub_((kv * va) / dv)
+        out[2].sub_(((kt * (pt - teq)) / (1.0 + kt * dt)) * scale)
+
+    paths = {"hip": hip, "torch": restated}
+    hip()
+    restated()
+    torch.cuda.synchronize()
+    for name, mine, theirs in zip(("u_dt", "v_dt", "pt_dt"), tendencies, restated_tendencies):
+        a, b = mine.data[cs, cs, :nz].double(), theirs.data[cs, cs, :nz].double()
+        print(f"  {name}: max |hip - torch| {float((a - b).abs().max()):.3e} at max |torch| {float(b.abs().max()):.3e}")
+    times = {k: [] for k in paths}
+    for fn in paths.values():
+        for _ in range(3):
+            fn()
+    for _ in range(reps):
+        for k, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    moved = (n * n * nz * 9 + n * n * (nz + 1) + 2 * n * n) * lib.real_bytes
+    print(f"held_suarez C{n} x {nz}, float{8 * lib.real_bytes} fields: tile 0 of the baroclinic state, accumulate on; "
+          f"{n * n * nz} cells, {moved / 1e6:.0f} MB algorithmic (pe, ua, va, pt, the tendencies read; the tendencies written); "
+          f"medians of {reps} alternating runs, ms")
+    for k in paths:
+        print(f"  {k:6s} {med[k]:9.3f} ms   (min {min(times[k]):.3f})")
+    print(f"  ratio torch / hip {med['torch'] / med['hip']:.2f}")
+    events = times_hip_calibrate(hip, reps)
+    launch = float(np.median(events))
+    print(f"  the pace_held_suarez launch in device events: median {launch:.3f} ms (min {min(events):.3f}) = "
           f"{moved / (launch * 1e-3) / 1e9:.0f} GB/s over the algorithmic bytes")
 
 
