@@ -86,10 +86,14 @@ def _remap_constraint(a1, a2, a3, a4, extm):
     return a1, n2, n3, n4
 
 
-def remap_profile(qs, a1, a2, a3, a4, delp, km, kord, iv, qmin=0.0, gam=None):
+def remap_profile(qs, a1, a2, a3, a4, delp, km, kord, iv, qmin=0.0, gam=None, store=None):
     """In place on a2, a3, a4 (and a1 where the reference writes it -- it never changes its value).  ``qs``: (ni, nj)
     bottom boundary value (used for iv == -2 only).  ``gam``: the RemapProfile object's persistent work field (level 0
-    keeps whatever an earlier call left when iv == -2; zeros for a fresh object)."""
+    keeps whatever an earlier call left when iv == -2; zeros for a fresh object).
+
+    ``store`` (None: the reference, nothing changes): a rounding applied where k_remap_interfaces (pace_amd/csrc/k_remap.hip)
+    puts a value into its workspace and reads it back -- the interface values and the multipliers of the forward sweep, which
+    the back substitution reads back while its own recurrence stays in a register, and the interface values it leaves."""
     kord = abs(kord)
     assert kord in (9, 10), "oracle restates kord 9 and 10"
     shp = a1.shape
@@ -118,8 +122,11 @@ def remap_profile(qs, a1, a2, a3, a4, delp, km, kord, iv, qmin=0.0, gam=None):
             g = grid_ratio[:, :, k]
             q[:, :, k] = (3.0 * (a1[:, :, k - 1] + a1[:, :, k]) - g * qs - q[:, :, k - 1]) / (2.0 + g + g - gam[:, :, k])
             q[:, :, km] = qs
+            carry = q[:, :, km - 1]
+            qr, gr_ = (q, gam) if store is None else (store(q), store(gam))
             for k in range(km - 2, -1, -1):
-                q[:, :, k] = q[:, :, k] - gam[:, :, k + 1] * q[:, :, k + 1]
+                carry = qr[:, :, k] - gr_[:, :, k + 1] * carry
+                q[:, :, k] = carry
         else:
             gr = delp[:, :, 1] / delp[:, :, 0]
             bet = gr * (gr + 0.5)
@@ -134,8 +141,13 @@ def remap_profile(qs, a1, a2, a3, a4, delp, km, kord, iv, qmin=0.0, gam=None):
             a_bot = 1.0 + d4 * (d4 + 1.5)
             q[:, :, km] = (2.0 * d4 * (d4 + 1.0) * a1[:, :, km - 1] + a1[:, :, km - 2] - a_bot * q[:, :, km - 1]) / (
                 d4 * (d4 + 0.5) - a_bot * gam[:, :, km - 1])
+            carry = q[:, :, km]
+            qr, gr_ = (q, gam) if store is None else (store(q), store(gam))
             for k in range(km - 1, -1, -1):
-                q[:, :, k] = q[:, :, k] - gam[:, :, k] * q[:, :, k + 1]
+                carry = qr[:, :, k] - gr_[:, :, k] * carry
+                q[:, :, k] = carry
+        if store is not None:
+            q = store(q)
 
     # ---- apply_constraints (remap_profile.py:267-337); k-domain = km levels
     tmp = np.zeros(shp)
@@ -303,9 +315,10 @@ def lagrangian_contributions(q, pe1, pe2, a1, a2, a3, a4, dp1, km):
             q[:, :, k] = np.where(inside, q_in, qsum / (p2b - p2a))
 
 
-def map_single(q1, pe1, pe2, km, kord, iv, qs=None, qmin=0.0, gam=None):
+def map_single(q1, pe1, pe2, km, kord, iv, qs=None, qmin=0.0, gam=None, store=None):
     """MapSingle.__call__ (map_single.py:154-200): q1 (ni, nj, >= km) is remapped in place from the layers bounded by pe1
-    to those bounded by pe2."""
+    to those bounded by pe2.  ``store`` (None: the reference): the rounding of everything the three kernels of k_remap.hip pass
+    to each other through their workspace (remap_profile's, and the coefficients a2, a3, a4)."""
     shp = q1.shape
     a1 = q1.copy()
     a2, a3, a4 = np.zeros(shp), np.zeros(shp), np.zeros(shp)
@@ -313,7 +326,9 @@ def map_single(q1, pe1, pe2, km, kord, iv, qs=None, qmin=0.0, gam=None):
     dp1[:, :, 0:km] = pe1[:, :, 1:km + 1] - pe1[:, :, 0:km]
     if qs is None:
         qs = np.zeros(shp[:2])
-    remap_profile(qs, a1, a2, a3, a4, dp1, km, kord, iv, qmin, gam)
+    remap_profile(qs, a1, a2, a3, a4, dp1, km, kord, iv, qmin, gam, store)
+    if store is not None:
+        a2, a3, a4 = store(a2), store(a3), store(a4)
     lagrangian_contributions(q1, pe1, pe2, a1, a2, a3, a4, dp1, km)
     return q1
 

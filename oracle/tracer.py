@@ -25,6 +25,41 @@ def flux_compute(g, cx, cy, xfx, yfx, nk):
     put(yfx, y, (g.is_ - 3, g.js), (n + 6, n + 1), k1=nk)
 
 
+def divide_fluxes(arrays, n_split, nk):
+    """divide_fluxes_by_n_substeps (tracer_2d_1l.py:80-106): origin_full, domain_full(add=(1, 1, 0)), the whole storage plane."""
+    frac = 1.0 / n_split
+    for a in arrays:
+        a[:, :, :nk] = a[:, :, :nk] * frac
+
+
+def _compute(g, nk):
+    return (slice(g.is_, g.ie + 1), slice(g.js, g.je + 1), slice(0, nk))
+
+
+def apply_mass_flux(g, dp1, mfx, mfy, dp2, nk):
+    """apply_mass_flux (tracer_2d_1l.py:115-135), compute domain."""
+    W = _compute(g, nk)
+    with np.errstate(all="ignore"):
+        d2 = dp1 + (mfx - sh(mfx, 1, 0) + mfy - sh(mfy, 0, 1)) * g.m2("rarea")
+    dp2[W] = d2[W]
+
+
+def apply_tracer_flux(g, q, dp1, fx, fy, dp2, nk):
+    """apply_tracer_flux (tracer_2d_1l.py:138-158), compute domain."""
+    W = _compute(g, nk)
+    with np.errstate(all="ignore"):
+        qn = (q * dp1 + (fx - sh(fx, 1, 0) + fy - sh(fy, 0, 1)) * g.m2("rarea")) / dp2
+    q[W] = qn[W]
+
+
+def swap_dp(g, dp1, dp2, nk):
+    """swap_dp (tracer_2d_1l.py:166-170), compute domain."""
+    W = _compute(g, nk)
+    tmp = dp1[W].copy()
+    dp1[W] = dp2[W]
+    dp2[W] = tmp
+
+
 def tracer_advection(grids, tracers, dp1, mfx, mfy, cx, cy, n, nk, hord=8):
     """TracerAdvection.__call__ (tracer_2d_1l.py:262-392).  tracers: dict name -> list of 6 arrays; the others: lists of 6
     arrays.  Everything is updated in place like the reference does."""
@@ -35,10 +70,8 @@ def tracer_advection(grids, tracers, dp1, mfx, mfy, cx, cy, n, nk, hord=8):
     for t in T:
         flux_compute(grids[t], cx[t], cy[t], xfx[t], yfx[t], nk)
     n_split = math.floor(1.0 + 2.0)
-    frac = 1.0 / n_split
     for t in T:
-        for a in (cx[t], xfx[t], mfx[t], cy[t], yfx[t], mfy[t]):
-            a[:, :, :nk] = a[:, :, :nk] * frac
+        divide_fluxes((cx[t], xfx[t], mfx[t], cy[t], yfx[t], mfy[t]), n_split, nk)
     for q in tracers.values():
         halo.halo_update(q, n, nk=nk)
     dp2 = [np.zeros(shape) for _ in T]
@@ -46,23 +79,13 @@ def tracer_advection(grids, tracers, dp1, mfx, mfy, cx, cy, n, nk, hord=8):
         last = it == n_split - 1
         for t in T:
             g = grids[t]
-            rarea = g.m2("rarea")
-            W = (slice(g.is_, g.ie + 1), slice(g.js, g.je + 1), slice(0, nk))
-            with np.errstate(all="ignore"):
-                d2 = dp1[t] + (mfx[t] - sh(mfx[t], 1, 0) + mfy[t] - sh(mfy[t], 0, 1)) * rarea
-            dp2[t][W] = d2[W]
+            apply_mass_flux(g, dp1[t], mfx[t], mfy[t], dp2[t], nk)
             for q in tracers.values():
                 fx, fy = np.zeros(shape), np.zeros(shape)
                 tr.fvtp2d(g, q[t], cx[t], cy[t], xfx[t], yfx[t], fx, fy, hord, x_mass_flux=mfx[t], y_mass_flux=mfy[t], nk=nk)
-                with np.errstate(all="ignore"):
-                    qn = (q[t] * dp1[t] + (fx - sh(fx, 1, 0) + fy - sh(fy, 0, 1)) * rarea) / dp2[t]
-                q[t][W] = qn[W]
+                apply_tracer_flux(g, q[t], dp1[t], fx, fy, dp2[t], nk)
         if not last:
             for q in tracers.values():
                 halo.halo_update(q, n, nk=nk)
             for t in T:
-                g = grids[t]
-                W = (slice(g.is_, g.ie + 1), slice(g.js, g.je + 1), slice(0, nk))
-                tmp = dp1[t][W].copy()
-                dp1[t][W] = dp2[t][W]
-                dp2[t][W] = tmp
+                swap_dp(grids[t], dp1[t], dp2[t], nk)

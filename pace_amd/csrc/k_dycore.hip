@@ -18,8 +18,9 @@ k_fv_setup_pt(Geo g, Water6 q, real* __restrict__ q_con, real* __restrict__ pkz,
               real* __restrict__ dp1) {
   CELL_IJK(g, 0, 0, 0);
   const double qv = q.qvapor[c];
-  const double ql = q.qliquid[c] + q.qrain[c];
-  const double qs = q.qice[c] + q.qsnow[c] + q.qgraupel[c];
+  // (the casts: with real = float the condensate sums would otherwise be formed in float)
+  const double ql = (double)q.qliquid[c] + (double)q.qrain[c];
+  const double qs = (double)q.qice[c] + (double)q.qsnow[c] + (double)q.qgraupel[c];
   const double gz = ql + qs;
   const double cvm = moist_cvm(qv + gz, qv, ql, qs);
   const double d1 = phys::ZVIR * qv;
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(256)
 k_omega_from_w(Geo g, const real* __restrict__ delp, const real* __restrict__ delz, const real* __restrict__ w,
                real* __restrict__ omga) {
   CELL_IJK(g, 0, 0, 0);
-  omga[c] = delp[c] / delz[c] * w[c];
+  omga[c] = (double)delp[c] / (double)delz[c] * (double)w[c];  // (the quotient in double, not rounded to real before it meets w)
 }
 
 __global__ void __launch_bounds__(256)
@@ -283,8 +284,9 @@ k_c2l(Geo g, Met m, const real* __restrict__ u, const real* __restrict__ v, cons
       ut = 2.0 * (u[c] * dx0 + u[c + sj] * dx1) / (dx0 + dx1);
     }
   } else {
-    ut = -0.125 * (u[c - sj] + u[c + 2 * sj]) + 1.125 * (u[c] + u[c + sj]);
-    vt = -0.125 * (v[c - 1] + v[c + 2]) + 1.125 * (v[c] + v[c + 1]);
+    // (the casts: the pair sums in double, not in real)
+    ut = -0.125 * ((double)u[c - sj] + (double)u[c + 2 * sj]) + 1.125 * ((double)u[c] + (double)u[c + sj]);
+    vt = -0.125 * ((double)v[c - 1] + (double)v[c + 2]) + 1.125 * ((double)v[c] + (double)v[c + 1]);
   }
   ua[c] = a11[c2] * ut + a12[c2] * vt;
   va[c] = a21[c2] * ut + a22[c2] * vt;

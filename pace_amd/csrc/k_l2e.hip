@@ -12,9 +12,10 @@
 
 // moist_cv_nwat6_fn + moist_cvm + set_cappa (moist_cv.py:16-46)
 __device__ __forceinline__ void moist_cv(const Water6Const& q, long c, double r_vir, double& gz, double& cappa) {
+  // (the casts: with real = float the condensate sums would otherwise be formed in float)
   const double qv = q.qvapor[c];
-  const double ql = q.qliquid[c] + q.qrain[c];
-  const double qs = q.qice[c] + q.qsnow[c] + q.qgraupel[c];
+  const double ql = (double)q.qliquid[c] + (double)q.qrain[c];
+  const double qs = (double)q.qice[c] + (double)q.qsnow[c] + (double)q.qgraupel[c];
   gz = ql + qs;
   cappa = moist_cappa(moist_cvm(qv + gz, qv, ql, qs), 1.0 + r_vir * qv);
 }
@@ -67,7 +68,7 @@ k_l2e_post(Geo g, Water6Const q, real* __restrict__ q_con, real* __restrict__ pk
   pe0[c] = peln[c];
   peln[c] = pn2[c];
   if (k == km) return;
-  const double dz = -delz[c] * delp[c];
+  const double dz = -(double)delz[c] * (double)delp[c];  // (in double: pkz below is formed from it, not from what delz stores)
   delz[c] = dz;
   double gz, cp;
   moist_cv(q, c, r_vir, gz, cp);
@@ -86,17 +87,17 @@ k_l2e_pressures(Geo g, const real* __restrict__ pe, const real* __restrict__ pe1
   const long nb = DIR == 0 ? -(long)g.sj : -1L;
   const long cb = c2 + (long)km * g.sk;
   if (DIR == 0) {
-    pe0[c] = (k == 0) ? pe[c] : 0.5 * (pe[c + nb] + pe1[c]);
+    pe0[c] = (k == 0) ? pe[c] : 0.5 * ((double)pe[c + nb] + (double)pe1[c]);  // (the casts: the pair sums in double)
     const double bkh = 0.5 * bk[k];
-    pe3[c] = ak[k] + bkh * (pe[cb + nb] + pe[cb]);
+    pe3[c] = ak[k] + bkh * ((double)pe[cb + nb] + (double)pe[cb]);
   } else {
     if (k == 0) {
       pe3[c] = ak[0];
       pe0[c] = pe[c];
     } else {
       const double bkh = 0.5 * bk[k];
-      pe0[c] = 0.5 * (pe[c + nb] + pe[c]);
-      pe3[c] = ak[k] + bkh * (pe[cb + nb] + pe[cb]);
+      pe0[c] = 0.5 * ((double)pe[c + nb] + (double)pe[c]);
+      pe3[c] = ak[k] + bkh * ((double)pe[cb + nb] + (double)pe[cb]);
     }
   }
 }
@@ -109,7 +110,7 @@ k_l2e_finish(Geo g, Water6Const q, real* __restrict__ pe, const real* __restrict
   if (k >= 1 && k < km) pe[c] = pe2[c];  // update_ua + copy_from_below: pe becomes the Eulerian interfaces
   if (last_step) {
     // moist_pt_last_step over km + 1 levels with dtmp = 0 (moist_cv.py:73-122, remapping.py:680-692)
-    const double gz = q.qliquid[c] + q.qrain[c] + q.qice[c] + q.qsnow[c] + q.qgraupel[c];
+    const double gz = (double)q.qliquid[c] + (double)q.qrain[c] + (double)q.qice[c] + (double)q.qsnow[c] + (double)q.qgraupel[c];
     pt[c] = (pt[c] + 0.0 * pkz[c]) / ((1.0 + r_vir * q.qvapor[c]) * (1.0 - gz));
   } else if (k < km) {
     pt[c] = pt[c] / pkz[c];

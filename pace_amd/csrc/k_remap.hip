@@ -102,7 +102,7 @@ k_remap_interfaces(Geo g, RemapWin w, RemapBatch B, const real* __restrict__ pe1
   real* __restrict__ gw = qi + field;  // (a2's storage: the back substitution's multipliers live there until the
                                          // coefficient kernel overwrites it)
 #define Q1(k) q1[c0 + (long)(k) * sk]
-#define DP(k) (pe1[c0 + (long)((k) + 1) * sk] - pe1[c0 + (long)(k) * sk])  // set_dp, map_single.py:14-18
+#define DP(k) ((double)pe1[c0 + (long)((k) + 1) * sk] - (double)pe1[c0 + (long)(k) * sk])  // set_dp, map_single.py:14-18 (double operands)
 #define QI(k) qi[c0 + (long)(k) * sk]
 #define GW(k) gw[c0 + (long)(k) * sk]
   // Loads are issued a chunk of RC levels ahead of the recurrences that consume them (the loop-carried values are two

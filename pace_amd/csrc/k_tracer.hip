@@ -42,7 +42,8 @@ k_apply_mass_flux(Geo g, Met m, const real* __restrict__ dp1, const real* __rest
   PATCH_IJK(g);
   if (i < g.is || i > g.ie || j < g.js || j > g.je) return;
   const long c = IDX3(g, i, j, k);
-  dp2[c] = dp1[c] + (mfx[c] - mfx[c + 1] + mfy[c] - mfy[c + g.sj]) * m.rarea[IDX2(g, i, j)];
+  // (the casts: with real = float the whole expression would otherwise be evaluated in float, every operand being a real load)
+  dp2[c] = (double)dp1[c] + ((double)mfx[c] - (double)mfx[c + 1] + (double)mfy[c] - (double)mfy[c + g.sj]) * (double)m.rarea[IDX2(g, i, j)];
 }
 
 // apply_tracer_flux (tracer_2d_1l.py:138-158), compute domain
@@ -52,7 +53,8 @@ k_apply_tracer_flux(Geo g, Met m, real* __restrict__ q, const real* __restrict__
   PATCH_IJK(g);
   if (i < g.is || i > g.ie || j < g.js || j > g.je) return;
   const long c = IDX3(g, i, j, k);
-  q[c] = (q[c] * dp1[c] + (fx[c] - fx[c + 1] + fy[c] - fy[c + g.sj]) * m.rarea[IDX2(g, i, j)]) / dp2[c];
+  q[c] = ((double)q[c] * (double)dp1[c] +
+          ((double)fx[c] - (double)fx[c + 1] + (double)fy[c] - (double)fy[c + g.sj]) * (double)m.rarea[IDX2(g, i, j)]) / (double)dp2[c];
 }
 
 // swap_dp (tracer_2d_1l.py:166-170), compute domain

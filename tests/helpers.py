@@ -358,17 +358,23 @@ def acoustic_errors(fix, out, n=12):
 # TracerAdvection on six tiles
 # ------------------------------------------------------------------------------------------------------------------
 def run_tracer_tile(comm, lib, device, fix, metrics, n):
+    nk = len(fix["k_sel"])
+    return run_tracer_arrays(comm, lib, device, {k: fix["in_" + k] for k in ("qvapor", "q2", "dp1", "mfxd", "mfyd", "cxd", "cyd")}, metrics, n, nk)
+
+
+def run_tracer_arrays(comm, lib, device, arrays, metrics, n, nk):
+    """TracerAdvection of the tracers qvapor and q2 on one rank's tile; arrays: qvapor, q2, dp1, mfxd, mfyd, cxd, cyd.  Returns
+    all seven as the call leaves them."""
     import torch
 
     from pace_amd.fv3core.stencils.fvtp2d import FiniteVolumeTransport
     from pace_amd.fv3core.stencils.tracer_2d_1l import TracerAdvection
     from pace_amd.util import CubedSphereCommunicator
 
-    nk = len(fix["k_sel"])
     env = Env(lib, device, metrics, n, nk)
     cube = CubedSphereCommunicator(comm, device=device, lib=lib)
-    tracers = {"qvapor": env.q3(fix["in_qvapor"]), "q2": env.q3(fix["in_q2"])}
-    f = {k: env.q3(fix["in_" + k]) for k in ("dp1", "mfxd", "mfyd", "cxd", "cyd")}
+    tracers = {"qvapor": env.q3(arrays["qvapor"]), "q2": env.q3(arrays["q2"])}
+    f = {k: env.q3(arrays[k]) for k in ("dp1", "mfxd", "mfyd", "cxd", "cyd")}
     transport = FiniteVolumeTransport(env.stencil_factory, env.qf, env.grid_data, env.damping, 0, 8)
     adv = TracerAdvection(env.stencil_factory, env.qf, transport, env.grid_data, cube, tracers)
     adv(tracers, f["dp1"], f["mfxd"], f["mfyd"], f["cxd"], f["cyd"])
@@ -377,6 +383,13 @@ def run_tracer_tile(comm, lib, device, fix, metrics, n):
     out = {k: v.numpy() for k, v in tracers.items()}
     out.update({k: v.numpy() for k, v in f.items()})
     return out
+
+
+def run_tracer_tiles(lib, device, metrics, arrays, n, nk):
+    """TracerAdvection on six tiles of any size joined by the cube communicator; metrics, arrays: one per tile."""
+    from pace_amd.util import run_tiles
+
+    return run_tiles(6, lambda comm: run_tracer_arrays(comm, lib, device, arrays[comm.Get_rank()], metrics[comm.Get_rank()], n, nk))
 
 
 def run_tracer_six_tiles(lib, device, n=12):
@@ -939,10 +952,15 @@ def run_d_sw_h5_fixture(env):
 # CubedToLatLon, the preamble kernels and the ord-8 transport at any size (tests/test_emu_kernels.py, tests/test_gpu_parity.py,
 # tests/test_vertical_edges.py)
 # ------------------------------------------------------------------------------------------------------------------
-def check_c2l_and_preamble(lib, device, n, nz, order):
+def check_c2l_and_preamble(lib, device, n, nz, order, storage=None):
     """pace_c2l_ord (order 2 or 4) and, with order 2, pace_fv_setup_pt and pace_omega_from_w on a synthetic C<n> tile with nz
     levels against oracle/dycore_parts.py: the wind transform bit for bit (order 2: compute + 1, order 4: compute), q_con,
-    cappa, dp1 and omga bit for bit, pkz and pt within 1e-14 (exp / log).  Returns {"pkz": error, "pt": error} (order 2)."""
+    cappa, dp1 and omga bit for bit, pkz and pt within 1e-14 (exp / log).  Returns {"pkz": error, "pt": error} (order 2).
+
+    storage="f32" (a float32-storage library): metrics and inputs are float32 values and the reference is float32(oracle) of them.
+    Every kernel here is one pass from its loads to its stores, so ua, va, q_con, cappa, dp1 and omga are in the exact class of
+    tests/test_f32_operators.py; pkz and pt (exp, log) in the last-place class: within 1 float32 ulp, at most 1e-4 of the
+    window different at all.  Returns {"pkz": number of elements that differ, "pt": the same}."""
     import ctypes as C
 
     from oracle import dycore_parts
@@ -951,14 +969,45 @@ def check_c2l_and_preamble(lib, device, n, nz, order):
     from pace_amd.fv3core.stencils.fillz import pointer_table
     from pace_amd.util.grid import geom_struct
 
+    assert storage in (None, "f32") and lib.real_bytes == (4 if storage else 8)
+
     def sync():
         if device != "cpu":
             import torch
 
             torch.cuda.synchronize()
 
+    def rnd(a):
+        """what a `real` field holds of `a`, as float64"""
+        from opchain import f32
+
+        return f32(a) if storage else a
+
+    def differ(name, got, ref):
+        """None if `got` is the reference as stored, bit for bit; else what differs"""
+        ref = ref.astype(np.float32) if storage else ref
+        if got.dtype == ref.dtype and np.array_equal(got, ref):
+            return None
+        worst = f", by up to {np.abs(got.view(np.int32).astype(np.int64) - ref.view(np.int32)).max()} ulp" if storage else ""
+        return f"{name}: {int((got != ref).sum())} of {ref.size} differ{worst}"
+
+    def last_place(name, got, ref):
+        if not storage:
+            e = compare(ref, got)
+            assert e < 1e-14, (name, e)
+            return e
+        r32 = ref.astype(np.float32)
+        for moved in (np.nextafter(ref, np.inf), np.nextafter(ref, -np.inf)):  # (the shape itself stays inside the class's share
+            assert (moved.astype(np.float32) != r32).sum() <= 1e-4 * ref.size, name  # under one float64 ulp of numpy's exp / log)
+        u = np.abs(got.view(np.int32).astype(np.int64) - r32.view(np.int32).astype(np.int64))  # (positive values: ordered like integers)
+        assert (got > 0).all() and (r32 > 0).all() and u.max() <= 1 and (u != 0).sum() <= 1e-4 * u.size, (name, int(u.max()), int((u != 0).sum()), u.size)
+        return int((u != 0).sum())
+
     metrics = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(metrics, n, nz)
+    if storage:
+        metrics = {k: (rnd(v) if isinstance(v, np.ndarray) and v.dtype.kind == "f" else v) for k, v in metrics.items()}
+        s = {k: (rnd(v) if isinstance(v, np.ndarray) and v.dtype.kind == "f" else v) for k, v in s.items()}
     env = Env(lib, device, metrics, n, nz)
     geom = geom_struct(env.qf)
     gd = env.grid_data
@@ -970,15 +1019,16 @@ def check_c2l_and_preamble(lib, device, n, nz, order):
     rua, rva = fn(s["u"], s["v"], metrics["dx"], metrics["dy"], metrics["a11"], metrics["a12"], metrics["a21"], metrics["a22"], n, nz)
     h = 1 if order == 2 else 0
     w = (slice(3 - h, 3 + n + h), slice(3 - h, 3 + n + h), slice(0, nz))
-    assert np.array_equal(ua.numpy()[w], rua[w]) and np.array_equal(va.numpy()[w], rva[w])
+    wrong = [d for d in (differ("ua", ua.numpy()[w], rua[w]), differ("va", va.numpy()[w], rva[w])) if d]
+    assert not wrong, wrong
     if order == 4:
         return {}
     # compute_preamble + omega
     cond = dycore_condensates(0, s["delp"].shape)
-    t = {k: np.abs(cond[k]) for k in ("qliquid", "qrain", "qice", "qsnow", "qgraupel")}
-    t["qvapor"] = 0.01 * np.ones_like(s["delp"])
+    t = {k: rnd(np.abs(cond[k])) for k in ("qliquid", "qrain", "qice", "qsnow", "qgraupel")}
+    t["qvapor"] = rnd(0.01 * np.ones_like(s["delp"]))
     qt = {k: env.q3(a) for k, a in t.items()}
-    pt0 = s["pt"] * 300.0
+    pt0 = rnd(s["pt"] * 300.0)
     f = {k: env.q3(a) for k, a in (("pt", pt0), ("delp", s["delp"]), ("delz", s["delz"]), ("w", s["w"]))}
     q_con, pkz, cappa, dp1, omga = env.q3(), env.q3(), env.q3(), env.q3(), env.q3()
     water = pointer_table([qt[k] for k in ("qvapor", "qliquid", "qrain", "qsnow", "qice", "qgraupel")])
@@ -989,33 +1039,43 @@ def check_c2l_and_preamble(lib, device, n, nz, order):
     cw = (slice(3, 3 + n), slice(3, 3 + n), slice(0, nz))
     tw = {k: a[cw] for k, a in t.items()}
     gz, _, rpkz, rcappa, rdp1 = dycore_parts.fv_setup(tw, pt0[cw], s["delp"][cw], s["delz"][cw])
-    assert np.array_equal(q_con.numpy()[cw], gz) and np.array_equal(cappa.numpy()[cw], rcappa) and np.array_equal(dp1.numpy()[cw], rdp1)
-    errs = {"pkz": compare(rpkz, pkz.numpy()[cw])}
-    assert errs["pkz"] < 1e-14
+    wrong = [differ(k, got.numpy()[cw], ref) for k, got, ref in (("q_con", q_con, gz), ("cappa", cappa, rcappa), ("dp1", dp1, rdp1),
+                                                                  ("omga", omga, s["delp"][cw] / s["delz"][cw] * s["w"][cw]))]
+    assert not any(wrong), [d for d in wrong if d]
+    errs = {"pkz": last_place("pkz", pkz.numpy()[cw], rpkz)}
     rpt = pt0[cw] * (1.0 + rdp1) * (1.0 - gz) / rpkz
-    errs["pt"] = compare(rpt, f["pt"].numpy()[cw])
-    assert errs["pt"] < 1e-14
-    assert np.array_equal(omga.numpy()[cw], s["delp"][cw] / s["delz"][cw] * s["w"][cw])
+    errs["pt"] = last_place("pt", f["pt"].numpy()[cw], rpt)
     from oracle import constants as oc
 
     assert oc.ZVIR > 0
     return errs
 
 
-def check_ord8_transport(lib, device, n, nz):
+def check_ord8_transport(lib, device, n, nz, storage=None):
     """Monotone (ord 8) PPM transport of the synthetic state's pt on a C<n> tile with nz levels, with the oracle's own flux
-    preparation, against oracle/ppm_transport.py: both fluxes bit for bit."""
+    preparation, against oracle/ppm_transport.py: both fluxes bit for bit.
+
+    storage="f32" (a float32-storage library): metrics, Courant numbers, area fluxes and pt are float32 values, and both fluxes
+    equal float32(oracle) bit for bit -- without mass fluxes k_fvtp2d keeps the inner fluxes and the advected intermediates in
+    LDS as double, so nothing lies between the loads and the two stores.  Returns {flux: number of elements compared}."""
     from oracle import dgrid_sw
     from oracle import ppm_transport as tr
     from pace_amd import synthetic
     from pace_amd.fv3core.stencils.fvtp2d import FiniteVolumeTransport
 
+    assert storage in (None, "f32") and lib.real_bytes == (4 if storage else 8)
     metrics = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(metrics, n, nz)
+    if storage:
+        from opchain import f32_dict as rnd
+
+        metrics, s = rnd(metrics), rnd(s)
     g = oracle_grid(metrics, n, nz)
     for k in ("crx", "cry", "xfx", "yfx"):
         s[k] = np.zeros_like(s["pt"])
     dgrid_sw.fxadv(g, s["uc"], s["vc"], s["crx"], s["cry"], s["xfx"], s["yfx"], np.zeros_like(s["pt"]), np.zeros_like(s["pt"]), s["dt"])
+    if storage:
+        s = rnd(s)
     env = Env(lib, device, metrics, n, nz)
     op = FiniteVolumeTransport(env.stencil_factory, env.qf, env.grid_data, env.damping, 0, 8)
     f = {k: env.q3(s[k]) for k in ("pt", "crx", "cry", "xfx", "yfx")}
@@ -1027,5 +1087,168 @@ def check_ord8_transport(lib, device, n, nz):
         torch.cuda.synchronize()
     ofx, ofy = np.zeros_like(s["pt"]), np.zeros_like(s["pt"])
     tr.fvtp2d(g, s["pt"].copy(), s["crx"], s["cry"], s["xfx"], s["yfx"], ofx, ofy, 8)
-    assert np.array_equal(ofx[window(n, 1, 0, nz)], fx.numpy()[window(n, 1, 0, nz)])
-    assert np.array_equal(ofy[window(n, 0, 1, nz)], fy.numpy()[window(n, 0, 1, nz)])
+    if storage:
+        ofx, ofy = ofx.astype(np.float32), ofy.astype(np.float32)
+    wx, wy = window(n, 1, 0, nz), window(n, 0, 1, nz)
+    gx, gy = fx.numpy(), fy.numpy()
+    assert gx.dtype == ofx.dtype
+    bad = {k: int((a != b).sum()) for k, a, b in (("fx", ofx[wx], gx[wx]), ("fy", ofy[wy], gy[wy])) if not np.array_equal(a, b)}
+    assert not bad, bad
+    return {"fx": int(ofx[wx].size), "fy": int(ofy[wy].size)}
+
+
+def check_l2e_kernels(lib, device, n, km, storage=None):
+    """The four kernels of k_l2e.hip one by one through their C entry points (pace_l2e_prepare, pace_l2e_post, pace_l2e_pressures
+    in both directions, pace_l2e_finish as the last step and not) on l2e_synthetic_case, against the statements of
+    oracle/remapping.lagrangian_to_eulerian that each of them restates, evaluated in float64 on what the fields hold.  Every
+    kernel is one pass from its loads to its stores, so with either storage type every output without exp / log equals the
+    reference as stored, bit for bit (storage="f32": float32(reference of float32 inputs)); pt, pn2, pk of the prepare kernel and
+    pkz of the post kernel (exp, log) are within 1e-14 (float64) or within 1 float32 ulp with at most 1e-4 of the window
+    different at all (float32: the last-place class of tests/test_f32_operators.py).  Returns {output: what was measured}."""
+    import ctypes as C
+
+    from oracle import constants as oc
+    from oracle.remapping import _moist_cvm_gz
+    from pace_amd import synthetic
+    from pace_amd.fv3core.stencils._common import dptr
+    from pace_amd.fv3core.stencils.fillz import pointer_table
+    from pace_amd.util.grid import geom_struct
+
+    assert storage in (None, "f32") and lib.real_bytes == (4 if storage else 8)
+    real = np.float32 if storage else np.float64
+
+    def rnd(a):
+        from opchain import f32
+
+        return f32(a) if storage else a
+
+    def sync():
+        if device != "cpu":
+            import torch
+
+            torch.cuda.synchronize()
+
+    f, tr, ak, bk, _ = l2e_synthetic_case(n, km)
+    f, tr, ak, bk = {k: rnd(v) for k, v in f.items()}, {k: rnd(v) for k, v in tr.items()}, rnd(ak), rnd(bk)
+    ptop = float(ak[0])
+    env = Env(lib, device, synthetic.tile_metrics(n, km), n, km)
+    geom_s = geom_struct(env.qf)
+    geom = C.byref(geom_s)
+    akq, bkq = env.kq(ak), env.kq(bk)  # (held: a pointer taken from a temporary outlives it)
+    report, wrong = {}, []
+    K, KK = slice(0, km), slice(0, km + 1)
+    cw, cj, ci = (slice(3, 3 + n), slice(3, 3 + n)), (slice(3, 3 + n), slice(3, 4 + n)), (slice(3, 4 + n), slice(3, 3 + n))
+
+    def exact(name, got, ref):
+        got, ref = got.numpy(), ref.astype(real)
+        assert got.dtype == real and np.isfinite(ref).all(), name
+        report[name] = int((got != ref).sum())
+        if report[name]:
+            wrong.append(f"{name}: {report[name]} of {ref.size} differ")
+
+    def last_place(name, got, ref):
+        got = got.numpy()
+        assert got.dtype == real and np.isfinite(ref).all(), name
+        if not storage:
+            report[name] = compare(ref, got)
+            if not report[name] < 1e-14:
+                wrong.append(f"{name}: {report[name]:.1e}")
+            return
+        r32 = ref.astype(np.float32)
+        u = np.abs(got.view(np.int32).astype(np.int64) - r32.view(np.int32).astype(np.int64))  # (one sign throughout)
+        assert (np.sign(got) == np.sign(r32)).all(), name
+        report[name] = int((u != 0).sum())
+        if u.max() > 1 or report[name] > 1e-4 * u.size:
+            wrong.append(f"{name}: {report[name]} of {u.size} differ, by up to {int(u.max())} ulp")
+
+    class View:  # a window of a field, with the numpy() of a Quantity
+        def __init__(self, q, w):
+            self.q, self.w = q, w
+
+        def numpy(self):
+            return self.q.numpy()[self.w]
+
+    def water(qt):
+        return pointer_table([qt[k] for k in ("qvapor", "qliquid", "qrain", "qsnow", "qice", "qgraupel")])
+
+    def moist(t, w):
+        cvm, gz = _moist_cvm_gz({k: v[w] for k, v in t.items()})
+        return gz, oc.RDGAS / (oc.RDGAS + cvm / (1.0 + oc.ZVIR * t["qvapor"][w]))
+
+    # ---- k_l2e_prepare ----
+    qt = {k: env.q3(v) for k, v in tr.items()}
+    q = {k: env.q3(f[k]) for k in ("pt", "delp", "delz", "pe", "peln", "pk")}
+    o = {k: env.q3() for k in ("q_con", "cappa", "pe1", "pe2", "dp2", "pn2")}
+    ps = env.q2()
+    lib.call("pace_l2e_prepare", geom, water(qt), dptr(o["q_con"]), dptr(q["pt"]), dptr(o["cappa"]), dptr(q["delp"]), dptr(q["delz"]),
+             dptr(q["pe"]), dptr(o["pe1"]), dptr(o["pe2"]), dptr(akq), dptr(bkq), dptr(o["dp2"]), dptr(ps), dptr(o["pn2"]),
+             dptr(q["peln"]), dptr(q["pk"]), ptop, oc.KAPPA, oc.ZVIR, None)
+    sync()
+    c3 = cw + (K,)
+    gz, cappa = moist(tr, c3)
+    psr = f["pe"][cw + (km,)]
+    e = np.stack([np.full(psr.shape, ptop) if k == 0 else (psr if k == km else ak[k] + bk[k] * psr) for k in range(km + 1)], axis=2)
+    exact("prepare.q_con", View(o["q_con"], c3), gz)
+    exact("prepare.cappa", View(o["cappa"], c3), cappa)
+    exact("prepare.delz", View(q["delz"], c3), -f["delz"][c3] / f["delp"][c3])
+    exact("prepare.pe1", View(o["pe1"], cj + (KK,)), f["pe"][cj + (KK,)])
+    exact("prepare.pe2", View(o["pe2"], cw + (KK,)), e)
+    exact("prepare.pe2.extra_row", View(o["pe2"], (cj[0], slice(3 + n, 4 + n), slice(km, km + 1))), f["pe"][cj[0], 3 + n:4 + n, km:km + 1])
+    exact("prepare.dp2", View(o["dp2"], c3), e[:, :, 1:] - e[:, :, :-1])
+    exact("prepare.delp", View(q["delp"], c3), e[:, :, 1:] - e[:, :, :-1])
+    exact("prepare.ps", View(ps, cw), psr)
+    exact("prepare.pn2.bottom", View(o["pn2"], cw + (slice(km, km + 1),)), f["peln"][cw + (slice(km, km + 1),)])
+    p = f["pt"][c3]
+    last_place("prepare.pt", View(q["pt"], c3), p * np.exp(cappa / (1.0 - cappa) * np.log(oc.RDG * f["delp"][c3] / f["delz"][c3] * p)))
+    last_place("prepare.pn2", View(o["pn2"], c3), np.log(e[:, :, :km]))
+    last_place("prepare.pk", View(q["pk"], c3), np.exp(oc.KAPPA * np.log(e[:, :, :km])))
+    # ---- k_l2e_post (delz: the adjusted one, -delz / delp) ----
+    dz_in = rnd(-f["delz"] / np.where(f["delp"] != 0.0, f["delp"], 1.0))
+    pn2_in = rnd(f["peln"] + 1.0e-3)
+    q = {k: env.q3(v) for k, v in (("pt", f["pt"]), ("delp", f["delp"]), ("delz", dz_in), ("peln", f["peln"]), ("pn2", pn2_in))}
+    o = {k: env.q3() for k in ("q_con", "cappa", "pkz", "pe0")}
+    lib.call("pace_l2e_post", geom, water(qt), dptr(o["q_con"]), dptr(o["pkz"]), dptr(q["pt"]), dptr(o["cappa"]), dptr(q["delp"]),
+             dptr(q["delz"]), dptr(q["peln"]), dptr(o["pe0"]), dptr(q["pn2"]), oc.ZVIR, None)
+    sync()
+    dz = -dz_in[c3] * f["delp"][c3]
+    exact("post.delz", View(q["delz"], c3), dz)
+    exact("post.q_con", View(o["q_con"], c3), gz)
+    exact("post.cappa", View(o["cappa"], c3), cappa)
+    exact("post.pe0", View(o["pe0"], cw + (KK,)), f["peln"][cw + (KK,)])
+    exact("post.peln", View(q["peln"], cw + (KK,)), pn2_in[cw + (KK,)])
+    last_place("post.pkz", View(o["pkz"], c3), np.exp(cappa * np.log(oc.RDG * f["delp"][c3] / dz * f["pt"][c3])))
+    # ---- k_l2e_pressures ----
+    pe = f["pe"]
+    pe1_in = rnd(pe * (1.0 + 1.0e-3))  # (distinct from pe: a kernel that read pe where it should read pe1 shows)
+    bot = pe[:, :, km]
+    for direction, win, nb in ((0, cj, (slice(3, 3 + n), slice(2, 3 + n))), (1, ci, (slice(2, 3 + n), slice(3, 3 + n)))):
+        q = {"pe": env.q3(pe), "pe1": env.q3(pe1_in)}
+        o = {"pe0": env.q3(), "pe3": env.q3()}
+        lib.call("pace_l2e_pressures", geom, direction, dptr(q["pe"]), dptr(q["pe1"]), dptr(akq), dptr(bkq), dptr(o["pe0"]),
+                 dptr(o["pe3"]), None)
+        sync()
+        here = pe1_in if direction == 0 else pe
+        pe0 = 0.5 * (pe[nb + (KK,)] + here[win + (KK,)])
+        pe0[:, :, 0] = pe[win + (0,)]
+        pe3 = np.stack([ak[k] + (0.5 * bk[k]) * (bot[nb] + bot[win]) for k in range(km + 1)], axis=2)
+        if direction == 1:
+            pe3[:, :, 0] = ak[0]
+        exact(f"pressures{direction}.pe0", View(o["pe0"], win + (KK,)), pe0)
+        exact(f"pressures{direction}.pe3", View(o["pe3"], win + (KK,)), pe3)
+    # ---- k_l2e_finish ----
+    pkz_in = rnd(1.0 + 0.1 * np.abs(np.sin(f["pt"])))
+    pe2_in = rnd(pe * (1.0 - 1.0e-3))
+    for last_step in (True, False):
+        q = {"pe": env.q3(pe), "pe2": env.q3(pe2_in), "pt": env.q3(f["pt"]), "pkz": env.q3(pkz_in)}
+        lib.call("pace_l2e_finish", geom, water(qt), dptr(q["pe"]), dptr(q["pe2"]), dptr(q["pt"]), dptr(q["pkz"]), oc.ZVIR, int(last_step), None)
+        sync()
+        want = pe[cw + (KK,)].copy()
+        want[:, :, 1:km] = pe2_in[cw + (slice(1, km),)]
+        exact(f"finish{int(last_step)}.pe", View(q["pe"], cw + (KK,)), want)
+        if last_step:
+            g5 = tr["qliquid"][c3] + tr["qrain"][c3] + tr["qice"][c3] + tr["qsnow"][c3] + tr["qgraupel"][c3]
+            exact("finish1.pt", View(q["pt"], c3), (f["pt"][c3] + 0.0 * pkz_in[c3]) / ((1.0 + oc.ZVIR * tr["qvapor"][c3]) * (1.0 - g5)))
+        else:
+            exact("finish0.pt", View(q["pt"], c3), f["pt"][c3] / pkz_in[c3])
+    assert not wrong, wrong
+    return report
