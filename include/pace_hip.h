@@ -429,6 +429,67 @@ int pace_l2e_pressures(const pace_geom_t* geom, int dir, const pace_real_t* pe, 
 int pace_l2e_finish(const pace_geom_t* geom, const pace_real_t* const* water, pace_real_t* pe, const pace_real_t* pe2,
                     pace_real_t* pt, const pace_real_t* pkz, double r_vir, int last_step, void* stream);
 
+/* ---- The total-energy fixer (consv_te > 0; the Fortran FV3's compute_total_energy and the consv > consv_min block of
+ * Lagrangian_to_Eulerian: non-hydrostatic, MOIST_CAPPA / USE_COND, nwat = 6.  The reference carries te_2d / te0_2d and dtmp
+ * and stops at the global sum).  Both storage types; every operation is double on the stored values (the float32 library
+ * widens first; exact), without FMA, without a reciprocal, without a transcendental.
+ *
+ * pace_energy_columns: ONE launch.  water: HOST array of the six device pointers qvapor, qliquid, qrain, qsnow, qice, qgraupel;
+ * pt, delp, delz, w, u, v, pkz share the storage geometry of geom; phis, rsin2, cosa_s, area, te0_2d, te_2d, zsum1 are planes of
+ * the same row stride.  For every column (i, j) of the compute domain -- origin (3, 3), extent (n, n) -- one pass from the bottom
+ * level up, k = nk - 1 ... 0, in this order:
+ *   phi_below = phis[i,j]                         before the first level
+ *   phi_above = phi_below - GRAV * delz[k]
+ *   ke   = (0.5 * rsin2) * ((((u0 * u0 + u1 * u1) + v0 * v0) + v1 * v1) - ((u0 + u1) * (v0 + v1)) * cosa_s)
+ *              u0 = u[i,j,k], u1 = u[i,j+1,k], v0 = v[i,j,k], v1 = v[i+1,j,k]: the D-grid winds around the cell
+ *   ql   = qliquid + qrain;  qs = (qice + qsnow) + qgraupel;  gz = ql + qs              moist_cv.py's nwat-6 order
+ *   cvm  = (1 - (qvapor + gz)) * CV_AIR + qvapor * CV_VAP + ql * C_LIQ + qs * C_ICE     csrc/thermo.h moist_cvm
+ *   e    = cvm * pt                                                     mode 0: pt holds the temperature
+ *   e    = (cvm * pt) / ((1 + r_vir * qvapor) * (1 - gz))               mode 1: pt as between pace_l2e_post and pace_l2e_finish
+ *   te   = te + delp[k] * (e + 0.5 * (((phi_above + phi_below) + w[k] * w[k]) + ke))      te = 0 before the first level
+ *   zsum = zsum + pkz[k] * delp[k]                                      mode 1 only; zsum = 0 before the first level
+ *   phi_below = phi_above
+ * (the Fortran sums from the top down; the bottom-up pass reads delz once and differs in rounding only).
+ *   mode 0 stores te0_2d[i,j] = (pace_real_t)te; pkz, area, te_2d, zsum1, words are not used and may be NULL.
+ *   mode 1 reads te0_2d, forms te_2d = (double)te0_2d[i,j] - te, stores te_2d[i,j] = (pace_real_t)te_2d and zsum1[i,j] =
+ *          (pace_real_t)zsum, and ADDS area * te_2d into words[0 .. 4] and area * zsum into words[5 .. 9] -- the products of the
+ *          doubles in registers, before the narrowing.  The caller zeroes `words` (PACE_ENERGY_WORDS int64 on the device) before
+ *          the first launch of a sum.
+ * Reproducible accumulator: a sum is five signed 64-bit words.  A finite v with |v| < 2^120 adds the four 40-bit limbs
+ * l_n = (trunc(|v| * 2^40) >> 40 n) & (2^40 - 1) to word[n], n = 0 .. 3, negated for v < 0 (the significand is only shifted:
+ * exact; bits below 2^-40 are dropped toward zero); any other v (NaN, infinity, |v| >= 2^120) adds 1 to word[4] and nothing
+ * else.  The additions are integer additions (a fold over the workgroup, then 64-bit integer atomics; no floating-point atomics):
+ * the words do not depend on the order, the launch shape or the partition into tiles.  23 bits of headroom: fewer than 2^23
+ * addends per sum over all the tiles that are finalised together.
+ * Nothing outside the planes' compute windows and the ten words is written; nothing outside the compute domain of the fields is
+ * read (u on n + 1 rows, v on n + 1 columns).
+ * PACE_ERR_ARG: a NULL geom, water entry or array the mode uses, a mode other than 0 / 1, an output that is an input or another
+ * output.
+ *
+ * pace_energy_finalize: ONE launch for any number of tiles (1 .. PACE_ENERGY_MAX_TILES).  words: HOST array of ntiles device
+ * pointers, in tile order, each to a tile's ten words; out: four doubles on the device.  The words are summed over the tiles, then
+ * each sum is decoded: M = sum_n word[n] * 2^(40 n) as an exact integer, the value M * 2^-40 rounded ONCE to the nearest double
+ * (ties to even), NaN if word[4] != 0.
+ *   out[0] = S_te  the sum of area * te_2d        out[1] = S_z  the sum of area * zsum1
+ *   out[2] = dtmp   = (consv_te * S_te) / (CV_AIR * S_z)
+ *   out[3] = e_flux = (consv_te * S_te) / ((((GRAV * dt_atmos) * 4) * PI) * (RADIUS * RADIUS))      W / m^2
+ * PACE_ERR_ARG: NULL words, entry or out, ntiles out of range, a consv_te that is not finite, a dt_atmos that is not finite and
+ * positive.
+ *
+ * pace_l2e_finish_dtmp: pace_l2e_finish's last-step form with the temperature increment of the fixer,
+ *   pt = (pt + dtmp * pkz) / ((1 + r_vir * qvapor) * (1 - gz)),   gz = (((qliquid + qrain) + qice) + qsnow) + qgraupel,
+ * dtmp = energy_result[2] read on the device (the host never needs it); pe as pace_l2e_finish. */
+#define PACE_ENERGY_WORDS 10
+#define PACE_ENERGY_MAX_TILES 64
+int pace_energy_columns(const pace_geom_t* geom, int mode, const pace_real_t* const* water, const pace_real_t* pt,
+                        const pace_real_t* delp, const pace_real_t* delz, const pace_real_t* w, const pace_real_t* u,
+                        const pace_real_t* v, const pace_real_t* pkz, const pace_real_t* phis, const pace_real_t* rsin2,
+                        const pace_real_t* cosa_s, const pace_real_t* area, pace_real_t* te0_2d, pace_real_t* te_2d,
+                        pace_real_t* zsum1, int64_t* words, double r_vir, void* stream);
+int pace_energy_finalize(const int64_t* const* words, int ntiles, double consv_te, double dt_atmos, double* out, void* stream);
+int pace_l2e_finish_dtmp(const pace_geom_t* geom, const pace_real_t* const* water, pace_real_t* pe, const pace_real_t* pe2,
+                         pace_real_t* pt, const pace_real_t* pkz, double r_vir, const double* energy_result, void* stream);
+
 /* ---- SatAdjust3d (fv3core/pace/fv3core/stencils/saturation_adjustment.py:947-1108): the fast saturation adjustment that
  * LagrangianToEulerian runs between the remap of v and moist_pt_last_step / the division by pkz (remapping.py:627-672).
  *   pace_sat_adjust_tables  fills `tables` (a DEVICE buffer of PACE_SAT_ADJUST_TABLE_DOUBLES doubles, in both builds) with the

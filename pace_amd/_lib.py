@@ -213,6 +213,9 @@ class HeldSuarezConfig(C.Structure):  # include/pace_hip.h pace_held_suarez_conf
                 ("heating_scale", C.c_double)]
 
 
+ENERGY_WORDS, ENERGY_MAX_TILES = 10, 64  # include/pace_hip.h PACE_ENERGY_WORDS, PACE_ENERGY_MAX_TILES
+
+
 class PaceError(RuntimeError):
     pass
 
@@ -290,6 +293,9 @@ _PROTOS = {
     "pace_l2e_post": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 9 + [C.c_double, C.c_void_p]),
     "pace_l2e_pressures": (C.c_int, [_P(Geom), C.c_int] + [c_dp] * 6 + [C.c_void_p]),
     "pace_l2e_finish": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 4 + [C.c_double, C.c_int, C.c_void_p]),
+    "pace_energy_columns": (C.c_int, [_P(Geom), C.c_int, _P(C.c_void_p)] + [c_dp] * 14 + [C.c_void_p, C.c_double, C.c_void_p]),
+    "pace_energy_finalize": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_double, C.c_double, c_dp, C.c_void_p]),
+    "pace_l2e_finish_dtmp": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 4 + [C.c_double, c_dp, C.c_void_p]),
     "pace_fv_setup_pt": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 7 + [C.c_void_p]),
     "pace_omega_from_w": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [C.c_void_p]),
     "pace_neg_adj3": (C.c_int, [_P(Geom), _P(C.c_void_p)] + [c_dp] * 3 + [C.c_void_p]),

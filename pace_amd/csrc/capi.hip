@@ -526,6 +526,43 @@ int pace_l2e_finish(const pace_geom_t* geom, const real* const* water, real* pe,
   return launch_l2e_finish(make_geo(geom), water, pe, pe2, pt, pkz, r_vir, last_step, S(stream));
 }
 
+int pace_l2e_finish_dtmp(const pace_geom_t* geom, const real* const* water, real* pe, const real* pe2, real* pt,
+                         const real* pkz, double r_vir, const double* energy_result, void* stream) {
+  NEED(geom && six(water) && pe && pe2 && pt && pkz && energy_result);
+  return launch_l2e_finish_dtmp(make_geo(geom), water, pe, pe2, pt, pkz, r_vir, energy_result, S(stream));
+}
+
+int pace_energy_columns(const pace_geom_t* geom, int mode, const real* const* water, const real* pt, const real* delp,
+                        const real* delz, const real* w, const real* u, const real* v, const real* pkz, const real* phis,
+                        const real* rsin2, const real* cosa_s, const real* area, real* te0_2d, real* te_2d, real* zsum1,
+                        int64_t* words, double r_vir, void* stream) {
+  NEED(geom && six(water) && pt && delp && delz && w && u && v && phis && rsin2 && cosa_s && te0_2d);
+  if (mode != 0 && mode != 1) return PACE_ERR_ARG;
+  const real* const in[] = {water[0], water[1], water[2], water[3], water[4], water[5], pt, delp, delz, w, u, v, pkz, phis, rsin2,
+                            cosa_s, area};
+  if (mode == 1) {
+    if (!(pkz && area && te_2d && zsum1 && words)) return PACE_ERR_ARG;
+    if (te_2d == zsum1 || te_2d == te0_2d || zsum1 == te0_2d) return PACE_ERR_ARG;
+    if ((const void*)words == (const void*)te_2d || (const void*)words == (const void*)zsum1) return PACE_ERR_ARG;
+    for (const real* p : in)
+      if (p == te_2d || p == zsum1 || p == te0_2d || (const void*)p == (const void*)words) return PACE_ERR_ARG;
+  } else {
+    for (const real* p : in)
+      if (p == te0_2d) return PACE_ERR_ARG;
+  }
+  return launch_energy_columns(make_geo(geom), mode, water, pt, delp, delz, w, u, v, pkz, phis, rsin2, cosa_s, area, te0_2d, te_2d,
+                               zsum1, words, r_vir, S(stream));
+}
+
+int pace_energy_finalize(const int64_t* const* words, int ntiles, double consv_te, double dt_atmos, double* out, void* stream) {
+  if (!words || !out || ntiles < 1 || ntiles > PACE_ENERGY_MAX_TILES) return PACE_ERR_ARG;
+  for (int t = 0; t < ntiles; ++t)
+    if (!words[t] || (const void*)words[t] == (const void*)out) return PACE_ERR_ARG;
+  if (!std::isfinite(consv_te) || !(std::isfinite(dt_atmos) && dt_atmos > 0.0)) return PACE_ERR_ARG;
+  (void)hipGetLastError();
+  return launch_energy_finalize(words, ntiles, consv_te, dt_atmos, out, S(stream));
+}
+
 static bool six_rw(real* const* w) {
   if (!w) return false;
   for (int n = 0; n < 6; ++n)

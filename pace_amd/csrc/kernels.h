@@ -309,6 +309,14 @@ int launch_nudge(const Geo& g, const pace_nudge_item_t* items, int nitems, doubl
 int launch_held_suarez(const Geo& g, const pace_held_suarez_config_t& cfg, const real* pe, const real* ua, const real* va,
                        const real* pt, const real* sin2lat, const real* cos2lat, real* u_dt, real* v_dt, real* pt_dt, real* teq,
                        hipStream_t st);
+// k_energy.hip
+int launch_energy_columns(const Geo& g, int mode, const real* const* water, const real* pt, const real* delp, const real* delz,
+                          const real* w, const real* u, const real* v, const real* pkz, const real* phis, const real* rsin2,
+                          const real* cosa_s, const real* area, real* te0_2d, real* te_2d, real* zsum1, int64_t* words,
+                          double r_vir, hipStream_t st);
+int launch_energy_finalize(const int64_t* const* words, int ntiles, double consv_te, double dt_atmos, double* out, hipStream_t st);
+int launch_l2e_finish_dtmp(const Geo& g, const real* const* water, real* pe, const real* pe2, real* pt, const real* pkz,
+                           double r_vir, const double* result, hipStream_t st);
 // k_dycore.hip
 int launch_fv_setup_pt(const Geo& g, real* const* water, real* q_con, real* pkz, real* pt, real* cappa,
                        const real* delp, const real* delz, real* dp1, hipStream_t st);

@@ -8,6 +8,8 @@
 #include "common.h"
 
 namespace phys {
+constexpr double RADIUS = 6.3712e6;
+constexpr double PI = 3.1415926535897931;
 constexpr double GRAV = 9.80665;
 constexpr double RGRAV = 1.0 / GRAV;
 constexpr double RDGAS = 287.05;

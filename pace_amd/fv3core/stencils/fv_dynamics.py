@@ -10,6 +10,7 @@ from ._common import Operator, check_layout, dptr
 from .c2l_ord import CubedToLatLon
 from .del2cubed import HyperdiffusionDamping
 from .dyn_core import AcousticDynamics
+from .energy_fixer import EnergyFixer
 from .fillz import pointer_table, tracer_variables
 from .neg_adj3 import AdjustNegativeTracerMixingRatio
 from .remapping import LagrangianToEulerian
@@ -88,6 +89,19 @@ class DynamicalCore(Operator):
         self._k_split = config.k_split
         self._conserve_total_energy = config.consv_te
         self._timestep = timestep.total_seconds()
+        # the total-energy fixer: its buffers exist only where it is asked for
+        self._energy_fixer = None
+        if self._conserve_total_energy > 0:
+            transport = comm.comm if hasattr(comm, "comm") else comm
+            self._energy_fixer = EnergyFixer(stencil_factory, quantity_factory, comm, total_tiles=transport.Get_size())
+
+    def energy_fixer_diagnostics(self):
+        """{"dtmp", "e_flux", "te_deficit", "zsum"} of the last step's total-energy fixer as Python floats -- dtmp [K per unit
+        pkz], e_flux [W/m^2], the global sums of area * te_2d [J] and area * zsum1 -- by one small transfer made here, on
+        demand, never in the step."""
+        if self._energy_fixer is None:
+            raise RuntimeError("energy_fixer_diagnostics: the dynamical core runs with consv_te = 0")
+        return self._energy_fixer.diagnostics()
 
     # ---- the reference's checkpoint call sites (fv_dynamics.py:321-423): same names, same variables ----
     def _checkpoint_fvdynamics(self, state, tag: str):
@@ -129,17 +143,28 @@ class DynamicalCore(Operator):
     def compute_preamble(self, state, is_root_rank: bool):
         if self.config.hydrostatic:
             raise NotImplementedError("Hydrostatic is not implemented")
-        if self._conserve_total_energy > 0:
-            raise NotImplementedError("compute total energy is not implemented")
         if (not self.config.rf_fast) and self.config.tau != 0:
             raise NotImplementedError("Rayleigh_Super, called when rf_fast=False and tau !=0")
         if self.config.adiabatic and self.config.kord_tm > 0:
             raise NotImplementedError("unimplemented namelist options adiabatic with positive kord_tm")
         # fv_setup + the pt adjustment (fv_dynamics.py:446-487) in one pass
-        water = pointer_table([state.qvapor, state.qliquid, state.qrain, state.qsnow, state.qice, state.qgraupel])
+        species = [state.qvapor, state.qliquid, state.qrain, state.qsnow, state.qice, state.qgraupel]
+        if self._energy_fixer is not None:
+            # compute_total_energy (fv_dynamics.py:470-473 stops here): te0_2d from the temperature at the top of the step
+            gd = self.grid_data
+            self._energy_fixer.total_energy(0, species, state.pt, state.delp, state.delz, state.w, state.u, state.v, None,
+                                            state.phis, gd.rsin2, gd.cosa_s, None, self._te0_2d, constants.ZVIR)
+        water = pointer_table(species)
         check_layout(self._geom, state.q_con, state.pkz, state.pt, self._cappa, state.delp, state.delz, self._dp_initial)
         self.call("pace_fv_setup_pt", water, dptr(state.q_con), dptr(state.pkz), dptr(state.pt), dptr(self._cappa),
                   dptr(state.delp), dptr(state.delz), dptr(self._dp_initial), self.stream())
+
+    def _energy_arguments(self):
+        if self._energy_fixer is None:
+            return {}
+        gd = self.grid_data
+        return dict(te0_2d=self._te0_2d, rsin2=gd.rsin2, cosa_s=gd.cosa_s, area_64=gd.area_64, energy_fixer=self._energy_fixer,
+                    dt_atmos=self._timestep)
 
     def __call__(self, *args, **kwargs):
         return self.step_dynamics(*args, **kwargs)
@@ -167,7 +192,7 @@ class DynamicalCore(Operator):
                         self.tracers, state.pt, state.delp, state.delz, state.peln, state.u, state.v, state.w, self._cappa,
                         state.q_con, state.qcld, state.pkz, state.pk, state.pe, state.phis, state.ps, self._wsd, self._ak,
                         self._bk, self._dp_initial, self._ptop, constants.KAPPA, constants.ZVIR, last_step,
-                        self._conserve_total_energy, self._timestep / self._k_split)
+                        self._conserve_total_energy, self._timestep / self._k_split, **self._energy_arguments())
                     self._checkpoint_remapping_out(state)
                 if last_step:
                     da_min = float(self._da_min)

@@ -60,14 +60,23 @@ class LagrangianToEulerian(Operator):
             self._saturation_adjustment = SatAdjust3d(sf, config.sat_adjust, area_64, self.kmp, quantity_factory=qf)
 
     def __call__(self, tracers, pt, delp, delz, peln, u, v, w, cappa, q_con, q_cld, pkz, pk, pe, hs, ps, wsd, ak, bk, dp1,
-                 ptop: float, akap: float, zvir: float, last_step: bool, consv_te: float, mdt: float):
+                 ptop: float, akap: float, zvir: float, last_step: bool, consv_te: float, mdt: float, *, te0_2d=None,
+                 rsin2=None, cosa_s=None, area_64=None, energy_fixer=None, dt_atmos=None):
         """Same arguments as the reference (remapping.py:485-563): tracers, pt, delp, delz, peln, u, v, w, cappa (inout);
         q_con, pk, ps (out); pkz, pe (inout); wsd, ak, bk (in); q_cld, hs, dp1, mdt are only used by the saturation
-        adjustment."""
+        adjustment.
+
+        Keyword-only, for consv_te > CONSV_MIN on the last step (the total-energy fixer, energy_fixer.py): te0_2d, the column
+        energies at the top of the step (EnergyFixer.total_energy(0, ...)); the metric planes rsin2, cosa_s and area_64; the
+        EnergyFixer that owns the buffers and the communicator of the global sum; dt_atmos, the seconds e_flux refers to
+        (mdt where it is not given).  Without them such a call raises as the reference does."""
         check_layout(self._geom, pt, delp, delz, peln, u, v, w, cappa, q_con, pkz, pk, pe)
+        fix_energy = False
         if last_step:
             if consv_te > CONSV_MIN:
-                raise NotImplementedError("We do not support consv_te > 0.001 because that would trigger an allReduce")
+                if any(x is None for x in (te0_2d, rsin2, cosa_s, area_64, energy_fixer)):
+                    raise NotImplementedError("We do not support consv_te > 0.001 because that would trigger an allReduce")
+                fix_energy = True
             elif consv_te < -CONSV_MIN:
                 raise NotImplementedError("Unimplemented/untested case consv(" + str(consv_te) + ")  < -CONSV_MIN("
                                           + str(-CONSV_MIN) + ")")
@@ -87,6 +96,11 @@ class LagrangianToEulerian(Operator):
         self._map_single_u(u, self._pe0, self._pe3)
         self.call("pace_l2e_pressures", 1, dptr(pe), dptr(self._pe1), dptr(ak), dptr(bk), dptr(self._pe0), dptr(self._pe3), st())
         self._map_single_v(v, self._pe0, self._pe3)
+        if fix_energy:
+            # the energy of the remapped state against te0_2d, then the global sum: dtmp stays on the device
+            energy_fixer.total_energy(1, [tracers[name] for name in _WATER], pt, delp, delz, w, u, v, pkz, hs, rsin2, cosa_s,
+                                      area_64, te0_2d, zvir)
+            result = energy_fixer.finalize(consv_te, mdt if dt_atmos is None else dt_atmos)
         if self._do_sat_adjust:
             fast_mp_consv = consv_te > CONSV_MIN
             self._saturation_adjustment(dp1, tracers["qvapor"], tracers["qliquid"], tracers["qice"], tracers["qrain"],
@@ -94,4 +108,9 @@ class LagrangianToEulerian(Operator):
                                         zvir, mdt, fast_mp_consv, last_step, akap, self.kmp)
         # on the last step, we need the regular temperature to send to the physics, but if we're staying in dynamics we
         # need to keep it as the virtual potential temperature
-        self.call("pace_l2e_finish", water, dptr(pe), dptr(self._pe2), dptr(pt), dptr(pkz), float(zvir), int(bool(last_step)), st())
+        if fix_energy:
+            self.call("pace_l2e_finish_dtmp", water, dptr(pe), dptr(self._pe2), dptr(pt), dptr(pkz), float(zvir), result.data_ptr(),
+                      st())
+        else:
+            self.call("pace_l2e_finish", water, dptr(pe), dptr(self._pe2), dptr(pt), dptr(pkz), float(zvir), int(bool(last_step)),
+                      st())

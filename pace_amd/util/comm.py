@@ -80,6 +80,13 @@ class TorchDistComm:
         self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self._group)
         return t.cpu().numpy().view(np.uint64)
 
+    def allreduce_fixed_point(self, words, finalize, stream=None):
+        """The energy fixer's global sum (pace_amd/fv3core/stencils/energy_fixer.py): `words`, this rank's int64 tensor of
+        fixed-point words, becomes the sum over the ranks by ONE int64 all_reduce(SUM) in place -- on the device under "nccl", no
+        copy to the host -- and ``finalize([words])`` makes this rank's finalising launch.  -> what finalize returned."""
+        self._dist.all_reduce(words, op=self._dist.ReduceOp.SUM, group=self._group)
+        return finalize([words])
+
 
 class NullComm:
     """util/pace/util/null_comm.py:15-80: the rank of a communicator that has no peers -- what it "receives" is a fill value
@@ -114,6 +121,11 @@ class NullComm:
     def allreduce_sum_u64(self, values):
         """None: a rank alone cannot know the sum over the globe."""
         return None
+
+    def allreduce_fixed_point(self, words, finalize, stream=None):
+        """The rank's own tile only: a rank alone cannot know the sum over the globe, so the "global" sum of the energy fixer
+        is this tile's.  It is what lets one tile's LagrangianToEulerian run alone with consv_te > 0."""
+        return finalize([words])
 
 
 class LoopbackComm(NullComm):
@@ -212,6 +224,15 @@ class ThreadComm:
                 self._wait(lambda: w.reduce_generation != gen, "allreduce_sum_u64")
             return w.reduce_result.copy()
 
+    def allreduce_fixed_point(self, words, finalize, stream=None):
+        """The energy fixer's global sum through the host, as allreduce_sum_u64: the words of every tile are summed there (the
+        wrapping unsigned sum is the signed sum), written back into `words`, and every rank makes its own finalising launch."""
+        import numpy as np
+
+        total = self.allreduce_sum_u64(words.cpu().numpy().view(np.uint64))
+        words.copy_(torch.from_numpy(total.view(np.int64).copy()))
+        return finalize([words])
+
     def rendezvous(self, tag, payload, last):
         """The collective of gather and scatter (pace_amd/util/gather.py): every rank posts `payload` under `tag`; the last one
         to arrive runs ``last({rank: payload})`` -- for DeviceCubeComm that is the one launch for the whole cube -- and every
@@ -263,6 +284,21 @@ class DeviceCubeComm(ThreadComm):
         super().__init__(world, rank)
         self.snapshot = bool(snapshot)
         self._halo_generation = defaultdict(int)  # tag -> updates this rank has started under it
+
+    def allreduce_fixed_point(self, words, finalize, stream=None):
+        """The energy fixer's global sum with no copy at all: a rendezvous, and the last rank to arrive makes the ONE finalising
+        launch over the six tiles' word buffers in tile order.  Every rank returns what that launch's finalize returned (the one
+        buffer of results, which every rank's next kernel reads).  The tiles' launches that filled the words and the finalising
+        launch must be ordered by one stream, as a fused halo update's."""
+        def last(posts):
+            order = sorted(posts)
+            streams = [posts[r][1] for r in order]
+            if len(set(streams)) != 1:
+                raise RuntimeError(f"the tiles of a fused global sum launched on different streams ({streams}): the one "
+                                   "finalising launch is ordered behind one stream only")
+            return finalize([posts[r][0] for r in order])
+
+        return self.rendezvous("allreduce_fixed_point", (words, getattr(stream, "value", stream)), last)
 
     def halo_post(self, tag, payload):
         """Post this rank's part of the next update under `tag`.  Returns (ticket, posts): posts is None unless this rank is

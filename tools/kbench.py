@@ -22,6 +22,9 @@
     python tools/kbench.py --only held_suarez       the Held-Suarez forcing of a tile of the baroclinic state, accumulated into the
                                                     tendencies (one pace_held_suarez launch), against a torch restatement on
                                                     the device, the same way, with the launch alone and its bandwidth
+    python tools/kbench.py --only energy_fixer      the total-energy fixer of one tile (consv_te > 0): pace_energy_columns in both
+                                                    modes and pace_energy_finalize against a torch restatement on the device, the
+                                                    same way, with each launch alone and its bandwidth
     python tools/kbench.py --only cube_gather       one output step (fourteen variables as float32 on the host) of six C96 and six
                                                     C192 tiles on this device: one pace_cube_gather launch and one transfer
                                                     against six pace_diag_pack passes, one per tile, with a transfer each
@@ -97,6 +100,9 @@ def main():
         return
     if args.only == "held_suarez":  # (its own fields)
         held_suarez_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "energy_fixer":  # (its own fields)
+        energy_fixer_bench(lib, n, nz, args.reps)
         return
     m = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(m, n, nz)
@@ -1357,6 +1363,103 @@ def held_suarez_bench(lib, n, nz, reps):
     launch = float(np.median(events))
     print(f"  the pace_held_suarez launch in device events: median {launch:.3f} ms (min {min(events):.3f}) = "
           f"{moved / (launch * 1e-3) / 1e9:.0f} GB/s over the algorithmic bytes")
+
+
+def energy_fixer_bench(lib, n, nz, reps):
+    """EnergyFixer on one tile of C<n> x <nz> (helpers.l2e_synthetic_case on synthetic.tile_metrics): the mode-0 launch, the
+    mode-1 launch (the words zeroed first, as in the step) and the finalising launch, each against the same quantities restated
+    with torch on the device (views of the compute domain; the geopotential by a cumulative sum, the global sums as float sums --
+    neither reproducible nor in the kernel's order).  Neither side synchronises; both are timed with the host clock from an idle
+    device to the end of a synchronisation added for the measurement, alternating, medians; then each launch alone in device
+    events, with its bandwidth over the algorithmic bytes: the six species, pt, delp, delz, w, u, v (mode 1: and pkz) read once."""
+    import time
+
+    from helpers import l2e_synthetic_case
+    from pace_amd import synthetic
+    from pace_amd.fv3core.stencils.energy_fixer import EnergyFixer
+    from pace_amd.tile import Env
+    from pace_amd.util import NullComm
+    from pace_amd.util import constants as c
+
+    f, tr, _, _, _ = l2e_synthetic_case(n, nz)
+    rng = np.random.default_rng(7)
+    f["pkz"] = rng.uniform(1.0, 7.0, f["pt"].shape)
+    f["phis"] = rng.uniform(0.0, 2.0e4, f["phis"].shape)
+    env = Env(lib, "cuda", synthetic.tile_metrics(n, nz), n, nz)
+    q = {k: env.q3(f[k]) for k in ("pt", "delp", "delz", "w", "u", "v", "pkz")}
+    water = [env.q3(tr[k]) for k in ("qvapor", "qliquid", "qrain", "qsnow", "qice", "qgraupel")]
+    phis, te0 = env.q2(f["phis"]), env.q2()
+    gd = env.grid_data
+    fixer = EnergyFixer(env.stencil_factory, env.qf, NullComm(0, 6))
+    cs, cs1 = slice(3, 3 + n), slice(4, 4 + n)
+    v3 = {k: x.data[cs, cs, :nz].double() if lib.real_bytes == 4 else x.data[cs, cs, :nz] for k, x in q.items()}
+    u1, v1 = q["u"].data[cs, cs1, :nz], q["v"].data[cs1, cs, :nz]
+    qv, ql, qr, qs, qi, qg = (x.data[cs, cs, :nz] for x in water)
+    rsin2, cosa, area = (x.data[cs, cs, None].double() for x in (gd.rsin2, gd.cosa_s, gd.area_64))
+    ph = phis.data[cs, cs, None].double()
+    restated = {}
+
+    def columns(mode):
+        u0, v0 = v3["u"], v3["v"]
+        interfaces = ph + torch.flip(torch.cumsum(torch.flip(-c.GRAV * v3["delz"], [2]), 2), [2])  # phi_above of every level
+        below = torch.cat([interfaces[:, :, 1:], ph], 2)
+        ke = (0.5 * rsin2) * ((u0 * u0 + u1 * u1 + v0 * v0 + v1 * v1) - ((u0 + u1) * (v0 + v1)) * cosa)
+        liquid, solid = ql + qr, qi + qs + qg
+        gz = liquid + solid
+        cvm = (1.0 - (qv + gz)) * c.CV_AIR + qv * c.CV_VAP + liquid * c.C_LIQ + solid * c.C_ICE
+        e = cvm * v3["pt"]
+        if mode == 1:
+            e = e / ((1.0 + c.ZVIR * qv) * (1.0 - gz))
+        te = (v3["delp"] * (e + 0.5 * (interfaces + below + v3["w"] * v3["w"] + ke))).sum(2)
+        if mode == 0:
+            restated["te0"] = te
+        else:
+            restated["te_2d"] = restated["te0"] - te
+            restated["zsum"] = (v3["pkz"] * v3["delp"]).sum(2)
+
+    def torch_finalize():
+        s_te = (area[:, :, 0] * restated["te_2d"]).sum()
+        s_z = (area[:, :, 0] * restated["zsum"]).sum()
+        restated["out"] = torch.stack([s_te, s_z, s_te / (c.CV_AIR * s_z), s_te / (c.GRAV * 225.0 * 4.0 * c.PI * c.RADIUS ** 2)])
+
+    args = (water, q["pt"], q["delp"], q["delz"], q["w"], q["u"], q["v"])
+    pairs = {
+        "mode 0": (lambda: fixer.total_energy(0, *args, None, phis, gd.rsin2, gd.cosa_s, None, te0, c.ZVIR), lambda: columns(0)),
+        "mode 1": (lambda: fixer.total_energy(1, *args, q["pkz"], phis, gd.rsin2, gd.cosa_s, gd.area_64, te0, c.ZVIR),
+                   lambda: columns(1)),
+        "finalize": (lambda: fixer.finalize(1.0, 225.0), torch_finalize),
+    }
+    for hip, restatement in pairs.values():
+        hip()
+        restatement()
+    torch.cuda.synchronize()
+    got = fixer.result.cpu().numpy()
+    want = restated["out"].cpu().numpy()
+    te_err = float((te0.data[cs, cs].double() - restated["te0"]).abs().max() / restated["te0"].abs().max())
+    print(f"  te0_2d: max |hip - torch| / max |torch| {te_err:.3e}; S_te hip {got[0]:.12e} torch {want[0]:.12e}; "
+          f"S_z hip {got[1]:.12e} torch {want[1]:.12e}; dtmp hip {got[2]:.6e} torch {want[2]:.6e}")
+    cells = n * n * nz
+    moved = {"mode 0": (12 * cells + 4 * n * n) * lib.real_bytes, "mode 1": (13 * cells + 7 * n * n) * lib.real_bytes, "finalize": 112}
+    print(f"energy_fixer C{n} x {nz}, float{8 * lib.real_bytes} fields, one tile: {n * n} columns; medians of {reps} alternating runs, ms")
+    for name, (hip, restatement) in pairs.items():
+        times = {"hip": [], "torch": []}
+        for _ in range(3):
+            hip()
+            restatement()
+        for _ in range(reps):
+            for k, fn in (("hip", hip), ("torch", restatement)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) * 1e3)
+        med = {k: float(np.median(x)) for k, x in times.items()}
+        events = times_hip_calibrate(hip, reps)
+        launch = float(np.median(events))
+        rate = f" = {moved[name] / (launch * 1e-3) / 1e9:.0f} GB/s over {moved[name] / 1e6:.1f} MB" if moved[name] > 1e6 else ""
+        print(f"  {name:9s} hip {med['hip']:8.3f} ms (min {min(times['hip']):.3f})   torch {med['torch']:8.3f} ms (min "
+              f"{min(times['torch']):.3f})   ratio torch / hip {med['torch'] / med['hip']:.2f}; in device events: median "
+              f"{launch * 1e3:.1f} us (min {min(events) * 1e3:.1f}){rate}")
 
 
 def times_hip_calibrate(fn, reps=10):
