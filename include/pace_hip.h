@@ -382,6 +382,62 @@ int pace_apply_tracer_flux(const pace_geom_t* geom, const pace_metrics_t* met, p
                            const pace_real_t* fx, const pace_real_t* fy, const pace_real_t* dp2, void* stream);
 int pace_swap_dp(const pace_geom_t* geom, pace_real_t* dp1, pace_real_t* dp2, void* stream);
 
+/* ---- Courant-number sub-cycling per level (the Fortran tracer_2d_1L: mp_reduce_max(cmax, npz), level k sub-cycled
+ * int(1. + cmax(k)) times; the reference fixes cmax = 2.0 and keeps the two cmax stencils, tracer_2d_1l.py:103-112, and their
+ * call site, :312-339, commented out).  Both storage types; every operation is double on the stored values (the float32 library
+ * widens first; exact).  Nothing here is sensitive to FMA contraction: fabs, comparisons, one add, one subtract, one reciprocal.
+ *
+ * pace_tracer_cmax: ONE launch per tile.  cx, cy share the storage geometry of geom, sin_sg5 is a plane of the same row stride,
+ * cmax is nk doubles on the device, which the caller zeroes before the launch.  For every level k = 0 .. nk - 1, cmax[k] becomes
+ * the maximum of its old value and, over the cells i = 3 .. n + 2, j = 3 .. n + 2 of the compute domain ONLY -- not column n + 3
+ * of cx, not row n + 3 of cy, no halo --, of
+ *   m                             for k < nk / 6 - 1     (integer division: the Fortran's "k < npz/6", k counted from 1)
+ *   (m + 1.0) - sin_sg5[i,j]      otherwise,             m = max(|cx[i,j,k]|, |cy[i,j,k]|)
+ * (the reference's commented draft takes one more plain level; this is the Fortran's split).  Every value is >= 0, so the
+ * maximum is taken on the bit patterns as unsigned 64-bit integers -- a fold over the workgroup, then one integer atomic maximum
+ * per workgroup and level: exact, bitwise the same for every order and launch shape.  A NaN (its sign cleared) orders above
+ * infinity: a NaN of cx, cy or sin_sg5 in the window reaches cmax[k].  No workspace.  Nothing outside cmax[0 .. nk - 1] is
+ * written; nothing outside the two fields' and the plane's compute windows is read.
+ * PACE_ERR_ARG: a NULL argument, cmax the same array as an input.
+ *
+ * pace_tracer_subcycles: ONE launch for any number of tiles (1 .. PACE_TRACER_MAX_TILES).  cmax_tables: HOST array of ntiles
+ * device pointers, each to a tile's nk doubles; out: nk + 2 int32 on the device.
+ *   out[2 + k] = (int)(1.0 + c),  c = the maximum over the tiles of cmax[k], the sum and the truncation in double exactly so
+ *                (c = nextafter(1, 0) gives 2: the sum rounds to 2.0);
+ *                0 if c is a NaN, infinite, below zero, or the result would exceed max_subcycles
+ *   out[0]     = the largest entry,   out[1] = the number of levels set to 0
+ * PACE_ERR_ARG: NULL cmax_tables, entry or out, ntiles out of range, nk outside 1 .. PACE_TRACER_MAX_LEVELS, max_subcycles
+ * outside 1 .. PACE_TRACER_MAX_SUBCYCLES, out the same array as a table.
+ *
+ * pace_tracer_divide_fluxes_levels: pace_tracer_divide_fluxes with frac = 1.0 / ksplt[k] read per level from the device (ksplt:
+ * nk int32), over the same planes -- the whole storage plane of the levels 0 .. nk - 1.  A level with ksplt[k] == 1 (or a refused
+ * one, 0) is neither read nor written.
+ *
+ * pace_apply_mass_flux_levels, pace_apply_tracer_flux_levels, pace_swap_dp_levels: the three compute-domain stencils above -- the
+ * same expressions, casts included -- on the levels with ksplt[k] >= min_subcycles only; the test is uniform over a workgroup
+ * and precedes every field access.
+ * PACE_ERR_ARG of the four: a NULL argument, min_subcycles < 1, ksplt or an input the same array as an output, dp1 == dp2 of
+ * the swap.
+ *
+ * The transport has no such form: a level's transport depends on that level alone and levels are the slowest storage axis, so a
+ * run of consecutive levels k0 .. k0 + nlev - 1 is pace_fvtp2d with every field pointer advanced by k0 * sk elements. */
+#define PACE_TRACER_MAX_TILES 64
+#define PACE_TRACER_MAX_LEVELS 4096
+#define PACE_TRACER_MAX_SUBCYCLES 1024
+int pace_tracer_cmax(const pace_geom_t* geom, const pace_real_t* cx, const pace_real_t* cy, const pace_real_t* sin_sg5,
+                     double* cmax, void* stream);
+int pace_tracer_subcycles(const double* const* cmax_tables, int ntiles, int nk, int max_subcycles, int32_t* out, void* stream);
+int pace_tracer_divide_fluxes_levels(const pace_geom_t* geom, pace_real_t* cxd, pace_real_t* xfx, pace_real_t* mfxd,
+                                     pace_real_t* cyd, pace_real_t* yfx, pace_real_t* mfyd, const int32_t* ksplt, void* stream);
+int pace_apply_mass_flux_levels(const pace_geom_t* geom, const pace_metrics_t* met, const pace_real_t* dp1,
+                                const pace_real_t* x_mass_flux, const pace_real_t* y_mass_flux, pace_real_t* dp2,
+                                const int32_t* ksplt, int min_subcycles, void* stream);
+int pace_apply_tracer_flux_levels(const pace_geom_t* geom, const pace_metrics_t* met, pace_real_t* q, const pace_real_t* dp1,
+                                  const pace_real_t* fx, const pace_real_t* fy, const pace_real_t* dp2, const int32_t* ksplt,
+                                  int min_subcycles, void* stream);
+int pace_swap_dp_levels(const pace_geom_t* geom, pace_real_t* dp1, pace_real_t* dp2, const int32_t* ksplt, int min_subcycles,
+                        void* stream);
+
 /* ---- MapSingle (Fortran map_single / map1_ppm / map_scalar): fv3core/pace/fv3core/stencils/map_single.py:96-200 with
  * RemapProfile (cs_profile), remap_profile.py:566-681.  q1 is remapped in place from the nk layers bounded by the
  * interface values pe1 to those bounded by pe2 (both nk + 1 levels; pressure or log-pressure -- remapping.py:587-627).

@@ -214,6 +214,8 @@ class HeldSuarezConfig(C.Structure):  # include/pace_hip.h pace_held_suarez_conf
 
 
 ENERGY_WORDS, ENERGY_MAX_TILES = 10, 64  # include/pace_hip.h PACE_ENERGY_WORDS, PACE_ENERGY_MAX_TILES
+# include/pace_hip.h PACE_TRACER_MAX_TILES, PACE_TRACER_MAX_LEVELS, PACE_TRACER_MAX_SUBCYCLES
+TRACER_MAX_TILES, TRACER_MAX_LEVELS, TRACER_MAX_SUBCYCLES = 64, 4096, 1024
 
 
 class PaceError(RuntimeError):
@@ -284,6 +286,12 @@ _PROTOS = {
     "pace_apply_mass_flux": (C.c_int, [_P(Geom), _P(Metrics)] + [c_dp] * 4 + [C.c_void_p]),
     "pace_apply_tracer_flux": (C.c_int, [_P(Geom), _P(Metrics)] + [c_dp] * 5 + [C.c_void_p]),
     "pace_swap_dp": (C.c_int, [_P(Geom), c_dp, c_dp, C.c_void_p]),
+    "pace_tracer_cmax": (C.c_int, [_P(Geom)] + [c_dp] * 4 + [C.c_void_p]),
+    "pace_tracer_subcycles": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pace_tracer_divide_fluxes_levels": (C.c_int, [_P(Geom)] + [c_dp] * 6 + [C.c_void_p, C.c_void_p]),
+    "pace_apply_mass_flux_levels": (C.c_int, [_P(Geom), _P(Metrics)] + [c_dp] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "pace_apply_tracer_flux_levels": (C.c_int, [_P(Geom), _P(Metrics)] + [c_dp] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "pace_swap_dp_levels": (C.c_int, [_P(Geom), c_dp, c_dp, C.c_void_p, C.c_int, C.c_void_p]),
     "pace_map_single_workspace_bytes": (C.c_int64, [_P(Geom)]),
     "pace_map_single": (C.c_int, [_P(Geom), c_dp, c_dp, c_dp, c_dp, c_dp, C.c_double] + [C.c_int] * 4 + [C.c_void_p]),
     "pace_mapn_tracer_workspace_bytes": (C.c_int64, [_P(Geom), C.c_int]),

@@ -451,6 +451,54 @@ int pace_swap_dp(const pace_geom_t* geom, real* dp1, real* dp2, void* stream) {
   return launch_swap_dp(make_geo(geom), dp1, dp2, S(stream));
 }
 
+int pace_tracer_cmax(const pace_geom_t* geom, const real* cx, const real* cy, const real* sin_sg5, double* cmax, void* stream) {
+  NEED(geom && cx && cy && sin_sg5 && cmax);
+  const void* const out = (const void*)cmax;
+  if (out == (const void*)cx || out == (const void*)cy || out == (const void*)sin_sg5) return PACE_ERR_ARG;
+  return launch_tracer_cmax(make_geo(geom), cx, cy, sin_sg5, cmax, S(stream));
+}
+
+int pace_tracer_subcycles(const double* const* cmax_tables, int ntiles, int nk, int max_subcycles, int32_t* out, void* stream) {
+  if (!cmax_tables || !out || ntiles < 1 || ntiles > PACE_TRACER_MAX_TILES || nk < 1 || nk > PACE_TRACER_MAX_LEVELS ||
+      max_subcycles < 1 || max_subcycles > PACE_TRACER_MAX_SUBCYCLES)
+    return PACE_ERR_ARG;
+  for (int t = 0; t < ntiles; ++t)
+    if (!cmax_tables[t] || (const void*)cmax_tables[t] == (const void*)out) return PACE_ERR_ARG;
+  (void)hipGetLastError();
+  return launch_tracer_subcycles(cmax_tables, ntiles, nk, max_subcycles, out, S(stream));
+}
+
+int pace_tracer_divide_fluxes_levels(const pace_geom_t* geom, real* cxd, real* xfx, real* mfxd, real* cyd, real* yfx, real* mfyd,
+                                     const int32_t* ksplt, void* stream) {
+  NEED(geom && cxd && xfx && mfxd && cyd && yfx && mfyd && ksplt);
+  for (const real* p : {cxd, xfx, mfxd, cyd, yfx, mfyd})
+    if ((const void*)p == (const void*)ksplt) return PACE_ERR_ARG;
+  return launch_tracer_divide_levels(make_geo(geom), cxd, xfx, mfxd, cyd, yfx, mfyd, ksplt, S(stream));
+}
+
+int pace_apply_mass_flux_levels(const pace_geom_t* geom, const pace_metrics_t* met, const real* dp1, const real* x_mass_flux,
+                                const real* y_mass_flux, real* dp2, const int32_t* ksplt, int min_subcycles, void* stream) {
+  NEED(geom && met && dp1 && x_mass_flux && y_mass_flux && dp2 && ksplt);
+  if (min_subcycles < 1) return PACE_ERR_ARG;
+  if (dp2 == dp1 || dp2 == x_mass_flux || dp2 == y_mass_flux || (const void*)dp2 == (const void*)ksplt) return PACE_ERR_ARG;
+  return launch_apply_mass_flux_levels(make_geo(geom), *met, dp1, x_mass_flux, y_mass_flux, dp2, ksplt, min_subcycles, S(stream));
+}
+
+int pace_apply_tracer_flux_levels(const pace_geom_t* geom, const pace_metrics_t* met, real* q, const real* dp1, const real* fx,
+                                  const real* fy, const real* dp2, const int32_t* ksplt, int min_subcycles, void* stream) {
+  NEED(geom && met && q && dp1 && fx && fy && dp2 && ksplt);
+  if (min_subcycles < 1) return PACE_ERR_ARG;
+  if (q == dp1 || q == fx || q == fy || q == dp2 || (const void*)q == (const void*)ksplt) return PACE_ERR_ARG;
+  return launch_apply_tracer_flux_levels(make_geo(geom), *met, q, dp1, fx, fy, dp2, ksplt, min_subcycles, S(stream));
+}
+
+int pace_swap_dp_levels(const pace_geom_t* geom, real* dp1, real* dp2, const int32_t* ksplt, int min_subcycles, void* stream) {
+  NEED(geom && dp1 && dp2 && ksplt);
+  if (min_subcycles < 1) return PACE_ERR_ARG;
+  if (dp1 == dp2 || (const void*)dp1 == (const void*)ksplt || (const void*)dp2 == (const void*)ksplt) return PACE_ERR_ARG;
+  return launch_swap_dp_levels(make_geo(geom), dp1, dp2, ksplt, min_subcycles, S(stream));
+}
+
 static int halo_check(const pace_geom_t* geom, const pace_halo_desc_t* d, int n) {
   const int ni = geom->n + 7;
   for (int t = 0; t < n; ++t) {

@@ -227,6 +227,15 @@ int launch_apply_mass_flux(const Geo& g, const Met& m, const real* dp1, const re
                            hipStream_t st);
 int launch_apply_tracer_flux(const Geo& g, const Met& m, real* q, const real* dp1, const real* fx, const real* fy,
                              const real* dp2, hipStream_t st);
+int launch_tracer_cmax(const Geo& g, const real* cx, const real* cy, const real* sin_sg5, double* cmax, hipStream_t st);
+int launch_tracer_subcycles(const double* const* cmax, int ntiles, int nk, int max_subcycles, int32_t* out, hipStream_t st);
+int launch_tracer_divide_levels(const Geo& g, real* cxd, real* xfx, real* mfxd, real* cyd, real* yfx, real* mfyd,
+                                const int32_t* ksplt, hipStream_t st);
+int launch_apply_mass_flux_levels(const Geo& g, const Met& m, const real* dp1, const real* mfx, const real* mfy, real* dp2,
+                                  const int32_t* ksplt, int min_subcycles, hipStream_t st);
+int launch_apply_tracer_flux_levels(const Geo& g, const Met& m, real* q, const real* dp1, const real* fx, const real* fy,
+                                    const real* dp2, const int32_t* ksplt, int min_subcycles, hipStream_t st);
+int launch_swap_dp_levels(const Geo& g, real* dp1, real* dp2, const int32_t* ksplt, int min_subcycles, hipStream_t st);
 int64_t map_single_workspace_bytes(const Geo& g, int nq);
 int launch_map_fields(const Geo& g, void* ws, real* const* q, int nq, const real* pe1, const real* pe2, const real* qs,
                       double qmin, int kord, int iv, int xstag, int ystag, hipStream_t st);

@@ -155,6 +155,9 @@ class DynamicalCoreConfig:
     tau_v2l: float = 90.0
     # the dry convective adjustment's time scale in seconds (util/pace/util/namelist.py: fv_sg_adj = -1, off)
     fv_sg_adj: int = -1
+    # an extension: the tracer advection sub-cycles level k int(1 + cmax(k)) times, cmax(k) the level's largest Courant number
+    # over the globe, as the Fortran tracer_2d_1L does; false: the reference's fixed three sub-cycles on every level
+    tracer_courant_subcycling: bool = False
     # fields of the reference's flat configuration that nothing here reads: carried so that its files load and round-trip
     # (defaults: util/pace/util/namelist.py NamelistDefaults)
     ntiles: int = 6

@@ -58,7 +58,8 @@ class DynamicalCore(Operator):
         self._dp_initial = temporaries["dp1"]
         self._cvm = temporaries["cvm"]
         self.tracer_advection = tracer_2d_1l.TracerAdvection(stencil_factory, quantity_factory, tracer_transport, grid_data, comm,
-                                                             self.tracers)
+                                                             self.tracers,
+                                                             courant_subcycling=config.tracer_courant_subcycling)
         self._ak = quantity_factory.zeros([Z_INTERFACE_DIM], units="Pa")
         self._bk = quantity_factory.zeros([Z_INTERFACE_DIM], units="")
         self._ak.set(grid_data.ak)
@@ -102,6 +103,15 @@ class DynamicalCore(Operator):
         if self._energy_fixer is None:
             raise RuntimeError("energy_fixer_diagnostics: the dynamical core runs with consv_te = 0")
         return self._energy_fixer.diagnostics()
+
+    def tracer_subcycles(self):
+        """The sub-cycles every level took in the last tracer advection (numpy int32, one per level), with
+        tracer_courant_subcycling on: int(1 + cmax(k)) of the level's largest Courant number over the globe."""
+        if not self.config.tracer_courant_subcycling:
+            raise RuntimeError("tracer_subcycles: the dynamical core runs with tracer_courant_subcycling = false")
+        if self.tracer_advection.subcycles is None:
+            raise RuntimeError("tracer_subcycles: no step has run yet")
+        return self.tracer_advection.subcycles.copy()
 
     # ---- the reference's checkpoint call sites (fv_dynamics.py:321-423): same names, same variables ----
     def _checkpoint_fvdynamics(self, state, tag: str):

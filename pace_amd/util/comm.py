@@ -87,6 +87,15 @@ class TorchDistComm:
         self._dist.all_reduce(words, op=self._dist.ReduceOp.SUM, group=self._group)
         return finalize([words])
 
+    def allreduce_level_max(self, cmax, finalize, stream=None):
+        """The tracer advection's Courant numbers per level (pace_amd/fv3core/stencils/tracer_2d_1l.py): `cmax`, this rank's
+        float64 tensor of one maximum per level, becomes the maximum over the ranks by ONE all_reduce(MAX) in place -- on the
+        device under "nccl" -- and ``finalize([cmax])`` makes this rank's pace_tracer_subcycles launch and its one transfer.
+        The reduction runs on the bit patterns (the same memory viewed as int64): every value is >= 0, so the patterns order
+        like the values, and a NaN, which a floating-point MAX may drop, is the largest of them.  -> what finalize returned."""
+        self._dist.all_reduce(cmax.view(torch.int64), op=self._dist.ReduceOp.MAX, group=self._group)
+        return finalize([cmax])
+
 
 class NullComm:
     """util/pace/util/null_comm.py:15-80: the rank of a communicator that has no peers -- what it "receives" is a fill value
@@ -126,6 +135,10 @@ class NullComm:
         """The rank's own tile only: a rank alone cannot know the sum over the globe, so the "global" sum of the energy fixer
         is this tile's.  It is what lets one tile's LagrangianToEulerian run alone with consv_te > 0."""
         return finalize([words])
+
+    def allreduce_level_max(self, cmax, finalize, stream=None):
+        """The rank's own tile only, as allreduce_fixed_point: one tile's TracerAdvection sub-cycles by its own Courant numbers."""
+        return finalize([cmax])
 
 
 class LoopbackComm(NullComm):
@@ -233,6 +246,19 @@ class ThreadComm:
         words.copy_(torch.from_numpy(total.view(np.int64).copy()))
         return finalize([words])
 
+    def allreduce_level_max(self, cmax, finalize, stream=None):
+        """The Courant numbers per level through the host, as allreduce_sum_u64: the maximum over the tiles of the bit patterns
+        (values >= 0 order like their patterns; a NaN is the largest) is written back into `cmax`, and every rank makes its own
+        pace_tracer_subcycles launch and transfer."""
+        import numpy as np
+
+        def last(posts):
+            return np.maximum.reduce([posts[r] for r in sorted(posts)])
+
+        total = self.rendezvous("allreduce_level_max", cmax.cpu().numpy().view(np.uint64).copy(), last)
+        cmax.copy_(torch.from_numpy(total.view(np.float64).copy()))
+        return finalize([cmax])
+
     def rendezvous(self, tag, payload, last):
         """The collective of gather and scatter (pace_amd/util/gather.py): every rank posts `payload` under `tag`; the last one
         to arrive runs ``last({rank: payload})`` -- for DeviceCubeComm that is the one launch for the whole cube -- and every
@@ -299,6 +325,21 @@ class DeviceCubeComm(ThreadComm):
             return finalize([posts[r][0] for r in order])
 
         return self.rendezvous("allreduce_fixed_point", (words, getattr(stream, "value", stream)), last)
+
+    def allreduce_level_max(self, cmax, finalize, stream=None):
+        """The Courant numbers per level with ONE launch and ONE transfer for the cube: a rendezvous, and the last rank to
+        arrive makes the pace_tracer_subcycles launch over the six tiles' buffers in tile order and the transfer of its nk + 2
+        integers.  Every rank returns the same host array.  One stream must order the tiles' launches, as for the fixed-point
+        sum."""
+        def last(posts):
+            order = sorted(posts)
+            streams = [posts[r][1] for r in order]
+            if len(set(streams)) != 1:
+                raise RuntimeError(f"the tiles of a fused level maximum launched on different streams ({streams}): the one "
+                                   "finalising launch is ordered behind one stream only")
+            return finalize([posts[r][0] for r in order])
+
+        return self.rendezvous("allreduce_level_max", (cmax, getattr(stream, "value", stream)), last)
 
     def halo_post(self, tag, payload):
         """Post this rank's part of the next update under `tag`.  Returns (ticket, posts): posts is None unless this rank is

@@ -318,6 +318,7 @@ def _angles(g, n):
     for k in range(1, 5):
         g[f"cos_sg{k}"], g[f"sin_sg{k}"] = pad(cs[:, :, k - 1]), pad(sn[:, :, k - 1])
     sin_sg5 = sn[:, :, 4]
+    g["sin_sg5"] = pad(sin_sg5)  # the cell-centre sine: the widened Courant number of the tracer sub-cycling (Fortran tracer_2d_1L)
     g["cosa"], g["sina"] = cosa, sina
     g["cosa_u"], g["sina_u"], g["rsin_u"] = pad(cosa_u), pad(sina_u), pad(rsin_u)
     g["cosa_v"], g["sina_v"], g["rsin_v"] = pad(cosa_v), pad(sina_v), pad(rsin_v)

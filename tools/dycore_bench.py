@@ -2,6 +2,7 @@
 thread per tile, halo exchanges through ThreadComm), synthetic balanced state, fp64.
 
     python tools/dycore_bench.py [--n 192] [--nz 79] [--n-split 4] [--steps 2] [--single] [--sat-adj] [--sg-adj]
+                                 [--tracer-subcycling {fixed,courant}]
 
 Prints the wall time per step for all six tiles (the device is shared, so per tile = / 6) and the split between the
 acoustic loop, the tracer advection, the remapping and the rest, from synchronising timers.
@@ -59,6 +60,10 @@ def main():
     ap.add_argument("--comm", default="thread", choices=("thread", "cube"),
                     help="six tiles: ThreadComm (pack, device-side copies, unpack per tile) or DeviceCubeComm (run_cube: one "
                          "pace_halo_cube launch per halo update for the whole cube)")
+    ap.add_argument("--tracer-subcycling", default="fixed", choices=("fixed", "courant"),
+                    help="the tracer advection's sub-cycles: the reference's three on every level, or int(1 + cmax(k)) on level k from "
+                         "the level's largest Courant number over the globe (DynamicalCoreConfig.tracer_courant_subcycling); the "
+                         "counts of the last step are printed")
     args = ap.parse_args()
     if os.environ.get("PACE_BENCH_TRACE"):
         import faulthandler
@@ -75,6 +80,9 @@ def main():
     lib = _lib.load(args.precision)
     n, nz = args.n, args.nz
     metrics = synthetic.tile_metrics(n, nz)
+    courant = args.tracer_subcycling == "courant"
+    if courant:  # the synthetic tile has no cell-centre sine: the mean of its four face sines stands in
+        metrics = dict(metrics, sin_sg5=np.minimum(0.25 * sum(metrics[f"sin_sg{m}"] for m in (1, 2, 3, 4)), 1.0))
     s = synthetic.acoustic_state(metrics, n, nz)
     dt_atmos = float(s["dt"]) * args.n_split
     results = {}
@@ -101,7 +109,7 @@ def main():
         state = DycoreState.init_from_numpy_arrays(arrays, env.qf)
         config = DynamicalCoreConfig(npx=n + 1, npy=n + 1, npz=nz, dt_atmos=dt_atmos, k_split=1, n_split=args.n_split,
                                      acoustic_dynamics=acoustic_config(args.n_split), do_sat_adj=args.sat_adj,
-                                     fv_sg_adj=600 if args.sg_adj else -1)
+                                     fv_sg_adj=600 if args.sg_adj else -1, tracer_courant_subcycling=courant)
         core = DynamicalCore(cube, env.grid_data, env.stencil_factory, env.qf, env.damping, config, state.phis, state,
                              datetime.timedelta(seconds=dt_atmos))
         to_physics = None
@@ -135,7 +143,8 @@ def main():
         comm.barrier()
         wall = time.perf_counter() - t0
         with lock:
-            results[tile] = (wall, dict(timer.t), float(np.isnan(state.w.numpy()).mean()), float(np.isnan(state.pt.numpy()).mean()))
+            results[tile] = (wall, dict(timer.t), float(np.isnan(state.w.numpy()).mean()), float(np.isnan(state.pt.numpy()).mean()),
+                             core.tracer_subcycles() if courant else None)
 
     if args.single:
         program(LoopbackComm(rank=0, total_ranks=6))
@@ -158,6 +167,12 @@ def main():
     for k, v in t.items():
         print(f"  {k:18s} {1e3 * v / args.steps:9.2f} ms of tile 0's wall time (threads interleave on the device) {100 * v / tot:5.1f} %")
     print(f"  NaN fraction after the run: w {results[0][2]:.2e}, pt {results[0][3]:.2e}")
+    if courant:
+        counts = results[0][4]
+        print(f"  tracer sub-cycles of the last step (--tracer-subcycling courant): " +
+              ", ".join(f"{int((counts == v).sum())} levels x {int(v)}" for v in np.unique(counts)) + "; fixed: every level x 3")
+    else:
+        print("  tracer sub-cycles (--tracer-subcycling fixed): every level x 3")
 
 
 if __name__ == "__main__":

@@ -25,6 +25,10 @@
     python tools/kbench.py --only energy_fixer      the total-energy fixer of one tile (consv_te > 0): pace_energy_columns in both
                                                     modes and pace_energy_finalize against a torch restatement on the device, the
                                                     same way, with each launch alone and its bandwidth
+    python tools/kbench.py --only tracer_subcycle   TracerAdvection of seven tracers on one tile of the baroclinic state behind a
+                                                    lone-rank LoopbackComm: the reference's three sub-cycles on every level against
+                                                    the Courant-number sub-cycling, alternating, medians; pace_tracer_cmax alone
+                                                    with its bandwidth, and the finalising launch with its transfer alone
     python tools/kbench.py --only cube_gather       one output step (fourteen variables as float32 on the host) of six C96 and six
                                                     C192 tiles on this device: one pace_cube_gather launch and one transfer
                                                     against six pace_diag_pack passes, one per tile, with a transfer each
@@ -103,6 +107,9 @@ def main():
         return
     if args.only == "energy_fixer":  # (its own fields)
         energy_fixer_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "tracer_subcycle":  # (its own fields)
+        tracer_subcycle_bench(lib, n, nz, args.reps)
         return
     m = synthetic.tile_metrics(n, nz)
     s = synthetic.acoustic_state(m, n, nz)
@@ -1460,6 +1467,88 @@ def energy_fixer_bench(lib, n, nz, reps):
         print(f"  {name:9s} hip {med['hip']:8.3f} ms (min {min(times['hip']):.3f})   torch {med['torch']:8.3f} ms (min "
               f"{min(times['torch']):.3f})   ratio torch / hip {med['torch'] / med['hip']:.2f}; in device events: median "
               f"{launch * 1e3:.1f} us (min {min(events) * 1e3:.1f}){rate}")
+
+
+def tracer_subcycle_bench(lib, n, nz, reps, device="cuda"):
+    """TracerAdvection of seven tracers on tile 0 of the C<n> x <nz> baroclinic state (the driver's initialisation on the generated
+    grid, a lone-rank LoopbackComm; the mass fluxes and Courant numbers are what ONE step_dynamics of that state accumulated):
+    the reference's fixed three sub-cycles against courant_subcycling=True.  Every run starts from the same fields (restored
+    outside the timed region), both are timed with the host clock from an idle device to the end of a synchronisation,
+    alternating, medians.  Then pace_tracer_cmax alone in device events, with its bandwidth over cx + cy read once, and the
+    finalising launch with the transfer and its synchronisation alone (host clock)."""
+    import ctypes as C
+    import time
+
+    import yaml
+
+    from pace_amd.driver import Driver, DriverConfig
+    from pace_amd.fv3core.stencils.fillz import tracer_variables
+    from pace_amd.fv3core.stencils.tracer_2d_1l import TracerAdvection
+    from pace_amd.util import CubedSphereCommunicator, LoopbackComm
+
+    with open(os.path.join(ROOT, "tests", "golden", "driver_baroclinic_c12.yaml")) as f:
+        settings = yaml.safe_load(f)
+    # (the dynamical core alone: the physics, which the float32 library refuses, never runs here)
+    settings.update(nx_tile=n, nz=nz, diagnostics_config={}, stencil_config={}, safety_check_frequency=0, disable_step_physics=True)
+    driver = Driver(DriverConfig.from_dict(settings), comm=LoopbackComm(rank=0, total_ranks=6), lib=lib, device=device)
+    core, state = driver.dycore, driver.state.dycore_state
+    core.step_dynamics(state)
+    torch.cuda.synchronize()
+    tracers = {name: core.tracers[name] for name in tracer_variables[:7]}
+    fields = dict(dp1=core._dp_initial, mfxd=state.mfxd, mfyd=state.mfyd, cxd=state.cxd, cyd=state.cyd, **tracers)
+    saved = {name: q._base.clone() for name, q in fields.items()}
+    cube = CubedSphereCommunicator(LoopbackComm(rank=0, total_ranks=6), device=device, lib=lib)
+    transport = core.tracer_advection.finite_volume_transport
+    make = lambda **kw: TracerAdvection(driver.stencil_factory, driver.quantity_factory, transport, driver.state.grid_data, cube,  # noqa: E731
+                                        tracers, **kw)
+    modes = {"fixed": make(), "courant": make(courant_subcycling=True)}
+
+    def restore():
+        for name, q in fields.items():
+            q._base.copy_(saved[name])
+
+    def run(mode):
+        modes[mode](tracers, fields["dp1"], fields["mfxd"], fields["mfyd"], fields["cxd"], fields["cyd"])
+
+    times = {mode: [] for mode in modes}
+    for rep in range(reps + 3):
+        for mode in modes:
+            restore()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(mode)
+            torch.cuda.synchronize()
+            if rep >= 3:
+                times[mode].append((time.perf_counter() - t0) * 1e3)
+    restore()
+    adv = modes["courant"]
+    counts = adv.subcycles
+    cmax = adv._cmax.cpu().numpy()
+    med = {mode: float(np.median(x)) for mode, x in times.items()}
+    print(f"tracer_subcycle C{n} x {nz}, float{8 * lib.real_bytes} fields, one tile, seven tracers; medians of {reps} alternating runs")
+    print(f"  cmax over the tile: {cmax.min():.4f} .. {cmax.max():.4f}; sub-cycles: " +
+          ", ".join(f"{int((counts == v).sum())} levels x {int(v)}" for v in np.unique(counts)))
+    print(f"  fixed (3 sub-cycles) {med['fixed']:8.3f} ms (min {min(times['fixed']):.3f})   courant {med['courant']:8.3f} ms (min "
+          f"{min(times['courant']):.3f})   ratio fixed / courant {med['fixed'] / med['courant']:.2f}")
+
+    def launch():
+        adv.call("pace_tracer_cmax", fields["cxd"].ptr, fields["cyd"].ptr, driver.state.grid_data.sin_sg5.ptr,
+                 C.c_void_p(adv._cmax.data_ptr()), adv.stream())
+
+    events = times_hip_calibrate(launch, reps)
+    alone = float(np.median(events))
+    moved = 2 * n * n * nz * lib.real_bytes
+    print(f"  pace_tracer_cmax alone, device events: median {alone * 1e3:.1f} us (min {min(events) * 1e3:.1f}) = "
+          f"{moved / (alone * 1e-3) / 1e12:.2f} TB/s over {moved / 1e6:.1f} MB (cx + cy)")
+    host = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        adv._subcycle_counts()
+        host.append((time.perf_counter() - t0) * 1e6)
+    print(f"  pace_tracer_subcycles + the transfer of {nz + 2} integers + its synchronisation, host clock: median "
+          f"{float(np.median(host)):.1f} us (min {min(host):.1f})")
+    driver.cleanup()
 
 
 def times_hip_calibrate(fn, reps=10):
