@@ -3,7 +3,7 @@
 # tests/emu/README.md).
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC := pace_amd/csrc
-SRCS := $(CSRC)/capi.hip $(CSRC)/k_fxadv.hip $(CSRC)/k_fvtp2d.hip $(CSRC)/k_fvt.hip $(CSRC)/k_fvt16.hip $(CSRC)/k_delnflux.hip $(CSRC)/k_dsw.hip $(CSRC)/k_riem3.hip $(CSRC)/k_riem3f.hip $(CSRC)/k_sim1.hip $(CSRC)/k_ppm.hip $(CSRC)/k_csw.hip $(CSRC)/k_acoustic.hip $(CSRC)/k_halo.hip $(CSRC)/k_tracer.hip $(CSRC)/k_remap.hip $(CSRC)/k_l2e.hip $(CSRC)/k_satadj.hip $(CSRC)/k_subgridz.hip $(CSRC)/k_updphys.hip $(CSRC)/k_microphys.hip $(CSRC)/k_physics.hip $(CSRC)/k_dycore.hip $(CSRC)/k_driver.hip $(CSRC)/k_diag.hip $(CSRC)/k_plev.hip $(CSRC)/k_gather.hip $(CSRC)/k_regrid.hip $(CSRC)/k_state.hip $(CSRC)/k_restart.hip $(CSRC)/k_ckpt.hip $(CSRC)/k_nudge.hip $(CSRC)/k_heldsuarez.hip $(CSRC)/k_energy.hip $(CSRC)/k_stencils.hip
+SRCS := $(CSRC)/capi.hip $(CSRC)/k_fxadv.hip $(CSRC)/k_fvtp2d.hip $(CSRC)/k_fvt.hip $(CSRC)/k_fvt16.hip $(CSRC)/k_delnflux.hip $(CSRC)/k_dsw.hip $(CSRC)/k_riem3.hip $(CSRC)/k_riem3f.hip $(CSRC)/k_sim1.hip $(CSRC)/k_ppm.hip $(CSRC)/k_csw.hip $(CSRC)/k_acoustic.hip $(CSRC)/k_halo.hip $(CSRC)/k_tracer.hip $(CSRC)/k_remap.hip $(CSRC)/k_l2e.hip $(CSRC)/k_satadj.hip $(CSRC)/k_subgridz.hip $(CSRC)/k_updphys.hip $(CSRC)/k_microphys.hip $(CSRC)/k_physics.hip $(CSRC)/k_dycore.hip $(CSRC)/k_driver.hip $(CSRC)/k_diag.hip $(CSRC)/k_plev.hip $(CSRC)/k_gather.hip $(CSRC)/k_regrid.hip $(CSRC)/k_state.hip $(CSRC)/k_restart.hip $(CSRC)/k_ckpt.hip $(CSRC)/k_nudge.hip $(CSRC)/k_heldsuarez.hip $(CSRC)/k_rayleigh.hip $(CSRC)/k_energy.hip $(CSRC)/k_stencils.hip
 HDRS := $(CSRC)/k_fvt.hip $(CSRC)/common.h $(CSRC)/kernels.h $(CSRC)/wgmap.h $(CSRC)/pack_table.h $(CSRC)/thermo.h $(CSRC)/lean_math.h $(CSRC)/delnflux_core.h $(CSRC)/fvt_core.h include/pace_hip.h
 # -ffp-contract=off: no FMA contraction, so horizontal stencils are bit-comparable with the numpy oracle.
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function

@@ -965,6 +965,28 @@ int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, 
                  const pace_real_t* v, const pace_real_t* a11, const pace_real_t* a12, const pace_real_t* a21,
                  const pace_real_t* a22, pace_real_t* ua, pace_real_t* va, void* stream);
 
+/* ---- Rayleigh_Super (the Fortran fv_dynamics.F90, rf_fast = .false., tau > 0; the reference has none): once per dycore step the
+ * sponge levels' u, v and w are scaled by a per-level factor and, with conserve, the kinetic energy lost is added to pt as heat.
+ * Non-hydrostatic.  met (dx, dy) and a11 .. a22 are what pace_c2l_ord takes; u, v, w, pt share the storage geometry of geom; pt is
+ * the temperature.  factor: HOST array of nk doubles, each in (0, 1]: f[k] = 1 / (1 + rf[k]) on the leading damped levels, exactly
+ * 1.0 from the first undamped level on; kmax = the number of leading levels with f[k] < 1.  On the levels k < kmax, in double on the
+ * stored values (the float32 library widens first), without FMA and without a reciprocal, every input read before it is written:
+ *   cells (i, j) of the compute domain -- origin (3, 3), extent (n, n):
+ *     u1 = 2.0 * (u[i,j] * dx[i,j] + u[i,j+1] * dx[i,j+1]) / (dx[i,j] + dx[i,j+1])
+ *     v1 = 2.0 * (v[i,j] * dy[i,j] + v[i+1,j] * dy[i+1,j]) / (dy[i,j] + dy[i+1,j])
+ *     ua = a11 * u1 + a12 * v1,  va = a21 * u1 + a22 * v1                             (pace_c2l_ord, order 2, bit for bit)
+ *     conserve:  pt[i,j,k] = (pace_real_t)(pt + ((0.5 * ((ua * ua + va * va) + w * w)) * (1.0 - f[k] * f[k])) * rcv)
+ *     w[i,j,k] = (pace_real_t)(f[k] * w)
+ *   u[i,j,k] = (pace_real_t)(f[k] * u) on (n, n + 1) points,  v[i,j,k] = (pace_real_t)(f[k] * v) on (n + 1, n) points
+ * conserve = 1: TWO ordered launches (heat and w from the old winds; then the winds); conserve = 0: one; kmax = 0: none.  No
+ * atomics, no workspace, no host synchronisation.  Nothing else is written (not the halo, not level nk, not the row padding,
+ * no level >= kmax); u, v, w, pt and the six metric planes are read only on the compute domain plus the staggered row / column.
+ * PACE_ERR_ARG, with nothing written: a NULL argument, conserve other than 0 / 1, with conserve an rcv that is not finite, a
+ * factor that is NaN, <= 0 or > 1, a damped level after an undamped one, any two of u, v, w, pt the same array. */
+int pace_rayleigh_super(const pace_geom_t* geom, const pace_metrics_t* met, const pace_real_t* a11, const pace_real_t* a12,
+                        const pace_real_t* a21, const pace_real_t* a22, pace_real_t* u, pace_real_t* v, pace_real_t* w,
+                        pace_real_t* pt, const double* factor, double rcv, int conserve, void* stream);
+
 /* Per-stencil device implementations behind FrozenStencil (dsl/pace/dsl/stencil.py:395-434) for gtscript definitions that the
  * reference's Translate tests launch as stencils of their own: `id` selects the definition, `fields` are its field arguments in
  * the definition's order (2-D metric arguments come from `met`, K-fields are device arrays of nk + 1 entries), `scalars` its

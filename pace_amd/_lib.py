@@ -337,6 +337,7 @@ _PROTOS = {
     "pace_ckpt_validate": (C.c_int, [_P(CkptItem), C.c_int, C.c_void_p, c_dp, C.c_void_p]),
     "pace_nudge": (C.c_int, [_P(Geom), _P(NudgeItem), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p]),
     "pace_held_suarez": (C.c_int, [_P(Geom), _P(HeldSuarezConfig)] + [c_dp] * 10 + [C.c_void_p]),
+    "pace_rayleigh_super": (C.c_int, [_P(Geom), _P(Metrics)] + [c_dp] * 8 + [_P(C.c_double), C.c_double, C.c_int, C.c_void_p]),
     "pace_c2l_ord": (C.c_int, [_P(Geom), _P(Metrics), C.c_int] + [c_dp] * 8 + [C.c_void_p]),
     "pace_stencil": (C.c_int, [_P(Geom), _P(Metrics), C.c_int, _P(C.c_void_p), C.c_int, _P(C.c_double), C.c_int, _P(C.c_int), _P(C.c_int),
                                C.c_void_p]),

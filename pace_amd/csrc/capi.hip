@@ -939,6 +939,28 @@ int pace_held_suarez(const pace_geom_t* geom, const pace_held_suarez_config_t* c
   return launch_held_suarez(make_geo(geom), *cfg, pe, ua, va, pt, sin2lat, cos2lat, u_dt, v_dt, pt_dt, teq, S(stream));
 }
 
+int pace_rayleigh_super(const pace_geom_t* geom, const pace_metrics_t* met, const real* a11, const real* a12, const real* a21,
+                        const real* a22, real* u, real* v, real* w, real* pt, const double* factor, double rcv, int conserve,
+                        void* stream) {
+  NEED(geom && met && a11 && a12 && a21 && a22 && u && v && w && pt && factor);
+  if (!met->dx || !met->dy) return PACE_ERR_ARG;
+  if (conserve != 0 && conserve != 1) return PACE_ERR_ARG;
+  if (conserve && !std::isfinite(rcv)) return PACE_ERR_ARG;
+  const real* const fields[] = {u, v, w, pt};
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < a; ++b)
+      if (fields[a] == fields[b]) return PACE_ERR_ARG;
+  // the leading damped levels, then exactly 1.0 to the bottom
+  int kmax = 0;
+  while (kmax < geom->nk && factor[kmax] < 1.0) ++kmax;
+  for (int k = 0; k < geom->nk; ++k) {
+    if (!(factor[k] > 0.0 && factor[k] <= 1.0)) return PACE_ERR_ARG;  // (a NaN fails both)
+    if (k >= kmax && factor[k] != 1.0) return PACE_ERR_ARG;
+  }
+  if (kmax == 0) return PACE_OK;
+  return launch_rayleigh_super(make_geo(geom), *met, a11, a12, a21, a22, u, v, w, pt, factor, kmax, rcv, conserve, S(stream));
+}
+
 int pace_c2l_ord(const pace_geom_t* geom, const pace_metrics_t* met, int order, const real* u, const real* v,
                  const real* a11, const real* a12, const real* a21, const real* a22, real* ua, real* va,
                  void* stream) {

@@ -318,6 +318,9 @@ int launch_nudge(const Geo& g, const pace_nudge_item_t* items, int nitems, doubl
 int launch_held_suarez(const Geo& g, const pace_held_suarez_config_t& cfg, const real* pe, const real* ua, const real* va,
                        const real* pt, const real* sin2lat, const real* cos2lat, real* u_dt, real* v_dt, real* pt_dt, real* teq,
                        hipStream_t st);
+// k_rayleigh.hip
+int launch_rayleigh_super(const Geo& g, const Met& met, const real* a11, const real* a12, const real* a21, const real* a22, real* u,
+                          real* v, real* w, real* pt, const double* factor, int kmax, double rcv, int conserve, hipStream_t st);
 // k_energy.hip
 int launch_energy_columns(const Geo& g, int mode, const real* const* water, const real* pt, const real* delp, const real* delz,
                           const real* w, const real* u, const real* v, const real* pkz, const real* phis, const real* rsin2,

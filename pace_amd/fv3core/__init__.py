@@ -10,3 +10,4 @@ from .initialization.dycore_state import DycoreState  # noqa: F401,E402
 from .initialization.geos_wrapper import GeosDycoreWrapper  # noqa: F401,E402
 from .stencils.fv_dynamics import DynamicalCore  # noqa: F401,E402
 from .stencils.fv_subgridz import DryConvectiveAdjustment  # noqa: F401,E402
+from .stencils.rayleigh_super import RayleighSuper  # noqa: F401,E402

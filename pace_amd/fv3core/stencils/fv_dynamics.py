@@ -13,6 +13,7 @@ from .dyn_core import AcousticDynamics
 from .energy_fixer import EnergyFixer
 from .fillz import pointer_table, tracer_variables
 from .neg_adj3 import AdjustNegativeTracerMixingRatio
+from .rayleigh_super import RayleighSuper
 from .remapping import LagrangianToEulerian
 
 # fv_dynamics.py:33-37: 8 is the only supported value
@@ -95,6 +96,11 @@ class DynamicalCore(Operator):
         if self._conserve_total_energy > 0:
             transport = comm.comm if hasattr(comm, "comm") else comm
             self._energy_fixer = EnergyFixer(stencil_factory, quantity_factory, comm, total_tiles=transport.Get_size())
+        # Rayleigh_Super (rf_fast = false, tau > 0): the sponge damping of the whole step, with its heat; tau < 0 stays refused
+        self._rayleigh_super = None
+        if (not config.rf_fast) and config.tau > 0 and not config.hydrostatic:
+            self._rayleigh_super = RayleighSuper(stencil_factory, quantity_factory, grid_data, config.acoustic_dynamics.rf_cutoff,
+                                                 config.tau, self._ptop, conserve=True)
 
     def energy_fixer_diagnostics(self):
         """{"dtmp", "e_flux", "te_deficit", "zsum"} of the last step's total-energy fixer as Python floats -- dtmp [K per unit
@@ -153,8 +159,8 @@ class DynamicalCore(Operator):
     def compute_preamble(self, state, is_root_rank: bool):
         if self.config.hydrostatic:
             raise NotImplementedError("Hydrostatic is not implemented")
-        if (not self.config.rf_fast) and self.config.tau != 0:
-            raise NotImplementedError("Rayleigh_Super, called when rf_fast=False and tau !=0")
+        if (not self.config.rf_fast) and self.config.tau < 0:
+            raise NotImplementedError("Rayleigh_Super, called when rf_fast=False and tau < 0")
         if self.config.adiabatic and self.config.kord_tm > 0:
             raise NotImplementedError("unimplemented namelist options adiabatic with positive kord_tm")
         # fv_setup + the pt adjustment (fv_dynamics.py:446-487) in one pass
@@ -164,6 +170,9 @@ class DynamicalCore(Operator):
             gd = self.grid_data
             self._energy_fixer.total_energy(0, species, state.pt, state.delp, state.delz, state.w, state.u, state.v, None,
                                             state.phis, gd.rsin2, gd.cosa_s, None, self._te0_2d, constants.ZVIR)
+        if self._rayleigh_super is not None:
+            # after te0_2d (the Fortran takes te_2d first), while pt is still the temperature; dt is the whole step's
+            self._rayleigh_super(state.u, state.v, state.w, state.pt, abs(self._timestep))
         water = pointer_table(species)
         check_layout(self._geom, state.q_con, state.pkz, state.pt, self._cappa, state.delp, state.delz, self._dp_initial)
         self.call("pace_fv_setup_pt", water, dptr(state.q_con), dptr(state.pkz), dptr(state.pt), dptr(self._cappa),

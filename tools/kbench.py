@@ -22,6 +22,9 @@
     python tools/kbench.py --only held_suarez       the Held-Suarez forcing of a tile of the baroclinic state, accumulated into the
                                                     tendencies (one pace_held_suarez launch), against a torch restatement on
                                                     the device, the same way, with the launch alone and its bandwidth
+    python tools/kbench.py --only rayleigh_super    Rayleigh_Super (rf_fast = false) of a tile of the baroclinic state: the two launches of
+                                                    one pace_rayleigh_super against a torch restatement on the device, with the
+                                                    sponge's own levels and with every level damped; then --only held_suarez's lines
     python tools/kbench.py --only energy_fixer      the total-energy fixer of one tile (consv_te > 0): pace_energy_columns in both
                                                     modes and pace_energy_finalize against a torch restatement on the device, the
                                                     same way, with each launch alone and its bandwidth
@@ -103,6 +106,10 @@ def main():
         nudging_bench(lib, n, nz, args.reps)
         return
     if args.only == "held_suarez":  # (its own fields)
+        held_suarez_bench(lib, n, nz, args.reps)
+        return
+    if args.only == "rayleigh_super":  # (its own fields; then pace_held_suarez in the same job, for its GB/s)
+        rayleigh_super_bench(lib, n, nz, args.reps)
         held_suarez_bench(lib, n, nz, args.reps)
         return
     if args.only == "energy_fixer":  # (its own fields)
@@ -1370,6 +1377,85 @@ def held_suarez_bench(lib, n, nz, reps):
     launch = float(np.median(events))
     print(f"  the pace_held_suarez launch in device events: median {launch:.3f} ms (min {min(events):.3f}) = "
           f"{moved / (launch * 1e-3) / 1e9:.0f} GB/s over the algorithmic bytes")
+
+
+def rayleigh_super_bench(lib, n, nz, reps):
+    """RayleighSuper on tile 0 of the C<n> x <nz> baroclinic state (ONE pace_rayleigh_super: the heat launch, then the wind
+    launch), against the same expressions restated with torch on the device (views of the windows, updated in place, the
+    factors a device vector over the damped levels).  Two rows: the sponge of rf_cutoff = 3000 Pa, and every level damped
+    (rf_cutoff above the surface pressure).  Neither side synchronises; both are timed with the host clock from an idle device
+    to the end of a synchronisation added for the measurement, alternating, medians; then the call alone in device events, with
+    its bandwidth over the algorithmic bytes of the damped levels: u, v, w, pt read and pt, w written by the first launch, u, v
+    read and written by the second -- ten fields' worth.  Before the timing the two paths' results from the same state are
+    compared at this size.  The winds are damped again in every repetition: they shrink, the work does not."""
+    import time
+
+    from pace_amd.fv3core import RayleighSuper
+    from pace_amd.fv3core.initialization.baroclinic import baroclinic_state_six_tiles
+    from pace_amd.tile import Env
+    from pace_amd.util import constants, gridgen
+
+    tiles = gridgen.tiles(n, nz)
+    host = baroclinic_state_six_tiles(tiles, n, nz)[0]
+    env = Env(lib, "cuda", {k: v for k, v in tiles[0].items() if k not in ("ee1", "ee2", "es1", "ew2")}, n, nz)
+    gd, dims, dt = env.grid_data, ["x", "y", "z"], 225.0
+    rcv = 1.0 / (constants.CP_AIR - constants.RDGAS)
+    cs, up = slice(3, 3 + n), slice(4, 4 + n)
+    for label, cutoff in (("the sponge of rf_cutoff 3000 Pa", 3000.0), ("every level damped", 2.0e5)):
+        damping = RayleighSuper(env.stencil_factory, env.qf, gd, cutoff, 10.0, gd.ptop)
+        table = damping.factors(dt)
+        kmax = int((table < 1.0).sum())
+        mine = {name: env.qf.from_array(host[name], dims, "") for name in ("u", "v", "w", "pt")}
+        theirs = {name: env.qf.from_array(host[name], dims, "") for name in ("u", "v", "w", "pt")}
+        f = torch.as_tensor(np.array(table[:kmax]), dtype=torch.float64, device="cuda")
+        g = 1.0 - f * f
+        dx0, dx1, dy0, dy1 = (a.double()[:, :, None] for a in (gd.dx.data[cs, cs], gd.dx.data[cs, up], gd.dy.data[cs, cs], gd.dy.data[up, cs]))
+        a11, a12, a21, a22 = (getattr(gd, name).data[cs, cs, None].double() for name in ("a11", "a12", "a21", "a22"))
+        u, v, w, pt = (theirs[name].data for name in ("u", "v", "w", "pt"))
+        K = slice(0, kmax)
+
+        def hip():
+            damping(mine["u"], mine["v"], mine["w"], mine["pt"], dt)
+
+        def restated():
+            u1 = 2.0 * (u[cs, cs, K].double() * dx0 + u[cs, up, K].double() * dx1) / (dx0 + dx1)
+            v1 = 2.0 * (v[cs, cs, K].double() * dy0 + v[up, cs, K].double() * dy1) / (dy0 + dy1)
+            ua, va = a11 * u1 + a12 * v1, a21 * u1 + a22 * v1
+            wk = w[cs, cs, K].double()
+            pt[cs, cs, K] += ((0.5 * ((ua * ua + va * va) + wk * wk)) * g) * rcv
+            w[cs, cs, K] = f * wk
+            u[cs, 3:4 + n, K] = f * u[cs, 3:4 + n, K].double()
+            v[3:4 + n, cs, K] = f * v[3:4 + n, cs, K].double()
+
+        paths = {"hip": hip, "torch": restated}
+        hip()
+        restated()
+        torch.cuda.synchronize()
+        for name in ("u", "v", "w", "pt"):
+            a, b = mine[name].data.double(), theirs[name].data.double()
+            print(f"  {name}: max |hip - torch| {float((a - b).abs().max()):.3e} at max |torch| {float(b.abs().max()):.3e}")
+        times = {k: [] for k in paths}
+        for fn in paths.values():
+            for _ in range(3):
+                fn()
+        for _ in range(reps):
+            for k, fn in paths.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) * 1e3)
+        med = {k: float(np.median(t)) for k, t in times.items()}
+        moved = 10 * n * n * kmax * lib.real_bytes
+        print(f"rayleigh_super C{n} x {nz}, float{8 * lib.real_bytes} fields, {label}: {kmax} damped levels, {n * n * kmax} cells, "
+              f"{moved / 1e6:.1f} MB algorithmic; medians of {reps} alternating runs, ms")
+        for k in paths:
+            print(f"  {k:6s} {med[k]:9.3f} ms   (min {min(times[k]):.3f})")
+        print(f"  ratio torch / hip {med['torch'] / med['hip']:.2f}")
+        events = times_hip_calibrate(hip, reps)
+        launch = float(np.median(events))
+        print(f"  the two launches of pace_rayleigh_super in device events: median {launch:.3f} ms (min {min(events):.3f}) = "
+              f"{moved / (launch * 1e-3) / 1e9:.0f} GB/s over the algorithmic bytes")
 
 
 def energy_fixer_bench(lib, n, nz, reps):
